@@ -6,6 +6,8 @@
                                           # torch.distributed.run ...` on 127.0.0.1 and a free port) and relays their line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node G --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus G --steps K --warmup W      # the same under a launcher (RANK / WORLD_SIZE set)
+    python bench.py --full                # ... plus everything beyond the headline figure (baselines, other configs, checks)
+    python bench.py --dump-outputs DIR    # ... and the arrays of the last timed step as DIR/<name>.npy
 
 A "step" is one pass of the hot path over the synthetic wake held in HBM:
   * 1 GPU  (BASELINE config 3): one induced_velocity all-pairs call, N sources x N targets;
@@ -18,11 +20,19 @@ value = ordered pair interactions (self pairs count) of all ranks / wall time, m
 
 WHAT THE N = 1 AND THE N > 1 LINES COMPARE.  `value` at N = 1 is config 3 (N = 1e6: the configuration the metric is quoted
 on); `value` at N > 1 is config 4 (N = 8e6: the configuration that is sharded).  The same-work denominator for "8 GPUs vs 1"
-is therefore NOT the N = 1 line's `value` but its `config4_one_gpu.value` (config 4's step on the one GPU); every N > 1 line
-says so in `scaling_denominator`.
+is therefore NOT the N = 1 line's `value` but its `config4_one_gpu.value` (config 4's step on the one GPU; a --full line);
+every N > 1 line says so in `scaling_denominator`.
 
-Order of a run: CPU baseline (rank 0, N = 1 only) -> warmup -> the timed region of exactly --steps steps (barrier +
-synchronize on both sides) -> --repeats further regions of the same length, reported as `repeat_values` (box-to-box and
+A plain run (no --full) does what `value` needs and nothing else: set-up -> --warmup steps -> the timed region of exactly
+--steps steps (barrier + synchronize on both sides) -> with --dump-outputs DIR, what the last timed step computed (config 3:
+the induced velocities u, w of every target; config 4: the positions x, z of every vortex after the step), one float32
+DIR/<name>.npy each, outside the timed region; above DUMP_BYTES in all, the same fixed, seeded sample of indices of each
+array -> the line.  The inputs are seeded, so two builds given the same arguments can be compared output for output.
+
+--full adds everything else the benchmark measures or checks; each of its parts can also be switched on or off by its own
+option (--cpu-rows, --repeats, --cfg4-steps, --cfg5, --cfg2, --cfg1, --other-variant, --check, --sweep), which then holds
+with or without --full.  Order of a --full run: CPU baseline (rank 0, N = 1 only) -> warmup -> the timed region of exactly
+--steps steps -> --repeats further regions of the same length, reported as `repeat_values` (box-to-box and
 run-to-run spread; they also keep the GPU busy long enough for a 5-second utilisation sampler to see the run) -> at
 N = 1, --cfg4-steps steps of config 4's workload (N = 8e6) on the one GPU, reported as `config4_one_gpu`, then one leg per
 remaining BASELINE config, each outside `value` and each with its own check: `config5_flowfield` (4096 x 4096 grid over the
@@ -32,7 +42,8 @@ final wake, first LEV step and max |dCl| over the first 600 steps against the re
 tests/golden/g7_config2_first1500.npz) and `config1_readme` (the README case's wall time and `cpu_baseline_time_loop`: the same
 case by the oracle's restatement of the reference's time_loop on one host core).  ~25 s on top of the rest (--cfg5/2/1 0 skip).
 
-Config 4 (every N > 1 run) is a self-checking measurement, because nobody gets to debug it on the 8-GPU node:
+Config 4 (every N > 1 run) with --full is a self-checking measurement, because nobody gets to debug it on the 8-GPU node
+(the first item and the last are part of every run):
   * `config.collective_ms_per_rank` beside `config.pair_kernel_ms_per_rank` (HIP events on the launch stream around the
     collective alone: transfer + wait for the slowest rank's kernel), with max / mean of both;
   * after the timed region the OTHER step variant runs too -- `symmetric_variant` (one all-reduce of the fixed-point sums,
@@ -127,6 +138,30 @@ def synthetic_wake(n):
     z = rng.uniform(-2, 2, n)
     g = rng.standard_normal(n) / n
     return x.astype(np.float32), z.astype(np.float32), g.astype(np.float32)
+
+
+# the parts of a --full run beyond the headline figure, with their --full value (a plain run: 0 unless asked for by name)
+FULL_DEFAULTS = {"cpu_rows": 2048, "repeats": 3, "cfg4_steps": 2, "cfg5": 1, "cfg2": 1, "cfg1": 1,
+                 "other_variant": 1, "check": 1, "sweep": 1}
+DUMP_BYTES = 60_000_000     # --dump-outputs: array data in all, under 64 MB with the .npy headers
+DUMP_SEED = 20260102
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array of one length n} -> path/<name>.npy, float32 or float64 as computed.  Above DUMP_BYTES in
+    all, every array keeps the same fixed, seeded sample of indices (sorted), so that two runs compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a) for k, a in arrays.items()}
+    arrays = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for k, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_index = sum(a.dtype.itemsize for a in arrays.values())
+    idx = None
+    if n * per_index > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_BYTES // per_index, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a[idx])
+    print(f"bench.py: wrote {', '.join(arrays)} ({n if idx is None else f'a seeded sample of {len(idx)} of {n}'} values each) "
+          f"to {path}", file=sys.stderr, flush=True)
 
 
 def usable_cpus():
@@ -525,9 +560,13 @@ def parse_args(argv):
     ap.add_argument("--splits", type=int, default=0, help="source splits (0 = engine heuristic)")
     ap.add_argument("--symmetric", type=int, choices=[0, 1], default=1,
                     help="1: self-interaction launches use the symmetric kernel (each unordered pair once); 0: direct")
-    ap.add_argument("--cpu-rows", type=int, default=2048, help="targets in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the parts below marked [--full] default to their --full value")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; a seeded sample above DUMP_BYTES)")
+    ap.add_argument("--cpu-rows", type=int, default=None, help="[--full: 2048] targets in the CPU baseline sample (0 = skip)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work at most")
-    ap.add_argument("--repeats", type=int, default=3, help="further timed regions of --steps steps after the reported one")
+    ap.add_argument("--repeats", type=int, default=None, help="[--full: 3] further timed regions of --steps steps after the reported one")
     ap.add_argument("--collectives", choices=["auto", "torch", "library"], default="auto",
                     help="N > 1: who issues the step's collective -- the library's own RCCL communicator (default on nccl) or torch.distributed")
     ap.add_argument("--budget-s", type=float, default=300.0,
@@ -538,18 +577,24 @@ def parse_args(argv):
                          "phase must not take the measurement with it (0 = no limit)")
     ap.add_argument("--comm-init-timeout", type=float, default=90.0,
                     help="config 4: seconds the library's communicator may take to come up before torch.distributed takes over")
-    ap.add_argument("--other-variant", type=int, choices=[0, 1], default=1,
-                    help="config 4: also time the other step variant (direct <-> symmetric) after the reported one")
-    ap.add_argument("--check", type=int, choices=[0, 1], default=1,
-                    help="config 4: result check after the timed regions (cross-rank checksum + sampled oracle check)")
-    ap.add_argument("--sweep", type=int, choices=[0, 1], default=1,
-                    help="config 4: collective micro-sweep at the class-level sharding's threshold sizes after the checks (< 1 s)")
-    ap.add_argument("--cfg5", type=int, choices=[0, 1], default=1, help="N = 1: config 5's flow field (4096^2 x 1e6, ~2 s per call) after config 4's leg")
-    ap.add_argument("--cfg2", type=int, choices=[0, 1], default=1, help="N = 1: config 2's full 50 000-step time_loop (~11 s)")
-    ap.add_argument("--cfg1", type=int, choices=[0, 1], default=1, help="N = 1: config 1 (README case) + its CPU baseline by the oracle (~5 s of CPU)")
-    ap.add_argument("--cfg4-steps", type=int, default=2,
-                    help="N = 1: steps of config 4's workload (N = 8e6, ~7 s each) timed on the one GPU after the config-3 run (0 = skip)")
-    return ap.parse_args(argv)
+    ap.add_argument("--other-variant", type=int, choices=[0, 1], default=None,
+                    help="[--full: 1] config 4: also time the other step variant (direct <-> symmetric) after the reported one")
+    ap.add_argument("--check", type=int, choices=[0, 1], default=None,
+                    help="[--full: 1] config 4: result check after the timed regions (cross-rank checksum + sampled oracle check)")
+    ap.add_argument("--sweep", type=int, choices=[0, 1], default=None,
+                    help="[--full: 1] config 4: collective micro-sweep at the class-level sharding's threshold sizes after the checks (< 1 s)")
+    ap.add_argument("--cfg5", type=int, choices=[0, 1], default=None,
+                    help="[--full: 1] N = 1: config 5's flow field (4096^2 x 1e6, ~2 s per call) after config 4's leg")
+    ap.add_argument("--cfg2", type=int, choices=[0, 1], default=None, help="[--full: 1] N = 1: config 2's full 50 000-step time_loop (~11 s)")
+    ap.add_argument("--cfg1", type=int, choices=[0, 1], default=None,
+                    help="[--full: 1] N = 1: config 1 (README case) + its CPU baseline by the oracle (~5 s of CPU)")
+    ap.add_argument("--cfg4-steps", type=int, default=None,
+                    help="[--full: 2] N = 1: steps of config 4's workload (N = 8e6, ~7 s each) timed on the one GPU after the config-3 run (0 = skip)")
+    args = ap.parse_args(argv)
+    for key, full_value in FULL_DEFAULTS.items():     # a plain run: 0 for each part not asked for by name
+        if getattr(args, key) is None:
+            setattr(args, key, full_value if args.full else 0)
+    return args
 
 
 class Run:
@@ -777,6 +822,8 @@ def run_config3(R):
     R.M.update(elapsed=elapsed, kernel_ms=kernel_ms, launches=launches, pairs_per_step=pairs_per_step,
                pairs_per_launch=pairs_per_step, desc=desc, collective=None, coll_note=None, per_rank_ms=[kernel_ms],
                per_rank_coll_ms=None, ns_l=n, nt_l=n)
+    if args.dump_outputs and R.rank == 0:
+        dump_outputs(args.dump_outputs, {"u": du.cpu().numpy(), "w": dw.cpu().numpy()})
     if R.cpu_rec is not None:
         R.M["u_first"] = du[: len(R.cpu_u)].cpu().numpy().astype(np.float64)
         R.M["w_first"] = dw[: len(R.cpu_u)].cpu().numpy().astype(np.float64)
@@ -1051,6 +1098,8 @@ def run_config4(R):
 
     R.rep.phase = f"warm-up and the reported timed region (config 4, {variant} variant)"
     wake, main_rec, elapsed, kernel_ms, launches = run_variant(symmetric, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:          # (before the checks: they step the wake once more)
+        dump_outputs(args.dump_outputs, {"x": wake.xs[:n].cpu().numpy(), "z": wake.zs[:n].cpu().numpy()})
     desc = (f"config 4: synthetic wake N={n}, sharded over {world} GPU(s); per step: "
             + ("symmetric kernel on the rank's I-tile block of the unordered pairs + ONE all-reduce of the 64-bit "
                "fixed-point sums + replicated Euler update" if symmetric else

@@ -11,6 +11,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 from bench_checks import assert_self_checking_config4, assert_sweep
@@ -35,7 +36,7 @@ def _run(script, *args, env=None, timeout=600):
 def test_self_launched_ranks_rehearse_config4(ranks, n):
     """Plain `<bench> --gpus N`: N ranks come up, one line comes back.  17 000 vortices on 8 ranks: blocks of 4096 (whole
     quads of 512-vortex tiles), ranks 5-7 own nothing but padding; the bits are those of any other world size."""
-    p, lines = _run(RIG, "--gpus", str(ranks), "--vortices", str(n), "--steps", "1", "--warmup", "0", "--repeats", "0")
+    p, lines = _run(RIG, "--full", "--gpus", str(ranks), "--vortices", str(n), "--steps", "1", "--warmup", "0", "--repeats", "0")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -49,8 +50,8 @@ def test_self_launched_ranks_rehearse_config4(ranks, n):
     assert_self_checking_config4(d, ranks, min_value=1e6)
     assert_sweep(d, ranks, ["torch"])
     # the same wake on any number of ranks: the same bits (integer sums commute) -- what two ranks print for the same arguments
-    p2, lines2 = _run(RIG, "--gpus", "2", "--vortices", str(n), "--steps", "1", "--warmup", "0", "--repeats", "0", "--other-variant", "0",
-                      "--sweep", "0")
+    p2, lines2 = _run(RIG, "--full", "--gpus", "2", "--vortices", str(n), "--steps", "1", "--warmup", "0", "--repeats", "0",
+                      "--other-variant", "0", "--sweep", "0")
     assert p2.returncode == 0 and len(lines2) == 1, p2.stderr[-3000:]
     d2 = json.loads(lines2[0])
     assert d2["config"]["ranks"] == 2 and "collective_sweep_us" not in d2 and "direct_variant" not in d2
@@ -117,7 +118,8 @@ def test_ranks_do_not_outlive_a_killed_parent():
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=_env(LUDVM_BENCH_TEST_HANG="1"))
 
     def descendants(pid):
-        out = subprocess.run(["ps", "-e", "-o", "pid=,ppid=,args="], capture_output=True, text=True).stdout
+        # -ww: whole command lines (ps otherwise cuts them at $COLUMNS, and a long checkout path hides the script's name)
+        out = subprocess.run(["ps", "-ww", "-e", "-o", "pid=,ppid=,args="], capture_output=True, text=True).stdout
         rows = [l.split(None, 2) for l in out.splitlines() if len(l.split(None, 2)) == 3]
         kids, frontier = [], {str(pid)}
         while frontier:
@@ -154,3 +156,48 @@ def test_a_visible_devices_list_shorter_than_the_ranks_is_refused_before_anythin
     p, lines = _run(os.path.join(ROOT, "bench.py"), "--gpus", "4", env=_env(HIP_VISIBLE_DEVICES="0"))
     assert p.returncode == 2 and lines == [] and "needs one GPU per rank; HIP_VISIBLE_DEVICES=0 shows 1" in p.stderr
     assert "torch.distributed.run" not in p.stderr and time.time() - t0 < 10
+
+
+def test_a_plain_run_leaves_everything_beyond_the_headline_to_full():
+    """`bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times K steps and prints the line; --full switches on every
+    other part with the value it had before --full existed, and a part named on the command line holds either way."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert plain.steps == 5 and plain.warmup == 1 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, k) == 0 for k in bench.FULL_DEFAULTS)
+    full = bench.parse_args(["--full"])
+    assert {k: getattr(full, k) for k in bench.FULL_DEFAULTS} == {
+        "cpu_rows": 2048, "repeats": 3, "cfg4_steps": 2, "cfg5": 1, "cfg2": 1, "cfg1": 1, "other_variant": 1, "check": 1, "sweep": 1}
+    assert bench.parse_args(["--cpu-rows", "64"]).cpu_rows == 64 and bench.parse_args(["--full", "--cfg2", "0"]).cfg2 == 0
+
+
+def test_dumped_outputs_keep_a_fixed_sample_when_large(tmp_path):
+    """--dump-outputs: whole arrays up to bench.DUMP_BYTES in all; above it the same seeded indices of every array, run after run."""
+    import bench
+    n = bench.DUMP_BYTES // 8 + 1000
+    u = np.arange(n, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"u": u, "w": -u})
+    bench.dump_outputs(str(tmp_path / "b"), {"u": u, "w": -u})
+    a_u, a_w, b_u = (np.load(tmp_path / d / f) for d, f in (("a", "u.npy"), ("a", "w.npy"), ("b", "u.npy")))
+    assert a_u.dtype == np.float32 and a_u.nbytes + a_w.nbytes <= bench.DUMP_BYTES and len(a_u) > 0.99 * bench.DUMP_BYTES // 8
+    assert np.array_equal(a_u, b_u) and np.array_equal(a_w, -a_u) and np.all(np.diff(a_u) > 0)
+    small = np.linspace(0, 1, 1000)
+    bench.dump_outputs(str(tmp_path / "c"), {"u": small})
+    assert np.array_equal(np.load(tmp_path / "c" / "u.npy"), small)
+
+
+def test_a_plain_self_launched_run_dumps_the_positions_after_its_last_step(tmp_path):
+    """Config 4's plain line (two ranks): only the reported variant, no checks, no sweep, no repeats; with --dump-outputs rank 0
+    writes the positions x, z of every vortex after the last timed step."""
+    out = tmp_path / "outputs"
+    p, lines = _run(RIG, "--gpus", "2", "--vortices", "16384", "--steps", "2", "--warmup", "0", "--dump-outputs", str(out))
+    assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["repeat_values"] == [] and "incomplete" not in d
+    assert "symmetric_variant" in d and not any(k in d for k in ("direct_variant", "result_check", "collective_sweep_us"))
+    import bench
+    x0, z0, _ = bench.synthetic_wake(16384)
+    x, z = np.load(out / "x.npy"), np.load(out / "z.npy")
+    assert sorted(os.listdir(out)) == ["x.npy", "z.npy"] and x.dtype == z.dtype == np.float32 and x.shape == z.shape == (16384,)
+    assert np.isfinite(x).all() and np.isfinite(z).all() and not np.array_equal(x, x0)
+    assert np.abs(x - x0).max() < 0.1 and np.abs(z - z0).max() < 0.1

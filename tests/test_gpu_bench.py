@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from bench_checks import assert_other_configs, assert_self_checking_config4 as _assert_self_checking_config4, assert_sweep
@@ -27,7 +28,7 @@ def _run(*args):
 
 @pytest.mark.parametrize("symmetric", [1, 0])
 def test_bench_json_contract(symmetric):
-    d = _run("--vortices", "40000", "--steps", "3", "--warmup", "1", "--cpu-rows", "64", "--symmetric", str(symmetric))
+    d = _run("--full", "--vortices", "40000", "--steps", "3", "--warmup", "1", "--cpu-rows", "64", "--symmetric", str(symmetric))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -53,20 +54,40 @@ def test_bench_json_contract(symmetric):
     assert "error" not in a and a["cores"] >= 1 and a["value"] > 1e6 and a["vs_numpy_max_rel_diff"] < 1e-12
 
 
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full): the timed steps and the line, nothing else.  --dump-outputs writes what the last timed step
+    computed, u and w of every target, and they agree with the oracle on a sample (cpu_baseline's bound)."""
+    d = _run("--vortices", "40000", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert d["metric"] == "biot_savart_pair_interactions_per_s" and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["roofline"]["kernel_launches_timed"] == 3
+    assert abs(d["value"] - 40000.0**2 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["repeat_values"] == []
+    assert not any(k in d for k in ("cpu_baseline", "config4_one_gpu", "config5_flowfield", "config2_time_loop", "config1_readme"))
+    import bench
+    from oracle import ludvm_oracle as O
+    u, w = np.load(tmp_path / "u.npy"), np.load(tmp_path / "w.npy")
+    assert sorted(os.listdir(tmp_path)) == ["u.npy", "w.npy"] and u.dtype == w.dtype == np.float32 and u.shape == w.shape == (40000,)
+    x, z, g = (a.astype(np.float64) for a in bench.synthetic_wake(40000))
+    idx = np.sort(np.random.default_rng(3).choice(40000, 256, replace=False))
+    uo, wo = O.induced_velocity(g, x, z, x[idx], z[idx], bench.V_CORE)
+    scale = max(np.abs(uo).max(), np.abs(wo).max())
+    assert max(np.abs(u[idx] - uo).max(), np.abs(w[idx] - wo).max()) / scale < 1e-5
+
+
 def test_bench_line_carries_every_baseline_config():
     """the default N = 1 line (config 3 at N = 1e6, shortened here to 3 steps and without config 4's 15 s
     leg) also times config 5's flow field, config 2's full 50 000-step time_loop and the README case, each with its check."""
-    d = _run("--steps", "3", "--warmup", "1", "--repeats", "0", "--cpu-rows", "256", "--cpu-budget", "4", "--cfg4-steps", "0")
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--repeats", "0", "--cpu-rows", "256", "--cpu-budget", "4", "--cfg4-steps", "0")
     assert "config 3" in d["config"]["workload"] and d["config"]["n_vortices"] == 1_000_000 and "config4_one_gpu" not in d
     assert d["cpu_baseline"]["gpu_vs_oracle_max_rel_err"] < 1e-5
     assert_other_configs(d)
     # a run at another size, or with forced tuning, measures that one thing only
-    d = _run("--vortices", "40000", "--steps", "2", "--warmup", "1", "--repeats", "0", "--cpu-rows", "0")
+    d = _run("--full", "--vortices", "40000", "--steps", "2", "--warmup", "1", "--repeats", "0", "--cpu-rows", "0")
     assert not any(k in d for k in ("config5_flowfield", "config2_time_loop", "config1_readme"))
 
 
 def test_bench_config4_shape_on_one_gpu():
-    d = _run("--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0")
+    d = _run("--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0")
     assert d["scaling"] == "strong" and "config 4" in d["config"]["workload"] and "cpu_baseline" not in d
     assert d["value"] > 1e11
     # one rank, no process group: no collective is issued (times 0), everything else is there
@@ -75,7 +96,7 @@ def test_bench_config4_shape_on_one_gpu():
 
 
 def test_bench_config4_direct_variant_reported():
-    d = _run("--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--symmetric", "0")
+    d = _run("--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--symmetric", "0")
     assert d["config"]["kernel_variant"] == "direct"
     _assert_self_checking_config4(d, 1, main="direct", collectives_issued=False)
     assert d["symmetric_variant"]["value"] > d["direct_variant"]["value"] * 0.8
@@ -83,7 +104,7 @@ def test_bench_config4_direct_variant_reported():
 
 def test_bench_budget_drops_the_other_variant_and_the_repeats_first():
     """--budget-s too small for anything but the reported region: the line still comes, says what was skipped."""
-    d = _run("--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--budget-s", "1")
+    d = _run("--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--budget-s", "1")
     assert d["value"] > 1e11 and d["repeat_values"] == [] and "budget" in d["direct_variant"]["skipped"]
     assert d["result_check"]["symmetric"]["ranks_agree"] is True and "direct" not in d["result_check"]
 
@@ -91,14 +112,14 @@ def test_bench_budget_drops_the_other_variant_and_the_repeats_first():
 def test_bench_config4_through_the_library_communicator_on_one_rank():
     """The N > 1 bench path with the collective inside the library, on a one-rank communicator (real RCCL): the
     communicator is created, proven on a known sum, used by every step and destroyed; no fallback note."""
-    d = _run("--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0",
+    d = _run("--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0",
              "--collectives", "library")
     assert d["config"]["collective_note"] is None, d["config"]["collective_note"]
     assert "inside libludvm_hip.so" in d["config"]["collective"] and d["value"] > 1e11
     _assert_self_checking_config4(d, 1)          # ncclAllReduce AND ncclAllGather issued (one-rank identities), timed, checked
     assert_sweep(d, 1, ["library"])              # ... and the collective micro-sweep through the library's communicator
     assert "ONE rank" in d["collective_sweep_us"]["min_wake_rule"]
-    ref = _run("--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0",
+    ref = _run("--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1", "--cpu-rows", "0",
                "--collectives", "torch")
     assert "torch.distributed" in ref["config"]["collective"] and ref["config"]["collective_note"] is None
 
@@ -145,7 +166,7 @@ def test_bench_two_ranks_through_the_launcher():
     """The driver's launch line for N > 1 (python -m torch.distributed.run ... bench.py --gpus N), rehearsed with two
     ranks sharing the one card over gloo (LUDVM_BENCH_BACKEND): config 4's sharded step, MAX-over-ranks timing, one
     JSON line from rank 0."""
-    d = _launch(2, {"LUDVM_BENCH_BACKEND": "gloo"}, "--vortices", "120000", "--steps", "2", "--warmup", "1")
+    d = _launch(2, {"LUDVM_BENCH_BACKEND": "gloo"}, "--full", "--vortices", "120000", "--steps", "2", "--warmup", "1")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and "config 4" in d["config"]["workload"]
     assert d["config"]["collective_backend"] == "gloo" and d["config"]["kernel_variant"] == "symmetric"
     assert d["config"]["ranks"] == 2 and len(d["config"]["pair_kernel_ms_per_rank"]) == 2
@@ -173,7 +194,7 @@ def _self_launch(nproc, extra_env, *args, timeout=600):
 def test_bench_starts_its_own_ranks():
     """The driver's most natural command for N = 2: plain `python bench.py --gpus 2 ...` (two gloo ranks sharing the one
     card): one JSON line, two ranks."""
-    p, lines = _self_launch(2, {"LUDVM_BENCH_BACKEND": "gloo"}, "--vortices", "120000", "--steps", "2", "--warmup", "1")
+    p, lines = _self_launch(2, {"LUDVM_BENCH_BACKEND": "gloo"}, "--full", "--vortices", "120000", "--steps", "2", "--warmup", "1")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -188,7 +209,7 @@ def test_bench_starts_four_ranks_with_padded_owner_blocks(n):
     """Four self-launched gloo ranks on the one card (a GPU box allows six processes on its card; the eight-rank rehearsal
     is tests/test_bench_cpu_rehearsal.py, on the CPU): 200 000 vortices -- the last rank's block is partly padding;
     18 000 -- blocks of 6144, the last rank owns nothing but padding."""
-    p, lines = _self_launch(4, {"LUDVM_BENCH_BACKEND": "gloo"}, "--vortices", str(n), "--steps", "2", "--warmup", "1")
+    p, lines = _self_launch(4, {"LUDVM_BENCH_BACKEND": "gloo"}, "--full", "--vortices", str(n), "--steps", "2", "--warmup", "1")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -214,7 +235,7 @@ def test_self_launched_ranks_print_the_deadline_line():
 def test_self_launched_ranks_survive_a_communicator_join_that_never_returns():
     """... and the join watchdog with two ranks: both time out, agree on it through torch, go on with torch.distributed's
     collectives on fresh engines."""
-    p, lines = _self_launch(2, {"LUDVM_BENCH_BACKEND": "gloo", "LUDVM_BENCH_TEST_HANG_COMM": "1"}, "--vortices", "120000", "--steps", "2",
+    p, lines = _self_launch(2, {"LUDVM_BENCH_BACKEND": "gloo", "LUDVM_BENCH_TEST_HANG_COMM": "1"}, "--full", "--vortices", "120000", "--steps", "2",
                             "--warmup", "1", "--collectives", "library", "--comm-init-timeout", "3")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines
@@ -227,7 +248,7 @@ def test_self_launched_ranks_survive_a_communicator_join_that_never_returns():
 def test_bench_config4_one_rank_on_the_real_rccl_backend_with_torch_collectives():
     """One rank, process group on the real "nccl" backend (LUDVM_BENCH_FORCE_DIST=1), torch.distributed's collectives
     forced: the all-reduce and the all-gather of both variants are issued on RCCL, timed and checked."""
-    d = _launch(1, {"LUDVM_BENCH_FORCE_DIST": "1"}, "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1",
+    d = _launch(1, {"LUDVM_BENCH_FORCE_DIST": "1"}, "--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2", "--warmup", "1",
                 "--collectives", "torch")
     assert "torch.distributed" in d["config"]["collective"] and d["config"]["ranks"] == 1
     _assert_self_checking_config4(d, 1)
@@ -299,7 +320,7 @@ def test_bench_two_ranks_on_rccl_with_two_gpus():
         pytest.skip("needs two GPUs (RCCL ranks cannot share a card)")
     for sym in ("1", "0"):
         for coll in ("auto", "torch"):
-            d = _launch(2, {}, "--vortices", "200000", "--steps", "2", "--warmup", "1", "--symmetric", sym, "--collectives", coll)
+            d = _launch(2, {}, "--full", "--vortices", "200000", "--steps", "2", "--warmup", "1", "--symmetric", sym, "--collectives", coll)
             assert d["n_gpus"] == 2 and d["config"]["collective_backend"] == "nccl" and d["config"]["ranks"] == 2
             assert len(d["config"]["pair_kernel_ms_per_rank"]) == 2 and d["value"] > 1e11
             assert ("libludvm_hip" in d["config"]["collective"]) == (coll == "auto")
@@ -338,7 +359,7 @@ def test_bench_survives_a_communicator_join_that_never_returns():
     env = dict(os.environ, LUDVM_BENCH_TEST_HANG_COMM="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, HANG_RIG, "--workload", "cfg4", "--vortices", "60000", "--steps", "2",
+    p = subprocess.run([sys.executable, HANG_RIG, "--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2",
                         "--warmup", "1", "--cpu-rows", "0", "--collectives", "library", "--comm-init-timeout", "3"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -357,7 +378,7 @@ def test_bench_leaves_a_communicator_alone_that_joined_late():
     env = dict(os.environ, LUDVM_BENCH_TEST_HANG_COMM="late")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, HANG_RIG, "--workload", "cfg4", "--vortices", "60000", "--steps", "2",
+    p = subprocess.run([sys.executable, HANG_RIG, "--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2",
                         "--warmup", "1", "--cpu-rows", "0", "--collectives", "library", "--comm-init-timeout", "3"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -377,7 +398,7 @@ def test_bench_falls_back_when_the_first_collective_on_the_library_communicator_
     env = dict(os.environ, LUDVM_BENCH_TEST_HANG_COMM="raise")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, HANG_RIG, "--workload", "cfg4", "--vortices", "60000", "--steps", "2",
+    p = subprocess.run([sys.executable, HANG_RIG, "--full", "--workload", "cfg4", "--vortices", "60000", "--steps", "2",
                         "--warmup", "1", "--cpu-rows", "0", "--collectives", "library", "--comm-init-timeout", "30"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]

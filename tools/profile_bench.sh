@@ -10,8 +10,8 @@ P=gpurun_out/$1; shift
 EXTRA="$@"
 export TMPDIR=/tmp
 W=/tmp/ludvm_prof_$$; mkdir -p $W
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 $EXTRA > ${P}_bench.json 2>${P}_bench.err || { tail ${P}_bench.err; exit 1; }
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $W/ks -o ks -- python bench.py --steps 20 --warmup 5 --cfg4-steps 0 --cfg5 0 --cfg2 0 --cfg1 0 $EXTRA > ${P}_bench_under_rocprof.json 2>$W/ks.err || { tail $W/ks.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 $EXTRA > ${P}_bench.json 2>${P}_bench.err || { tail ${P}_bench.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $W/ks -o ks -- python bench.py --full --steps 20 --warmup 5 --cfg4-steps 0 --cfg5 0 --cfg2 0 --cfg1 0 $EXTRA > ${P}_bench_under_rocprof.json 2>$W/ks.err || { tail $W/ks.err; exit 1; }
 find $W/ks -name "*kernel_stats.csv" -exec cp {} ${P}_kernel_stats.csv \;
 pmc() {  # name counters...
   local name=$1; shift

@@ -4,7 +4,7 @@
     python tools/scaling_table.py line_n1.json line_n2.json ...      # files holding a bench line, or a driver record with "parsed"
 
 The N = 1 line's `value` is config 3 (N = 1e6) and the N > 1 lines' `value` is config 4 (N = 8e6): the same-work denominator of
-"G GPUs vs 1" is the N = 1 line's `config4_one_gpu.value` (bench.py, `scaling_denominator`).  Per line: pairs/s, ms per step,
+"G GPUs vs 1" is the N = 1 line's `config4_one_gpu.value` (bench.py --full, `scaling_denominator`).  Per line: pairs/s, ms per step,
 speed-up and efficiency against that denominator, the slowest rank's pair kernel and collective per step, both step variants, the
 result checks, and -- from the first line that carries it -- what the run says about the class-level sharding's thresholds."""
 import json
