@@ -11,7 +11,8 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_si
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libludvm_hip.so")
-# the measurement build (-DLUDVM_EXPERIMENTS: environment switches, forced kernel variants); Engine(lib_path=EXP_LIB_PATH)
+# the measurement build (the product's objects, with the two units that read switches compiled with -DLUDVM_EXPERIMENTS:
+# environment switches, forced kernel variants); Engine(lib_path=EXP_LIB_PATH)
 EXP_LIB_PATH = os.path.join(_HERE, "csrc", "libludvm_hip_exp.so")
 
 OK, E_ARG, E_HIP, E_NOMEM, E_NODEVICE, E_STATE, E_COMM = range(7)

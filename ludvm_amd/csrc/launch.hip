@@ -430,15 +430,6 @@ extern "C" {
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 
-#ifdef LUDVM_WAVE_TRACE
-int ludvm_debug_set_wave_trace(ludvm_ctx* c, unsigned long long* d_trace) {
-  if (!c) return LUDVM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(ludvm::g_wave_trace), &d_trace, sizeof(d_trace)));
-  return LUDVM_OK;
-}
-#endif
-
 int ludvm_fixed_point_probe(ludvm_ctx* c, const float* values, size_t n, int scale_log2, long long* units) {
   if (!c) return LUDVM_E_ARG;
   if (n && (!values || !units)) return fail(c, LUDVM_E_ARG, "null array");

@@ -466,10 +466,7 @@ pair_f64_few(PairArgs a) {
   // reads the same j of two groups' tiles in one instruction; TILE doubles apart they share a bank (1024 B = 4 x 64 banks):
   // SQ_LDS_BANK_CONFLICT was 10 % of this kernel's busy cycles in config 2 [MI355X, profiles/r04_config2_sizes_pmc_sq.csv].
   // Two doubles of padding per group move the groups 4 banks apart.  (Addresses only: the same bits.)
-#ifndef LUDVM_FEW_PAD
-#define LUDVM_FEW_PAD 2
-#endif
-  constexpr int kPad = LUDVM_FEW_PAD;
+  constexpr int kPad = 2;
   // few waves with a dependent launch waiting for them (the march's solve chain runs them beside a roll-up kernel that
   // keeps every SIMD's issue slots busy): they go first
   __builtin_amdgcn_s_setprio(3);

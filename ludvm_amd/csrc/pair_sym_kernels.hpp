@@ -269,22 +269,8 @@ __device__ __forceinline__ float dpp_rol1(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x134, 0xf, 0xf, false));
 }
 __device__ __forceinline__ f32x2 dpp_rol1(f32x2 v) { return (f32x2){dpp_rol1(v.x), dpp_rol1(v.y)}; }
-// The same move through the LDS crossbar (ds_bpermute_b32: no LDS memory involved) instead of the vector ALU: src4 = 4 *
-// ((lane + 1) % 64).  A DPP move costs 4 VALU issue cycles on gfx950 and the rotation loop is VALU-bound (16 of them per
-// rotation step of a 512-vortex tile = 3 % of its issue slots), so taking them off the VALU looked like 3 % -- measured
-// [MI355X] it LOSES 3-4 % (N = 1e6: 122.8 ms against 118-120 ms with DPP on the same box, profiles/
-// r03_rotation_through_lds_negative_result.txt): the accumulators come back after an LDS round trip that the next
-// half-step's first J-side FMAs wait for.  Kept as a build switch (-DLUDVM_SYM_ROTATE_LDS=1), off.
-#ifndef LUDVM_SYM_ROTATE_LDS
-#define LUDVM_SYM_ROTATE_LDS 0
-#endif
-__device__ __forceinline__ float lds_rol1(float v, int src4) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src4, __builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ f32x2 rol1(f32x2 v, int src4) {
-  if (LUDVM_SYM_ROTATE_LDS) return (f32x2){lds_rol1(v.x, src4), lds_rol1(v.y, src4)};
-  return dpp_rol1(v);
-}
+// The same move through the LDS crossbar (ds_bpermute_b32) measured 3-4 % slower [MI355X] and was removed:
+// profiles/r03_rotation_through_lds_negative_result.txt.
 
 // Packed targets.  A v_pk_* instruction pairs two SOURCES against one target, so the target operand is the same number
 // in both halves.  Instead of keeping every target twice ({x, x}: what hipcc does with a splat, re-made with v_mov
@@ -293,17 +279,8 @@ __device__ __forceinline__ f32x2 rol1(f32x2 v, int src4) {
 // SIMD instead of 2); the instruction count and the speed at the headline size are unchanged, 65-100 k vortices gain
 // ~2 % (profiles/r02_packed_targets_ab.txt).  hipcc does not select these forms itself; tools/ubench/opsel_check.hip
 // pins their semantics on the hardware.
-// LUDVM_SYM_PACK=0 builds the splat form (same bits), LUDVM_SYM_OCC8 is the occupancy the T = 8 kernel is compiled for.
-#ifndef LUDVM_SYM_PACK
-#define LUDVM_SYM_PACK 1
-#endif
-#ifndef LUDVM_SYM_OCC8
-#define LUDVM_SYM_OCC8 3
-#endif
-constexpr bool kPackTargets = LUDVM_SYM_PACK != 0;
 // {p[half], p[half]} - s
 __device__ __forceinline__ f32x2 pk_sub_sel(f32x2 p, f32x2 s, int half) {
-  if (!kPackTargets) return (half ? (f32x2){p.y, p.y} : (f32x2){p.x, p.x}) - s;
   f32x2 d;
   if (half) asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(p), "v"(s));
   else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(p), "v"(s));
@@ -314,7 +291,6 @@ __device__ __forceinline__ f32x2 pk_sub_sel(f32x2 p, f32x2 s, int half) {
 // assembly.  `after` must therefore be a value that ordinary code computed FROM s (the j-side strength s * gj): naming it
 // as an operand puts at least that instruction between the v_rsq and this one.
 __device__ __forceinline__ f32x2 pk_mul_sel(f32x2 s, f32x2 p, int half, f32x2 after) {
-  if (!kPackTargets) return s * (half ? (f32x2){p.y, p.y} : (f32x2){p.x, p.x});
   f32x2 d;
   if (half) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(d) : "v"(s), "v"(p), "v"(after));
   else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(d) : "v"(s), "v"(p), "v"(after));
@@ -374,13 +350,10 @@ __device__ __forceinline__ void slab_load(const float* l, int home4, f32x2 (&out
 // workgroup barrier per round.  Every wave of a workgroup runs the same number of tile-pair rounds (`per`), valid or
 // not, so the barriers are uniform.
 // RED = false (R = 1; hi+lo positions never use the 512-vortex tile): every wave adds its own partial sums.
-#ifdef LUDVM_WAVE_TRACE
-// measurement build only (tools/sym_wave_trace.py): every wave stores its start and end time (100 MHz clock)
-__device__ unsigned long long* g_wave_trace = nullptr;
-#endif
 // R = 0: mixed granularity -- a workgroup holds either four single-wave items or one four-wave item (sym_geometry).
+// 3 waves per SIMD: the 512-vortex tile at 158 VGPRs fits three.
 template <int T, bool HILO = false, int R = 1, bool RED = (R != 1)>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(T == 8 || HILO ? LUDVM_SYM_OCC8 : 4)))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(T == 8 || HILO ? 3 : 4)))
 pair_sym_f32(SymArgs a) {
   static_assert(T == 4 || T == 8, "T vortices per lane, read as T/4 ds_read_b128 per component");
   static_assert(R == 0 || R == 1 || R == 2 || R == 4, "waves per item");
@@ -409,9 +382,6 @@ pair_sym_f32(SymArgs a) {
     }
     if (a.diag_only) ysplit = 1;
   }
-#ifdef LUDVM_WAVE_TRACE
-  const unsigned long long trace_t0 = wall_clock64();
-#endif
   constexpr int H = T / 2;
   constexpr int kWaves = kBlock / 64;
   constexpr int kComp = HILO ? 5 : 3;
@@ -483,7 +453,7 @@ pair_sym_f32(SymArgs a) {
   if (d_hi > dtot + 1) d_hi = dtot + 1;
 
   // my targets.  The packed ops pair two SOURCES against one target; targets 2 h and 2 h + 1 share register pair h and
-  // op_sel broadcasts the wanted half (kPackTargets).
+  // op_sel broadcasts the wanted half.
   // Local origins: a vortex's offset is relative to the origin of its CLASS -- its 256-vortex block x its index parity
   // (pair_kernels.hpp).  Lane l holds vortices I W + l + 64 t: their index parity is the lane's, their block is t / 4.
   // A partner tile J is taken in NS = T / 4 passes, one per origin block q of J (plane q of the slab: 4 J vortices per
@@ -575,7 +545,6 @@ pair_sym_f32(SymArgs a) {
   // non-finite position or strength is a source (J member) of its own tile's diagonal round, where it poisons the I-side
   // sums of that tile's lanes -- so the J-side partials need no check of their own.
   float chk = 0.0f;
-  const int rot4 = ((lane + 1) & 63) * 4;   // lane l takes over from lane l + 1
   const int lane32x4 = ((lane + 32) & 63) * 4;
 
   // ---- tile pairs: each unordered pair once, both sides accumulated ------------------------------------------------
@@ -686,7 +655,7 @@ pair_sym_f32(SymArgs a) {
             }
             // hand the pass's J accumulators to the lane that meets the same J vortices next step (lane - 1)
 #pragma unroll
-            for (int mm = 0; mm < 2; ++mm) { bu[2 * q + mm] = rol1(bu[2 * q + mm], rot4); bw[2 * q + mm] = rol1(bw[2 * q + mm], rot4); }
+            for (int mm = 0; mm < 2; ++mm) { bu[2 * q + mm] = dpp_rol1(bu[2 * q + mm]); bw[2 * q + mm] = dpp_rol1(bw[2 * q + mm]); }
           }
         }
       }
@@ -699,11 +668,6 @@ pair_sym_f32(SymArgs a) {
     // 2m, 1: u of 2m+1, 2: w of 2m, 3: w of 2m+1}
     const int home = (lane + k_hi) & 63;
     if (diag) continue;        // (no barrier in this round)
-#ifdef LUDVM_SYM_BARRIER_PROBE
-    // measurement build only: what two workgroup barriers per round would cost the barrier-free single-wave items (the
-    // price of sharing a partner tile's J-side sums among the four waves of a workgroup)
-    if (!RED) { __syncthreads(); __syncthreads(); }
-#endif
     if (!RED || !shared) {
       if (valid) {
 #pragma unroll
@@ -766,13 +730,6 @@ pair_sym_f32(SymArgs a) {
     }
   }
   if (!(__builtin_fabsf(chk) < __builtin_inff())) atomicAdd(reinterpret_cast<unsigned long long*>(a.bad), 1ULL);
-#ifdef LUDVM_WAVE_TRACE
-  if (g_wave_trace && (threadIdx.x & 63) == 0) {
-    const long long wid = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    g_wave_trace[2 * wid] = trace_t0;
-    g_wave_trace[2 * wid + 1] = wall_clock64();
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -848,7 +805,7 @@ __host__ __device__ inline long long quad_blocks(long long i_count, int ysplit, 
 }
 
 template <int T>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LUDVM_SYM_OCC8)))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3)))
 pair_sym_quad_f32(SymArgs a) {
   static_assert(T == 8, "the quad variant is built for the 512-vortex tile");
   constexpr int H = T / 2, NS = T / 4;

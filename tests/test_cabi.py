@@ -55,6 +55,10 @@ def test_production_library_reads_no_experiment_switch():
     assert len(units) == 9          # context, launch, comm, order, induce, wake, march, flowfield + spatial_order (ctx.hpp)
     direct = [v for u in units for v in re.findall(r'std::getenv\("(\w+)"\)', open(u).read())]
     assert sorted(direct) == ["LUDVM_COMM_FORCE", "LUDVM_RCCL_LIB"], direct
+    # the measurement build recompiles only the units that read a switch (EXP_UNITS): a switch in any other unit would do nothing
+    readers = {os.path.basename(u)[:-4] for u in units if re.search(r"LUDVM_EXP_ENV|LUDVM_EXPERIMENTS", open(u).read())}
+    exp_units = re.search(r"^EXP_UNITS\s*=(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+    assert readers == set(exp_units), (readers, exp_units)
     for hdr in glob.glob(os.path.join(csrc, "*.hpp")):
         text = open(hdr).read()
         assert "getenv" not in text.replace("#define LUDVM_EXP_ENV(name) std::getenv(name)", ""), hdr
