@@ -18,6 +18,11 @@ Fixture groups:
   G7 config-2 regime  -- BASELINE config 2's parameters (dt = 1e-3, v_core = 1.3e-3) run by the reference itself for the
                          first 1500 steps (the full 50 000 do not fit its dense history): loads, circulations, LESP, the
                          onset of LEV shedding (step 1335) and three wake rows.
+  G8 fp32 routes      -- LUDVM.induced_velocity called unbound on sampled targets of the cases of oracle/g8_cases.py, which
+                         straddle every routing threshold of the fp32 pair kernels (direct / symmetric, T = 4 / 8, quad,
+                         tile sizes, targets per lane, grid patches, float64, hi+lo, Morton order).  Only outputs are
+                         stored: the inputs regenerate from the case table (its digest is kept per case).
+                             python oracle/gen_golden.py g8    # this group alone
 G2-G5 run the unmodified reference class with oracle/airfoils_standin on sys.path (zero camber,
 valid for the symmetric NACA0012 all BASELINE configs use).
 """
@@ -244,14 +249,54 @@ def g7_config2_regime():
           "reference wall %.0f s" % (time.time() - t0))
 
 
+def g8_fp32_routes():
+    """The G8 cases (oracle/g8_cases.py): the reference's pair sum on each case's sampled targets x all its sources."""
+    import time
+    if ROOT not in sys.path:
+        sys.path.append(ROOT)
+    from oracle import g8_cases as G8
+    t0 = time.time()
+
+    def ref(vc, g, xw, zw, xp, zp):
+        ns = types.SimpleNamespace(v_core=vc)
+        rows = max(1, (1 << 24) // max(len(xw), 1))          # ~8 temporaries of rows x len(xw) float64: <= ~1 GB
+        u, w = np.empty(len(xp)), np.empty(len(xp))
+        for a in range(0, len(xp), rows):
+            u[a:a + rows], w[a:a + rows] = REF.LUDVM.induced_velocity(ns, g, xw, zw, xp[a:a + rows], zp[a:a + rows])
+        return u, w
+
+    flat = {}
+    for c in G8.CASES:
+        inp = G8.inputs(c)
+        idx = G8.sample(c)
+        xp, zp = G8.targets(c, inp, idx)
+        u, w = ref(c["v_core"], inp["g"], inp["xs"], inp["zs"], xp, zp)
+        name = c["name"]
+        flat[f"{name}/idx"] = idx
+        flat[f"{name}/u"] = u
+        flat[f"{name}/w"] = w
+        flat[f"{name}/params"] = G8.params(c)
+        flat[f"{name}/sha256"] = G8.digest(inp)
+        if "foil_x" in inp:        # the second call of :1105-1106: the bound vortices on the same wake points
+            flat[f"{name}/u_foil"], flat[f"{name}/w_foil"] = ref(c["v_core"], inp["foil_g"], inp["foil_x"], inp["foil_z"], xp, zp)
+        print(f"G8 {name}: {len(idx)} x {c['ns']}  ({time.time() - t0:.0f} s)", flush=True)
+    path = os.path.join(OUT, "g8_fp32_routes.npz")
+    np.savez_compressed(path, **flat)
+    print("G8:", len(G8.CASES), "cases,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "g7":
         g7_config2_regime()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "g8":
+        g8_fp32_routes()
         sys.exit(0)
     g1_kernel_kats()
     g2_g3_g4_config1()
     g5_variants()
     g6_generators()
     g7_config2_regime()
+    g8_fp32_routes()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("total fixture bytes:", tot)

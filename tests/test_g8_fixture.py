@@ -1,0 +1,181 @@
+"""CPU tier of G8 (tests/golden/g8_fp32_routes.npz, oracle/g8_cases.py): the inputs regenerate, both oracles are pinned to
+the reference's numbers at the sizes where the fp32 routes change, and every pair of cases still straddles the library's
+threshold.  A threshold that moves fails here: move the case pair with it and regenerate G8 (python oracle/gen_golden.py g8).
+The GPU tier runs the same cases through the production entry points (tests/test_gpu_g8.py)."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import grouped, load_golden
+from oracle import c_oracle
+from oracle import g8_cases as G8
+from oracle import ludvm_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ludvm_amd", "csrc")
+REGEN = "regenerate G8 with the case pair at the new value (oracle/g8_cases.py, python oracle/gen_golden.py g8)"
+
+
+@pytest.fixture(scope="module")
+def g8():
+    return grouped(load_golden("g8_fp32_routes.npz"))
+
+
+def _targets(c, ref):
+    inp = G8.inputs(c)
+    return inp, G8.targets(c, inp, ref["idx"])
+
+
+def test_g8_inputs_regenerate_and_the_fixture_is_the_tables(g8):
+    assert sorted(g8) == sorted(G8.BY_NAME)
+    for c in G8.CASES:
+        ref = g8[c["name"]]
+        inp = G8.inputs(c)
+        assert np.array_equal(ref["sha256"], G8.digest(inp)), c["name"]
+        assert np.array_equal(ref["params"], G8.params(c)), c["name"]
+        assert np.array_equal(ref["idx"], G8.sample(c)), c["name"]
+        assert len(np.unique(ref["idx"])) == len(ref["idx"]) == (512 if c["nt"] == 512 else 256)
+        for k, v in inp.items():        # what every entry point is handed is exactly what the reference saw
+            assert v.dtype == np.float64 and np.array_equal(v, v.astype(np.float32).astype(np.float64)), (c["name"], k)
+        assert len(inp["xs"]) == c["ns"], c["name"]
+        if c["kind"] != "grid":
+            assert len(inp.get("xt", inp["xs"])) == c["nt"], c["name"]
+        if c["kind"] == "grid":
+            x1, z1 = G8.grid_axes(c)
+            assert (len(x1), len(z1)) == (c["nx"], c["nz"]) and c["nt"] == c["nx"] * c["nz"]
+            nx, nz = c["nx"], c["nz"]
+            corners = {0, nz - 1, (nx - 1) * nz, nx * nz - 1}
+            assert corners <= set(ref["idx"].tolist()), c["name"]
+        elif c["nt"] > 512:
+            assert np.array_equal(ref["idx"][:64], np.arange(64)) and np.array_equal(ref["idx"][-64:], np.arange(c["nt"] - 64, c["nt"]))
+
+
+def test_g8_python_oracle_is_bit_identical(g8):
+    """oracle/ludvm_oracle.py on every G8 case: the reference's arithmetic, so the same bits (rows are independent: chunked
+    by target rows as test_g1_row_chunking_is_bit_identical relies on)."""
+    for c in G8.CASES:
+        ref = g8[c["name"]]
+        inp, (xp, zp) = _targets(c, ref)
+        rows = max(1, (1 << 24) // c["ns"])
+        u, w = O.induced_velocity(inp["g"], inp["xs"], inp["zs"], xp, zp, c["v_core"], rows_per_chunk=rows)
+        assert np.array_equal(u, ref["u"]) and np.array_equal(w, ref["w"]), c["name"]
+        if "foil_x" in inp:
+            u, w = O.induced_velocity(inp["foil_g"], inp["foil_x"], inp["foil_z"], xp, zp, c["v_core"])
+            assert np.array_equal(u, ref["u_foil"]) and np.array_equal(w, ref["w_foil"]), c["name"]
+
+
+@pytest.mark.skipif(not c_oracle.available(), reason="oracle/libpair_oracle.so not built")
+def test_g8_c_oracle_matches_the_reference(g8):
+    """oracle/pair_oracle.c (what the GPU tests use at large N) within test_c_oracle_matches_goldens' bound: same terms, only
+    the order of the row sum differs."""
+    for c in G8.CASES:
+        ref = g8[c["name"]]
+        inp, (xp, zp) = _targets(c, ref)
+        srcs = [(inp["g"], inp["xs"], inp["zs"], "u", "w")]
+        if "foil_x" in inp:
+            srcs.append((inp["foil_g"], inp["foil_x"], inp["foil_z"], "u_foil", "w_foil"))
+        for g, xs, zs, ku, kw in srcs:
+            u, w = c_oracle.induced_velocity(g, xs, zs, xp, zp, c["v_core"])
+            scale = np.abs(g).sum()
+            bound = 1e-13 * max(1.0, np.abs(ref[ku]).max(), np.abs(ref[kw]).max()) * max(1.0, scale)
+            np.testing.assert_allclose(u, ref[ku], rtol=1e-11, atol=bound, err_msg=c["name"])
+            np.testing.assert_allclose(w, ref[kw], rtol=1e-11, atol=bound, err_msg=c["name"])
+
+
+def _library_constants():
+    launch = open(os.path.join(CSRC, "launch.hip")).read()
+    ctx = open(os.path.join(CSRC, "ctx.hpp")).read()
+
+    def one(pattern, text, conv=int):
+        m = re.findall(pattern, text)
+        assert len(m) == 1, (pattern, m)
+        return conv(m[0])
+    return {
+        "kSymMinN": one(r"constexpr long long kSymMinN = (\d+);", launch),
+        "kSymT8MinN": one(r"constexpr long long kSymT8MinN = (\d+);", launch),
+        "kPatch4MinTargets": 1 << one(r"constexpr long long kPatch4MinTargets = 1LL << (\d+);", launch),
+        "tpl2_min_targets": one(r"p\.tpl = nt >= (\d+) \? 2 : 1;", launch),
+        "kOrderMin": one(r"constexpr size_t kOrderMin = (\d+);", ctx),
+        "kSmallSidePairsF64": one(r"constexpr double kSmallSidePairsF64 = ([0-9.]+);", ctx, float),
+        "small_tile_max": one(r"long long small_tile_max = (\d+);", ctx),
+        "sym_quad_min_tiles": one(r"long long sym_quad_min_tiles = (\d+);", ctx),
+        "kMaxExtentOverCore": one(r"constexpr double kMaxExtentOverCore = ([0-9.]+);", ctx, float),
+        "kMaxExtentOverCoreCloud": one(r"constexpr double kMaxExtentOverCoreCloud = ([0-9.]+);", ctx, float),
+    }
+
+
+def _first_quad_size(tmp_path, t8, min_tiles):
+    """The smallest vortex count whose symmetric launch takes the quad variant under the default rule: T = 8, at least
+    `min_tiles` 512-vortex tiles, and items of one wave (launch.hip, launch_sym_tiles), from the library's sym_geometry."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    src = tmp_path / "quad.hip"
+    src.write_text('#include <cstdio>\n#include "pair_sym_kernels.hpp"\nint main() {\n'
+                   f'  for (long long n = {t8}; n < 4000000; ++n) {{\n'
+                   '    const ludvm::SymGeom g = ludvm::sym_geometry(n, 8, 0, 0);\n'
+                   '    const bool one_wave_items = g.rsplit == 1 || (g.rsplit == 0 && g.rbulk == 1);\n'
+                   f'    if (g.ntiles >= 16 && one_wave_items && g.ntiles >= {min_tiles}) {{ std::printf("%lld\\n", n); return 0; }}\n'
+                   '  }\n  return 1;\n}\n')
+    exe = tmp_path / "quad"
+    p = subprocess.run([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", f"-I{CSRC}", "-o", str(exe), str(src)],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, "no quad launch below 4e6 vortices"
+    return int(r.stdout.split()[0])
+
+
+def test_g8_pairs_straddle_the_librarys_thresholds(tmp_path):
+    """Each pair of G8 cases is (t - 1, t), t = the first size on the far side of the library's current threshold."""
+    k = _library_constants()
+    first = {
+        "small_tile_max": k["small_tile_max"] + 1,           # launch.hip make_plan: ns <= small_tile_max -> 256-source tiles
+        "kSymMinN": k["kSymMinN"],                           # use_symmetric: n >= kSymMinN
+        "kSymT8MinN": k["kSymT8MinN"],                       # sym_tile_t: n >= kSymT8MinN -> T = 8
+        "sym_quad_min_tiles": _first_quad_size(tmp_path, k["kSymT8MinN"], k["sym_quad_min_tiles"]),
+        "kOrderMin": k["kOrderMin"],                         # ludvm_induce_f64: min(ns, nt) < kOrderMin -> float64 / hi+lo
+        "kSmallSidePairsF64": int(k["kSmallSidePairsF64"] // 512) + 1,     # ns * 512 <= 2^28 -> float64 (512 targets)
+        "tpl2_min_targets": k["tpl2_min_targets"],           # make_plan: nt >= 131072 -> 2 targets per lane
+    }
+    for lo, hi, const in G8.PAIRS:
+        a, b = G8.BY_NAME[lo], G8.BY_NAME[hi]
+        key = "ns" if a["ns"] != b["ns"] else "nt"
+        t = first[const]
+        assert (a[key], b[key]) == (t - 1, t), f"{const} moved: the first size on its far side is now {t}; {REGEN}"
+    for c in G8.CASES:
+        if c["threshold"] is not None and c["threshold"][0] in k:
+            name, value = c["threshold"]
+            assert k[name] == value, f"{c['name']}: {name} is {k[name]}, the case table says {value}; {REGEN}"
+
+
+def test_g8_grid_and_extent_cases_sit_on_their_sides():
+    k = _library_constants()
+    ff = {n: G8.BY_NAME[n] for n in ("ff_default", "ff_small", "ff_fine", "ff_ragged")}
+    # 2 x 4 patch below kPatch4MinTargets grid points, 4 x 4 from there (launch.hip grid_patch_rows)
+    assert ff["ff_default"]["nt"] < k["kPatch4MinTargets"] <= ff["ff_fine"]["nt"], REGEN
+    assert ff["ff_default"]["ns"] > k["small_tile_max"] and ff["ff_fine"]["ns"] > k["small_tile_max"], REGEN
+    # 256-source tiles: at most small_tile_max sources and 65 536 grid points (make_plan)
+    assert ff["ff_small"]["ns"] <= k["small_tile_max"] and ff["ff_small"]["nt"] <= 65536, REGEN
+    # the patch kernels need rows of a multiple of 4 points; the generic grid path takes the others
+    assert ff["ff_ragged"]["nz"] % 4 != 0 and all(ff[n]["nz"] % 4 == 0 for n in ("ff_default", "ff_small", "ff_fine"))
+    # the first G8 flow field is the reference's default grid (flowfield(), LUDVM.py:1186)
+    assert (ff["ff_default"]["nx"], ff["ff_default"]["nz"]) == (500, 400)
+    # extent bounds: the host restatement of order.hip's decision puts each case on its side, with a margin
+    margin = {False: 0.05, True: 0.10}        # (Morton order on the device may differ from this estimate in its key rounding)
+    for c in G8.CASES:
+        if c["extent_side"] is None:
+            continue
+        inp = G8.inputs(c)
+        reordered, extent = G8.predicted_order(inp["xs"], inp["zs"])
+        assert reordered == c["reordered"], c["name"]
+        bound = k["kMaxExtentOverCoreCloud"] if reordered else k["kMaxExtentOverCore"]
+        ratio = extent / c["v_core"]
+        if c["extent_side"] == "above":
+            assert ratio > (1 + margin[reordered]) * bound, (c["name"], ratio, bound, REGEN)
+        else:
+            assert ratio < (1 - margin[reordered]) * bound, (c["name"], ratio, bound, REGEN)

@@ -706,10 +706,12 @@ def test_full_size_config3_properties(eng):
         eng.set_stream(None)
 
 
-@pytest.mark.parametrize("n", [16384, 16385, 20000, 40959, 40960, 40961, 65536 + 255, 98304, 98305, 131072, 131072 + 511, 200000])
+@pytest.mark.parametrize("n", [16384, 16385, 20000, 36863, 36864, 36865, 40959, 40960, 40961, 65536 + 255, 98304, 98305, 131072,
+                               131072 + 511, 200000, 327168, 327169])
 def test_symmetric_kernel_tile_edges(eng, n):
-    """Symmetric self-interaction at sizes around its tilings (256-vortex tiles below 40 960 vortices,
-    512 from there; odd and even tile counts, ragged last tile) against the C oracle and the direct kernel."""
+    """Symmetric self-interaction at sizes around its tilings (256-vortex tiles below 36 864 vortices (kSymT8MinN),
+    512 from there; the quad variant plus a diagonal launch from 640 tiles of 512, i.e. from 327 169 vortices; odd and even
+    tile counts, ragged last tile) against the C oracle and the direct kernel."""
     import torch
     rng = np.random.default_rng(n)
     x = rng.uniform(-10, 0, n).astype(np.float32)
