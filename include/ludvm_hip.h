@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LUDVM_ABI_VERSION 5
+#define LUDVM_ABI_VERSION 6
 
 enum {
   LUDVM_OK = 0,
@@ -362,6 +362,57 @@ int ludvm_march_setup(ludvm_ctx* ctx, int npan, int ncoef, const double* scalars
                       size_t kin_rows);
 int ludvm_march_run(ludvm_ctx* ctx, long long first_step, long long count, int precision, double* state, double* rows,
                     double* hist, size_t hist_nmax, const long long* anchors);
+
+/* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
+ *
+ * A parameter sweep (LESPcrit, k, alpha_max, dt, a gust vortex, 'Faure' / 'Ramesh') is `members` independent simulations,
+ * each far too small to fill the device.  ludvm_ensemble_run runs them all in ONE kernel launch: one workgroup per member,
+ * the whole time loop of LUDVM.py:659-1171 inside the kernel -- chord sums :746-751 / :921-931, Gamma_TEV :758-760 or Newton
+ * :683-739, LESP test :781, the 2x2 system :944-954 or Newton :807-914, Fourier coefficients :765-773, bound vorticity
+ * :987-1010, loads :1035-1090, roll-up :1095-1127, placement :672-681 / :788-800 -- all float64, with the pair arithmetic
+ * of LUDVM_PREC_F64, so a member differs from a run of its own through ludvm_march_run(LUDVM_PREC_F64) by summation
+ * order only.  Every sum is formed in an order that depends on the member's own data: a member's result bits do not
+ * depend on `members`, on its index, on the other members or on where it ran, and a call repeats bit for bit.
+ *
+ * npan and ncoef are common to the batch; everything else is per member m (packed host arrays):
+ *   scalars [members][12]     as ludvm_march_setup's; scalar_count = the number of doubles given, must be 12 members
+ *   tables  [members][T]      as ludvm_march_setup's, T = 8 npan + ncoef npan + (ncoef - 1) npan
+ *   kin     kin_rows rows     of 7 + 2 npan doubles as ludvm_march_setup's; member m owns rows [kin_off, kin_off + nt)
+ *   init    [members][LUDVM_ENSEMBLE_INIT_HEAD + ncoef]
+ *                             tev_x, lev_x, tev_z, lev_z of step 1 (:672-681, :788-800), LESPcrit, three reserved (0),
+ *                             then the Fourier coefficients of step 0 (:645-646)
+ *   free    3 free_count      the free vortices (:268-277): member m owns x[nfree] | z[nfree] | g[nfree] at double
+ *                             3 free_off
+ *   desc    [members][LUDVM_ENSEMBLE_DESC] integers
+ *                             nt (time levels: steps 1 .. nt - 1 are run), kin_off (rows), nfree, free_off (vortices),
+ *                             row_off (rows of `rows`), wake_off (doubles of `wakes`)
+ *   snap_steps[nsnap]         strictly increasing steps >= 1, common to the batch, after which the wake is recorded;
+ *                             steps beyond a member's nt - 1 are skipped for it
+ * Outputs (host):
+ *   rows    rows_count rows   of 12 + 2 ncoef + 2 npan doubles, exactly ludvm_march_run's row layout; member m's step s is
+ *                             row row_off + s - 1
+ *   wakes   wake_doubles      member m owns nsnap + 1 records of x[cap] | z[cap] | g[cap] from wake_off on, cap =
+ *                             nfree + 2 (nt - 1): the wake in shedding order (free vortices first) after each snapshot step
+ *                             and, last, after step nt - 1
+ *   wake_n  [members][nsnap + 1]  the number of vortices in each record, -1 for a skipped snapshot.
+ * Limits (ludvm_ensemble_limits returns them as max_steps, max_wake, max_snapshots): 1 <= npan <= 256, 4 <= ncoef <= 64,
+ * nt - 1 <= LUDVM_ENSEMBLE_MAX_STEPS, cap <= LUDVM_ENSEMBLE_MAX_WAKE, nsnap <= LUDVM_ENSEMBLE_MAX_SNAPSHOTS: a member's
+ * workgroup then stays around a second.  Everything -- the limits, every member's ranges inside the arrays given, the Newton
+ * controls of a 'Ramesh' member -- is checked before anything is launched: LUDVM_E_ARG, the message names the member.
+ * members = 0 is valid and does nothing.  Synchronous.  The call uses device buffers of its own: the resident wake, the
+ * state of ludvm_march_setup, tuning, stream, shard and communicator of the context are as before it.  A sharded context
+ * (ludvm_set_shard / ludvm_comm_init with world > 1) answers LUDVM_E_STATE: members are independent, a caller with several
+ * devices splits the list. */
+#define LUDVM_ENSEMBLE_MAX_STEPS 2048
+#define LUDVM_ENSEMBLE_MAX_WAKE 8192
+#define LUDVM_ENSEMBLE_MAX_SNAPSHOTS 1024
+#define LUDVM_ENSEMBLE_INIT_HEAD 8
+#define LUDVM_ENSEMBLE_DESC 6
+int ludvm_ensemble_limits(ludvm_ctx* ctx, long long* limits3);
+int ludvm_ensemble_run(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n);
 
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 

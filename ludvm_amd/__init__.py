@@ -14,6 +14,7 @@ _prepare_ipc_environment()      # (a launcher announced several ranks: the IPC m
 from ._ffi import LudvmHipError  # noqa: F401,E402
 from .engine import Engine  # noqa: F401,E402
 from .ludvm import LUDVM, SparseHistory  # noqa: F401,E402
+from .ensemble import sweep  # noqa: F401,E402
 from .freevort import (generate_free_vortices, generate_free_single_vortex, generate_flowfield_vortices,  # noqa: F401,E402
                        generate_flowfield_turbulence)
 

@@ -1,8 +1,8 @@
 // Shared by the translation units of libludvm_hip.so: the context, error plumbing, the staging arena, and the internal
 // host functions one unit offers the others.  Kernels are NOT here: templates and device helpers live in pair_kernels.hpp /
 // pair_sym_kernels.hpp (includable anywhere); every non-template kernel lives in a header that exactly one unit includes
-// (sym_prepare_kernels.hpp -> launch.hip, induce_kernels.hpp -> induce.hip, wake_kernels.hpp -> wake.hip, march_kernels.hpp ->
-// march.hip, field_kernels.hpp -> flowfield.hip, order_kernels.hpp -> order.hip).
+// (sym_prepare_kernels.hpp -> launch.hip, induce_kernels.hpp -> induce.hip, wake_kernels.hpp -> wake.hip, march_kernels.hpp and
+// ensemble_kernels.hpp -> march.hip, field_kernels.hpp -> flowfield.hip, order_kernels.hpp -> order.hip).
 //
 //   context.hip    lifecycle, streams, tuning, the error string, staging copies            (ludvm_create ... ludvm_set_symmetric)
 //   launch.hip     plans and launches of the pair kernels, direct and symmetric; timing    (internal; ludvm_kernel_time_ms)
@@ -10,7 +10,7 @@
 //   order.hip      spatial order of unordered inputs                                       (ludvm_spatial_order)
 //   induce.hip     stateless pair sums, the multi-GPU shard step's entry points            (ludvm_induce_*, ludvm_advect_dev_f32, ludvm_sym_*)
 //   wake.hip       the resident wake and its roll-up                                       (ludvm_wake_*)
-//   march.hip      the device-resident time march                                          (ludvm_march_*)
+//   march.hip      the device-resident time march; the ensemble of small simulations       (ludvm_march_*, ludvm_ensemble_*)
 //   flowfield.hip  flow-field grids and the vorticity stencil                              (ludvm_flowfield_*, ludvm_vorticity_*)
 #pragma once
 #pragma GCC visibility push(default)          // the C ABI is what the library exports; everything else is hidden (-fvisibility=hidden)
@@ -107,6 +107,10 @@ struct ludvm_ctx {
   hipEvent_t march_ev[2] = {nullptr, nullptr};
   hipStream_t stream_b = nullptr;              // the solve chain beside the roll-up (overlapped march steps)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+
+  // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
+  // that a sweep leaves the resident wake and the march's state alone
+  Buf ens_in, ens_work, ens_out;
 
   // sharded roll-up (ludvm_set_shard): this context evaluates tile block `shard_rank` of `shard_world`; the hook sums
   // the fixed-point accumulators over the contexts / processes before every Euler finisher

@@ -1,0 +1,364 @@
+// Ensemble of small simulations (LUDVM.time_loop, reference LUDVM.py:597-1171, run many times at once): ONE workgroup owns
+// one member and runs all of its time steps inside the kernel, __syncthreads() between the phases of a step.  A member of
+// the README size (400 steps, wake <= ~800 vortices) is a chain of tiny dependent launches when it runs alone
+// (march_kernels.hpp); here it is one CU's worth of fp64 work and up to a few hundred members run side by side.
+//
+// Per time step s = 1 .. nt - 1 of a member, all float64, the mathematics of march_chord_finish / march_solve / the fp64
+// roll-up (march_kernels.hpp has the map to the reference's lines):
+//   1. chord sums      wake -> the npan + 1 targets (chord points of the step and the origin; the two placements, which the
+//                      solo march adds for its overlapped steps, are not needed: the roll-up below treats the shed
+//                      vortices like every other), the source tile staged through LDS; few targets: lane = (target,
+//                      slice of the tile), slices summed in order
+//   2. solve           T1 / T2 / T3, Gamma_TEV, LESP test, Gamma_LEV, Fourier coefficients, bound vorticity, loads; the
+//                      shed vortices join the member's wake slab, the bound vortices are staged behind them
+//   3. roll-up         every wake vortex <- wake + bound vortices, explicit Euler.  Positions are double-buffered: every
+//                      velocity is computed from the pre-step buffer and the new positions go to the other one, so no
+//                      position a pair still has to read is ever overwritten
+//   4. placement       of the next step's TEV / candidate LEV by the threads that have just moved the newest vortices;
+//                      snapshot of the wake on the listed steps and after the last one
+//
+// Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
+// walks the sources in index order; the fixed trees of block_sum_n; slices combined in slice order).  No atomics, nothing
+// is shared between workgroups, no workgroup waits for another: a member's bits do not depend on the batch, on its index
+// in it, or on the CU it ran on.  Pair arithmetic is pair_f64's, so a member differs from a solo precision='f64' run by
+// summation order only.
+#pragma once
+#include "march_kernels.hpp"
+
+namespace ludvm {
+
+constexpr int kEnsTile = kBlock;        // sources staged per pass: 3 x 2 KiB of LDS
+constexpr int kEnsSlicesMax = 4;        // few targets: up to this many lanes share a target, each walking a slice of the tile
+constexpr int kEnsInitHead = 8;         // init row: tev_x, lev_x, tev_z, lev_z, LESPcrit, 3 reserved, then A[ncoef] of step 0
+
+// Everything a member's workgroup needs, one record per member in a device array indexed by blockIdx.x.
+struct EnsembleMember {
+  MarchSetup m;                 // scalars and (device) table pointers of this member
+  const double* kin;            // nt kinematics rows [alpha, alpha_dot, h_dot, te_x, te_z, le_x, le_z, xg[npan], zg[npan]]
+  const double* init;           // kEnsInitHead + ncoef doubles
+  const double* free_x; const double* free_z; const double* free_g;
+  long long nt;                 // time levels: steps 1 .. nt - 1 are run
+  long long nfree;
+  long long cap;                // nfree + 2 (nt - 1): the most vortices the wake can hold
+  double* xa; double* za;       // wake slab, positions double-buffered (cap + npan each) ...
+  double* xb; double* zb;
+  double* g;                    // ... and circulations (cap + npan)
+  double* rows;                 // nt - 1 rows of kMarchRowHead + 2 ncoef + 2 npan doubles
+  double* rec;                  // nsnap + 1 wake records of x[cap] | z[cap] | g[cap]: the snapshot steps, then the last step
+  long long* rec_n;             // ... and their sizes (-1: the member has no such step)
+};
+
+// One Vatistas pair, pair_f64's arithmetic
+__device__ __forceinline__ void ens_pair(double xp, double zp, double xs, double zs, double gs, double vc4, double& au, double& aw) {
+  const double dx = xp - xs;
+  const double dz = zp - zs;
+  const double r2 = __builtin_fma(dz, dz, dx * dx);
+  const double q = __builtin_fma(r2, r2, vc4);
+  const double s = gs * rsqrt_f64(q);
+  au = __builtin_fma(dz, s, au);
+  aw = __builtin_fma(dx, s, aw);
+}
+
+// fp64 Vatistas sums of sources [0, ns) at this lane's target, sources staged through LDS in tiles (lx, lz, lg hold
+// kEnsTile + kEnsGroup doubles each); every lane with `mine` adds the sources in index order.  Raw sums: the caller scales
+// by kInv2PiD.
+//   SLICED = false (the roll-up: a target per lane)  the lane walks the whole tile, four sources at a time with the next
+//                  four already on their way from LDS -- a workgroup has ONE wave per SIMD, nothing else hides that latency.
+//                  The tile is padded to a multiple of four with far-away zero-strength sources, which add exactly 0.
+//   SLICED = true  (few targets: `slices` lanes per target)  the lane walks slice `slice` of every tile.
+constexpr int kEnsGroup = 4;
+template <bool SLICED>
+__device__ __forceinline__ void ens_pair_sums(const double* __restrict__ xs, const double* __restrict__ zs,
+                                              const double* __restrict__ gs, long long ns, double xp, double zp, double vc4,
+                                              bool mine, int slice, int slices, double* lx, double* lz, double* lg, double& au,
+                                              double& aw) {
+  const int tid = threadIdx.x;
+  const int sub = (kEnsTile + slices - 1) / slices;
+  au = 0.0; aw = 0.0;
+  for (long long base = 0; base < ns; base += kEnsTile) {
+    const int cnt = (int)(ns - base < kEnsTile ? ns - base : kEnsTile);
+    const int cnt_pad = (cnt + kEnsGroup - 1) / kEnsGroup * kEnsGroup;
+    __syncthreads();
+    if (tid < cnt_pad) {
+      const bool ok = tid < cnt;
+      lx[tid] = ok ? xs[base + tid] : kPadPosD; lz[tid] = ok ? zs[base + tid] : kPadPosD; lg[tid] = ok ? gs[base + tid] : 0.0;
+    }
+    __syncthreads();
+    if (!mine) continue;
+    if (SLICED) {
+      const int j0 = slice * sub;
+      int j1 = j0 + sub;
+      if (j1 > cnt) j1 = cnt;
+#pragma unroll 4
+      for (int j = j0; j < j1; ++j) ens_pair(xp, zp, lx[j], lz[j], lg[j], vc4, au, aw);
+    } else {
+      double cx[kEnsGroup], cz[kEnsGroup], cg[kEnsGroup];
+#pragma unroll
+      for (int k = 0; k < kEnsGroup; ++k) { cx[k] = lx[k]; cz[k] = lz[k]; cg[k] = lg[k]; }
+      for (int j = 0; j < cnt_pad; j += kEnsGroup) {
+        double nx[kEnsGroup], nz[kEnsGroup], ng[kEnsGroup];
+#pragma unroll
+        for (int k = 0; k < kEnsGroup; ++k) { nx[k] = lx[j + kEnsGroup + k]; nz[k] = lz[j + kEnsGroup + k]; ng[k] = lg[j + kEnsGroup + k]; }
+#pragma unroll
+        for (int k = 0; k < kEnsGroup; ++k) ens_pair(xp, zp, cx[k], cz[k], cg[k], vc4, au, aw);
+#pragma unroll
+        for (int k = 0; k < kEnsGroup; ++k) { cx[k] = nx[k]; cz[k] = nz[k]; cg[k] = ng[k]; }
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+ensemble_march(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap) {
+  __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
+  __shared__ __attribute__((aligned(16))) double lz[kEnsTile + kEnsGroup];
+  __shared__ __attribute__((aligned(16))) double lg[kEnsTile + kEnsGroup];
+  __shared__ double pu[kEnsSlicesMax - 1][kBlock / 2], pw[kEnsSlicesMax - 1][kBlock / 2];
+  __shared__ double Wn[kMarchMaxPan];
+  __shared__ double A[kMarchMaxCoef], Ad[kMarchMaxCoef], prevA[kMarchMaxCoef];
+  __shared__ double scratch[4 * 8];
+  __shared__ double place[4];           // coming step: tev_x, lev_x, tev_z, lev_z
+  __shared__ double pvel[2];            // what the wake induces at the origin: u, w
+
+  const EnsembleMember& E = members[blockIdx.x];
+  const MarchSetup m = E.m;
+  const int j = threadIdx.x;
+  const int npan = m.npan, ncoef = m.ncoef, ntt = npan + 1;
+  const bool on = j < npan;
+  const double pi = 3.14159265358979323846;
+  const long long nt = E.nt, cap = E.cap;
+  const size_t krow = 7 + 2 * (size_t)npan;
+  const size_t row_doubles = kMarchRowHead + 2 * (size_t)ncoef + 2 * (size_t)npan;
+  double* xc = E.xa; double* zc = E.za;      // positions before the step
+  double* xn_ = E.xb; double* zn_ = E.zb;    // ... and after it
+  double* g = E.g;
+  const bool ramesh = m.method == 1;
+  const double ucpi = m.U * m.chord * pi;
+
+  // step 0: the free vortices are the wake; state of the march as ludvm_march_run takes it from its caller
+  for (long long i = j; i < E.nfree; i += kBlock) { xc[i] = E.free_x[i]; zc[i] = E.free_z[i]; g[i] = E.free_g[i]; }
+  if (j < ncoef) prevA[j] = E.init[kEnsInitHead + j];
+  if (j < 4) place[j] = E.init[j];
+  if (j <= nsnap) E.rec_n[j] = -1;
+  for (int r = kBlock + j; r <= nsnap; r += kBlock) E.rec_n[r] = -1;
+  long long n = E.nfree;
+  double lesp_crit = E.init[4], sum_tev = 0.0, sum_lev = 0.0;
+  int snap_i = 0;
+  __syncthreads();
+
+  for (long long step = 1; step < nt; ++step) {
+    const double* kin = E.kin + (size_t)step * krow;
+    const double* xg = kin + 7;
+    const double* zg = kin + 7 + npan;
+    const double tev_x = place[0], lev_x = place[1], tev_z = place[2], lev_z = place[3];
+
+    // ---- 1. chord sums: wake -> chord points and the origin (:746, :751, :921-931, :1112-1118) ----------------------------
+    double u1 = 0, w1 = 0;
+    for (int t0 = 0; t0 < ntt; t0 += kBlock) {
+      const int cnt = ntt - t0 < kBlock ? ntt - t0 : kBlock;
+      int slices = kBlock / cnt;
+      if (slices > kEnsSlicesMax) slices = kEnsSlicesMax;
+      const int slice = j / cnt, p = t0 + (j - slice * cnt);
+      const bool mine = slice < slices;
+      double xp = 0.0, zp = 0.0;
+      if (p < npan) { xp = xg[p]; zp = zg[p]; }          // (p = npan: the origin)
+      double au, aw;
+      ens_pair_sums<true>(xc, zc, g, n, xp, zp, m.vc4, mine, slice, slices, lx, lz, lg, au, aw);
+      double su = au * kInv2PiD, sw = -aw * kInv2PiD;
+      __syncthreads();                               // (pu / pw of the previous pass have been read)
+      if (mine && slice > 0) { pu[slice - 1][p - t0] = su; pw[slice - 1][p - t0] = sw; }
+      __syncthreads();
+      if (slice == 0) {
+        for (int q = 1; q < slices; ++q) { su += pu[q - 1][p - t0]; sw += pw[q - 1][p - t0]; }
+        if (p < npan) { u1 = su; w1 = sw; }          // (t0 = 0: thread p keeps chord point p)
+        else { pvel[0] = su; pvel[1] = sw; }
+      }
+    }
+    __syncthreads();
+    const double puo = pvel[0], pwo = pvel[1];
+
+    // ---- 2. solve (march_solve's arithmetic; the state lives in registers and LDS) --------------------------------------------
+    const double al = kin[0], ald = kin[1], hd = kin[2];
+    const double ca = cos(al), sa = sin(al);
+    double ut1 = 0, wt1 = 0, ul1 = 0, wl1 = 0, dedx = 0, cm1 = 0, wq = 0;
+    if (on) {
+      unit_pair_f64(xg[j], zg[j], tev_x, tev_z, m.vc4, ut1, wt1);     // unit TEV / candidate LEV at the chord points
+      unit_pair_f64(xg[j], zg[j], lev_x, lev_z, m.vc4, ul1, wl1);
+      dedx = m.detadx[j]; cm1 = m.cm1[j]; wq = m.wq[j];
+    }
+    double t1 = 0, t2 = 0, t3 = 0;
+    if (on) {
+      const double u = u1 * ca - w1 * sa, w = u1 * sa + w1 * ca;
+      t1 = dedx * (m.U * ca + hd * sa + u - ald * m.eta[j]) - m.U * sa - ald * (m.xpan[j] - m.piv) + hd * ca - w;
+      const double ut = ut1 * ca - wt1 * sa, un = ut1 * sa + wt1 * ca;
+      t2 = dedx * ut - un;
+      const double ult = ul1 * ca - wl1 * sa, uln = ul1 * sa + wl1 * ca;
+      t3 = dedx * ult - uln;
+    }
+    double ij[6] = {t1 * cm1, t2 * cm1, t3 * cm1, t1 * wq, t2 * wq, t3 * wq};
+    block_sum_n<6>(ij, scratch);
+    const double I1 = ij[0], I2 = ij[1];
+    const double kelvin = sum_tev + sum_lev + m.kelvin0;
+    RameshProj rp{};
+    double g_tev;
+    if (ramesh) {
+      const double c0 = on ? m.cproj[j] / m.U : 0.0, c1 = on ? m.cproj[npan + j] / m.U : 0.0;
+      double pr[6] = {t1 * c0, t2 * c0, t3 * c0, t1 * c1, t2 * c1, t3 * c1};
+      block_sum_n<6>(pr, scratch);
+      rp.p0[0] = pr[0]; rp.p0[1] = pr[1]; rp.p0[2] = pr[2];
+      rp.p1[0] = pr[3]; rp.p1[1] = pr[4]; rp.p1[2] = pr[5];
+      rp.ucpi = ucpi;
+      rp.kelvin = kelvin;
+      g_tev = ramesh_tev(rp, m.maxerror, m.maxiter, m.epsilon);
+    } else {
+      g_tev = -(I1 + kelvin) / (1 + I2);               // :758-760
+    }
+    double g_lev = 0.0;
+    if (on) Wn[j] = (t1 + g_tev * t2) / m.U;
+    __syncthreads();
+    if (j < ncoef) {
+      double acc = 0.0;
+      const double* cp = m.cproj + (long long)j * npan;
+      for (int q = 0; q < npan; ++q) acc = __builtin_fma(cp[q], Wn[q], acc);
+      A[j] = acc;
+      Ad[j] = (acc - prevA[j]) / m.dt;                 // :772-773
+    }
+    __syncthreads();
+    double bound = ramesh ? ucpi * (A[0] + A[1] / 2) : I1 + g_tev * I2;     // :761 / :738
+    const double lesp_prev = A[0];
+    const bool shed = fabs(A[0]) >= fabs(lesp_crit);   // :781
+    __syncthreads();                                   // everyone has read A[0] before it is rewritten
+    if (shed) {
+      lesp_crit = A[0] < 0 ? -fabs(lesp_crit) : fabs(lesp_crit);     // :802-805
+      const double I3 = ij[2];
+      const double J1 = -1 / pi * ij[3];
+      const double J2 = -1 / pi * ij[4];
+      const double J3 = -1 / pi * ij[5];
+      if (ramesh) ramesh_tev_lev(rp, lesp_crit, g_tev, m.maxerror, m.maxiter, m.epsilon, g_tev, g_lev);
+      else solve2(1 + I2, 1 + I3, J2, J3, -(I1 + kelvin), lesp_crit - J1, g_tev, g_lev);   // :944-954
+      if (on) Wn[j] = (t1 + g_tev * t2 + g_lev * t3) / m.U;
+      __syncthreads();
+      if (j < ncoef) {
+        double acc = 0.0;
+        const double* cp = m.cproj + (long long)j * npan;
+        for (int q = 0; q < npan; ++q) acc = __builtin_fma(cp[q], Wn[q], acc);
+        // 'Faure' takes A0 from the LESP form (:959); derivatives keep their values in both methods (:963-966)
+        A[j] = (j == 0 && !ramesh) ? J1 + g_tev * J2 + g_lev * J3 : acc;
+      }
+      __syncthreads();
+      bound = ramesh ? ucpi * (A[0] + A[1] / 2) : I1 + g_tev * I2 + g_lev * I3;
+    }
+
+    // bound vorticity per panel (:987-1010)
+    double gamma = 0.0, dgamma = 0.0;
+    if (on) {
+      double ssum = 0.0;
+      for (int q = 1; q < ncoef; ++q) ssum = __builtin_fma(A[q], m.ssin[(long long)(q - 1) * npan + j], ssum);
+      gamma = 2 * m.U * (A[0] * m.opcs[j] + ssum);
+      dgamma = gamma * m.hcsd[j];
+    }
+    const int k = shed ? 2 : 1;
+    // loads (:1035-1090; tangential velocity on the chord from the whole wake by linearity) and, on a step that sheds no
+    // LEV, what the bound vortices induce at the origin (the reference's zero-strength LEV slot, :1112-1118)
+    double r4[4] = {0, 0, 0, 0};     // fn, m, fuo, fwo
+    if (on) {
+      const double uc1 = u1 + g_tev * ut1 + (shed ? g_lev * ul1 : 0.0);
+      const double wc1 = w1 + g_tev * wt1 + (shed ? g_lev * wl1 : 0.0);
+      const double u = uc1 * ca - wc1 * sa;
+      r4[0] = u * gamma * m.wx[j];
+      r4[1] = u * gamma * m.xpan[j] * m.wx[j];
+      if (!shed) {
+        double uu, ww;
+        unit_pair_f64(0.0, 0.0, xg[j], zg[j], m.vc4, uu, ww);
+        r4[2] = dgamma * uu; r4[3] = dgamma * ww;
+      }
+    }
+    block_sum_n<4>(r4, scratch);
+    const double fn_sum = r4[0], m_sum = r4[1], suo = r4[2], swo = r4[3];
+
+    const long long n0 = n;
+    double* row = E.rows + (size_t)(step - 1) * row_doubles;
+    if (j == 0) {
+      const double c = m.chord, U = m.U, rho = m.rho;
+      const double A0 = A[0], A1 = A[1], A2 = A[2];
+      const double A0d = Ad[0], A1d = Ad[1], A2d = Ad[2], A3d = Ad[3];
+      const double Ueff = U * ca + hd * sa;
+      const double Fn = rho * pi * c * U * (Ueff * (A0 + 0.5 * A1) + c * (3.0 / 4 * A0d + 1.0 / 4 * A1d + 1.0 / 8 * A2d))
+          + rho * fn_sum;
+      const double Fs = rho * pi * c * U * U * A0 * A0;
+      const double M = m.piv * Fn - rho * pi * c * c * U * (Ueff * (1.0 / 4 * A0 + 1.0 / 4 * A1 - 1.0 / 8 * A2)
+          + c * (7.0 / 16 * A0d + 3.0 / 16 * A1d + 1.0 / 16 * A2d - 1.0 / 64 * A3d)) - rho * m_sum;
+      row[0] = g_tev; row[1] = g_lev; row[2] = shed ? 1.0 : 0.0; row[3] = bound; row[4] = lesp_prev; row[5] = A0;
+      row[6] = Fn; row[7] = Fs; row[8] = M; row[9] = (double)n0;
+      row[10] = 0.0; row[11] = 0.0;
+      if (!shed) {
+        double uu, ww;
+        unit_pair_f64(0.0, 0.0, tev_x, tev_z, m.vc4, uu, ww);
+        row[10] = puo + suo + g_tev * uu;
+        row[11] = pwo + swo + g_tev * ww;
+      }
+      // the shed vortices join the wake (:1095-1098)
+      xc[n0] = tev_x; zc[n0] = tev_z; g[n0] = g_tev;
+      if (shed) { xc[n0 + 1] = lev_x; zc[n0 + 1] = lev_z; g[n0 + 1] = g_lev; }
+    }
+    if (j < ncoef) {
+      prevA[j] = A[j];
+      row[kMarchRowHead + j] = A[j];
+      row[kMarchRowHead + ncoef + j] = Ad[j];
+    }
+    if (on) {
+      row[kMarchRowHead + 2 * ncoef + j] = gamma;
+      row[kMarchRowHead + 2 * ncoef + npan + j] = dgamma;
+      // bound vortices ride behind the wake as sources of the roll-up (:1106, :1115, :1124)
+      const long long i = n0 + k + j;
+      xc[i] = xg[j]; zc[i] = zg[j]; g[i] = dgamma;
+    }
+    n = n0 + k;
+    sum_tev += g_tev;
+    sum_lev += g_lev;
+    __syncthreads();
+
+    // ---- 3. roll-up (:1095-1127) and 4. placement of the coming step (:672-681, :788-800) -------------------------------
+    const double* kin_next = step + 1 < nt ? kin + krow : nullptr;
+    for (long long t0 = 0; t0 < n; t0 += kBlock) {
+      const long long i = t0 + j;
+      const bool mine = i < n;
+      const double xp = mine ? xc[i] : 0.0, zp = mine ? zc[i] : 0.0;
+      double au, aw;
+      ens_pair_sums<false>(xc, zc, g, n + npan, xp, zp, m.vc4, mine, 0, 1, lx, lz, lg, au, aw);
+      if (mine) {
+        const double xn = xp + m.dt * (au * kInv2PiD);
+        const double zn = zp + m.dt * (-aw * kInv2PiD);
+        xn_[i] = xn; zn_[i] = zn;
+        if (kin_next) {
+          if (i == n - k) {
+            const double tex = kin_next[3], tez = kin_next[4];
+            place[0] = tex + (xn - tex) / 3; place[2] = tez + (zn - tez) / 3;
+          }
+          if (i == n - 1) {
+            const double lex = kin_next[5], lez = kin_next[6];
+            double px = lex, pz = lez;
+            if (shed) { px = lex + (xn - lex) / 3; pz = lez + (zn - lez) / 3; }
+            place[1] = px; place[3] = pz;
+          }
+        }
+      }
+    }
+    { double* t = xc; xc = xn_; xn_ = t; t = zc; zc = zn_; zn_ = t; }
+    __syncthreads();
+
+    // wake records: the listed steps, and the last one
+    while (snap_i < nsnap && snap_steps[snap_i] < step) ++snap_i;
+    int rec = -1;
+    if (snap_i < nsnap && snap_steps[snap_i] == step) rec = snap_i;
+    for (int pass = 0; pass < 2; ++pass) {
+      const int r = pass == 0 ? rec : (step == nt - 1 ? nsnap : -1);
+      if (r < 0) continue;
+      double* o = E.rec + (size_t)r * 3 * (size_t)cap;
+      for (long long i = j; i < n; i += kBlock) { o[i] = xc[i]; o[cap + i] = zc[i]; o[2 * cap + i] = g[i]; }
+      if (j == 0) E.rec_n[r] = n;
+    }
+  }
+}
+
+}  // namespace ludvm

@@ -1,9 +1,11 @@
 // libludvm_hip.so -- C-ABI implementation (see include/ludvm_hip.h for the contract and the reference file:line each entry point
 // replaces; ctx.hpp for how the library is divided into translation units).  gfx950 only; no CPU path: every entry point either
 // runs the HIP kernels or returns an error code.
-// This unit: the device-resident time march (LUDVM.time_loop, LUDVM.py:597-1171, with the solve on the device).
+// This unit: the device-resident time march (LUDVM.time_loop, LUDVM.py:597-1171, with the solve on the device), and the
+// ensemble of small simulations (many such time loops in one launch).
 #include "ctx.hpp"
 #include "march_kernels.hpp"
+#include "ensemble_kernels.hpp"
 
 extern "C" {
 
@@ -347,6 +349,131 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   for (int k = 0; k < 4; ++k) state[12 + k] = tailbuf[k];
   for (int k = 0; k < m.ncoef; ++k) state[16 + k] = hs.prevA[k];
   if (c->timing) CHK(drain_timing(c));
+  return LUDVM_OK;
+}
+
+}  // extern "C"
+
+/* ---- ensemble of small simulations ------------------------------------------------------------ */
+
+extern "C" {
+
+int ludvm_ensemble_limits(ludvm_ctx* c, long long* limits3) {
+  if (!c) return LUDVM_E_ARG;
+  if (!limits3) return fail(c, LUDVM_E_ARG, "null array");
+  limits3[0] = LUDVM_ENSEMBLE_MAX_STEPS; limits3[1] = LUDVM_ENSEMBLE_MAX_WAKE; limits3[2] = LUDVM_ENSEMBLE_MAX_SNAPSHOTS;
+  return LUDVM_OK;
+}
+
+int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n) {
+  if (!c) return LUDVM_E_ARG;
+  if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
+    return fail(c, LUDVM_E_STATE, "ensemble: the context is sharded; members are independent -- split the list per device");
+  if (members == 0) return LUDVM_OK;
+  if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
+    return fail(c, LUDVM_E_ARG, "null array");
+  if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
+    return fail(c, LUDVM_E_ARG, "ensemble: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
+  if (members > ((size_t)1 << 24)) return fail(c, LUDVM_E_ARG, "ensemble: too many members");
+  if (scalar_count != 12 * members) return fail(c, LUDVM_E_ARG, "ensemble: scalars must hold 12 values per member");
+  if (nsnap > LUDVM_ENSEMBLE_MAX_SNAPSHOTS) return fail(c, LUDVM_E_ARG, "ensemble: too many snapshot steps");
+  for (size_t k = 0; k < nsnap; ++k)
+    if (snap_steps[k] < 1 || (k && snap_steps[k] <= snap_steps[k - 1]))
+      return fail(c, LUDVM_E_ARG, "ensemble: snapshot steps must be >= 1 and strictly increasing");
+  const size_t P = (size_t)npan, NC = (size_t)ncoef;
+  const size_t tab_doubles = 8 * P + NC * P + (NC - 1) * P;
+  const size_t krow = 7 + 2 * P;
+  const size_t row_doubles = kMarchRowHead + 2 * NC + 2 * P;
+  const size_t init_doubles = kEnsInitHead + NC;
+  const size_t nrec = nsnap + 1;
+
+  // every member inside the limits and inside the arrays given, before anything touches the device
+  size_t work_doubles = 0;
+  for (size_t mi = 0; mi < members; ++mi) {
+    const long long* d = desc + mi * LUDVM_ENSEMBLE_DESC;
+    const long long nt = d[0], kin_off = d[1], nfree = d[2], free_off = d[3], row_off = d[4], wake_off = d[5];
+    const std::string who = "ensemble: member " + std::to_string(mi) + ": ";
+    if (nt < 2 || nt - 1 > LUDVM_ENSEMBLE_MAX_STEPS)
+      return fail(c, LUDVM_E_ARG, who + "1 <= steps <= " + std::to_string(LUDVM_ENSEMBLE_MAX_STEPS) + " (it can be run on its own)");
+    if (nfree < 0 || nfree + 2 * (nt - 1) > LUDVM_ENSEMBLE_MAX_WAKE)
+      return fail(c, LUDVM_E_ARG, who + "free vortices + 2 steps <= " + std::to_string(LUDVM_ENSEMBLE_MAX_WAKE) + " (it can be run on its own)");
+    const size_t cap = (size_t)(nfree + 2 * (nt - 1));
+    if (kin_off < 0 || (size_t)kin_off + (size_t)nt > kin_rows) return fail(c, LUDVM_E_ARG, who + "kinematics rows outside the table");
+    if (free_off < 0 || (size_t)free_off + (size_t)nfree > free_count) return fail(c, LUDVM_E_ARG, who + "free vortices outside the array");
+    if (row_off < 0 || (size_t)row_off + (size_t)(nt - 1) > rows_count) return fail(c, LUDVM_E_ARG, who + "output rows outside the array");
+    if (wake_off < 0 || (size_t)wake_off + nrec * 3 * cap > wake_doubles) return fail(c, LUDVM_E_ARG, who + "wake records outside the array");
+    const double* sc = scalars + 12 * mi;
+    if (sc[8] != 0.0 && !(sc[9] > 0.0 && sc[10] >= 1.0 && sc[11] > 0.0))
+      return fail(c, LUDVM_E_ARG, who + "'Ramesh' needs maxerror > 0, maxiter >= 1, epsilon > 0");
+    work_doubles += 5 * (cap + P);
+  }
+
+  HIPCHK(c, hipSetDevice(c->device));
+  // inputs: tables | kin | init | free | snapshot steps | member records
+  const size_t in_tab = Arena::need(members * tab_doubles, 8), in_kin = Arena::need(kin_rows * krow, 8);
+  const size_t in_init = Arena::need(members * init_doubles, 8), in_free = Arena::need(3 * free_count + 1, 8);
+  const size_t in_snap = Arena::need(nsnap + 1, 8), in_mem = Arena::need(members, sizeof(EnsembleMember));
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem));
+  CHK(ensure(c, c->ens_work, work_doubles * 8));
+  const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
+  const size_t out_n = Arena::need(members * nrec, 8);
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n));
+  Arena in(c->ens_in.p), out(c->ens_out.p);
+  double* d_tab = in.take<double>(members * tab_doubles);
+  double* d_kin = in.take<double>(kin_rows * krow);
+  double* d_init = in.take<double>(members * init_doubles);
+  double* d_free = in.take<double>(3 * free_count + 1);
+  long long* d_snap = in.take<long long>(nsnap + 1);
+  EnsembleMember* d_mem = in.take<EnsembleMember>(members);
+  double* d_rows = out.take<double>(rows_count * row_doubles);
+  double* d_wakes = out.take<double>(wake_doubles);
+  long long* d_n = out.take<long long>(members * nrec);
+
+  std::vector<EnsembleMember> hm(members);
+  double* work = static_cast<double*>(c->ens_work.p);
+  for (size_t mi = 0; mi < members; ++mi) {
+    const long long* d = desc + mi * LUDVM_ENSEMBLE_DESC;
+    const double* sc = scalars + 12 * mi;
+    EnsembleMember& e = hm[mi];
+    MarchSetup& m = e.m;
+    m.npan = npan; m.ncoef = ncoef;
+    m.U = sc[0]; m.chord = sc[1]; m.rho = sc[2]; m.dt = sc[3]; m.piv = sc[4];
+    m.kelvin0 = sc[7] - sc[6];          // sum(Gamma_free) - IC
+    m.vc4 = (sc[5] * sc[5]) * (sc[5] * sc[5]);
+    m.method = sc[8] != 0.0 ? 1 : 0;
+    m.maxerror = sc[9]; m.maxiter = (int)sc[10]; m.epsilon = sc[11];
+    const double* t = d_tab + mi * tab_doubles;
+    m.detadx = t; m.eta = t + P; m.xpan = t + 2 * P; m.cm1 = t + 3 * P; m.wq = t + 4 * P; m.opcs = t + 5 * P;
+    m.hcsd = t + 6 * P; m.wx = t + 7 * P; m.cproj = t + 8 * P; m.ssin = t + 8 * P + NC * P;
+    e.nt = d[0]; e.nfree = d[2];
+    e.cap = d[2] + 2 * (d[0] - 1);
+    const size_t cap = (size_t)e.cap, slab = cap + P;
+    e.kin = d_kin + (size_t)d[1] * krow;
+    e.init = d_init + mi * init_doubles;
+    e.free_x = d_free + 3 * (size_t)d[3]; e.free_z = e.free_x + d[2]; e.free_g = e.free_z + d[2];
+    e.xa = work; e.za = work + slab; e.xb = work + 2 * slab; e.zb = work + 3 * slab; e.g = work + 4 * slab;
+    work += 5 * slab;
+    e.rows = d_rows + (size_t)d[4] * row_doubles;
+    e.rec = d_wakes + (size_t)d[5];
+    e.rec_n = d_n + mi * nrec;
+  }
+  HIPCHK(c, hipMemcpyAsync(d_tab, tables, members * tab_doubles * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_kin, kin, kin_rows * krow * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_init, init, members * init_doubles * 8, hipMemcpyHostToDevice, c->stream));
+  if (free_count) HIPCHK(c, hipMemcpyAsync(d_free, free_xzg, 3 * free_count * 8, hipMemcpyHostToDevice, c->stream));
+  if (nsnap) HIPCHK(c, hipMemcpyAsync(d_snap, snap_steps, nsnap * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_mem, hm.data(), members * sizeof(EnsembleMember), hipMemcpyHostToDevice, c->stream));
+  // ONE launch: a workgroup per member, all of its time steps inside
+  hipLaunchKernelGGL(ensemble_march, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
+                     (const long long*)d_snap, (int)nsnap);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(rows, d_rows, rows_count * row_doubles * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(wakes, d_wakes, wake_doubles * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(wake_n, d_n, members * nrec * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm lives on this frame)
   return LUDVM_OK;
 }
 

@@ -395,6 +395,42 @@ class Engine:
         """The four steps whose wake sizes ludvm_march_run wants in `anchors` for a call that begins at first_step."""
         return [max(64 * (int(first_step) // 64 - 3 + q) - 1, 0) for q in range(4)]
 
+    # -- ensemble of small simulations ---------------------------------------------------------------
+    def ensemble_limits(self):
+        """(max steps, max wake capacity, max snapshot steps) of a member of `ensemble_run`."""
+        lim = (c_longlong * 3)()
+        self._check(self._lib.ludvm_ensemble_limits(self._ctx, lim))
+        return int(lim[0]), int(lim[1]), int(lim[2])
+
+    def ensemble_run(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=()):
+        """Many whole time loops in ONE device launch, a workgroup per member (ludvm_ensemble_run; the packed layouts are
+        documented in include/ludvm_hip.h).  scalars [members, 12]; tables [members, T]; kin [rows, 7 + 2 npan]; init
+        [members, 8 + ncoef]; free_xzg: 3 * (free vortices of all members) doubles; desc [members, 6] int64 = nt, kin_off,
+        nfree, free_off, row_off, wake_off; snap_steps: increasing steps >= 1.
+        -> (rows [sum(nt - 1), 12 + 2 ncoef + 2 npan], wakes (float64, flat), wake_n [members, len(snap_steps) + 1])."""
+        npan, ncoef = int(npan), int(ncoef)
+        desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
+        members = desc.shape[0]
+        sc, tb, ini, fr = _f64(scalars), _f64(tables), _f64(init), _f64(free_xzg)
+        kin = np.ascontiguousarray(kin, dtype=np.float64).reshape(-1, 7 + 2 * npan)
+        snaps = np.ascontiguousarray(list(snap_steps), dtype=np.int64).reshape(-1)
+        if members and (len(tb) != members * (8 * npan + ncoef * npan + (ncoef - 1) * npan)
+                        or len(ini) != members * (_ffi.ENSEMBLE_INIT_HEAD + ncoef) or len(fr) % 3):
+            raise ValueError("ensemble_run: wrong table / init / free-vortex array length")
+        nrec = len(snaps) + 1
+        rows_count = int(max((desc[:, 4] + desc[:, 0] - 1).max(), 0)) if members else 0
+        cap = desc[:, 2] + 2 * (desc[:, 0] - 1)
+        wake_doubles = int(max((desc[:, 5] + nrec * 3 * cap).max(), 0)) if members else 0
+        rows = np.empty([rows_count, self.MARCH_ROW_HEAD + 2 * ncoef + 2 * npan])
+        wakes = np.empty(wake_doubles)
+        wake_n = np.empty([members, nrec], dtype=np.int64)
+        pll = POINTER(c_longlong)
+        self._check(self._lib.ludvm_ensemble_run(
+            self._ctx, members, npan, ncoef, _pd(sc), len(sc), _pd(tb), _pd(kin), kin.shape[0], _pd(ini), _pd(fr), len(fr) // 3,
+            desc.ctypes.data_as(pll), snaps.ctypes.data_as(pll), len(snaps), _pd(rows), rows_count, _pd(wakes), wake_doubles,
+            wake_n.ctypes.data_as(pll)))
+        return rows, wakes, wake_n
+
     # -- flow field ------------------------------------------------------------------------------
     def flowfield(self, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core):
         """(u, w) float32 [nx, nz] on the grid (xmin + i*dr, zmin + j*dr) (LUDVM.py:1193-1195)."""

@@ -1,0 +1,177 @@
+"""`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run).
+
+A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
+'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
+a sweep are independent, so the engine gives each a workgroup of its own and runs its whole time loop inside one kernel
+(ludvm_amd/csrc/ensemble_kernels.hpp).
+
+    from ludvm_amd import sweep
+    sims = sweep([dict(LESPcrit=l, alpha_max=a) for l in (0.1, 0.2, 0.3) for a in (10, 20)], tf=6, verbose=False)
+    print([s.Cl.mean() for s in sims])
+
+Geometry and kinematics of every member come from the ordinary constructor (run=False); the tables a member hands the device
+are the ones a solo march uploads (LUDVM._march_inputs) and its results are stored by the routine that stores a solo march's
+(LUDVM._store_march_results).
+"""
+import numpy as np
+
+from . import _ffi
+from .ludvm import LUDVM
+
+__all__ = ["sweep"]
+
+_REFUSED = {
+    # keyword -> (value that is fine, why not otherwise)
+    "checkpoint_every": (0, "a sweep has no checkpoint / resume"),
+    "checkpoint_path": (None, "a sweep has no checkpoint / resume"),
+    "distributed": (None, "a sweep runs on one GPU (members are independent: split the list per device)"),
+    "devices": (None, "a sweep runs on one GPU (members are independent: split the list per device)"),
+    "march": (True, "the members of a sweep are marched on the device"),
+    "run": (True, "the members of a sweep are run"),
+}
+
+
+class _RecordedWakes:
+    """hist[r, 0 | 1] of LUDVM._store_march_results for a member: the wake's x / z after the steps the device recorded."""
+
+    def __init__(self):
+        self.rows = {}
+
+    def __getitem__(self, key):
+        r, k = key
+        rec = self.rows.get(int(r))
+        return None if rec is None else rec[k]
+
+
+def _check_case(idx, kw, first):
+    """Everything that can be refused from the keywords alone (no device, no engine call)."""
+    who = f"sweep: member {idx}: "
+    for key in ("engine", "device", "snapshot_steps", "verbose"):
+        if key in kw:
+            raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
+    for key, (fine, why) in _REFUSED.items():
+        if key in kw and not (kw[key] is fine or kw[key] == fine):
+            raise ValueError(who + f"{key}={kw[key]!r}: {why}")
+    if kw.get("precision", "auto") not in ("auto", "f64"):
+        raise ValueError(who + f"precision={kw['precision']!r}: the members of a sweep run in float64 ('auto' or 'f64')")
+    if kw.get("history", "auto") == "full":
+        raise ValueError(who + "history='full': a sweep keeps rows at snapshot_steps and the last step only")
+    if kw.get("method", "Faure") not in ("Faure", "Ramesh"):
+        raise ValueError(who + "method must be 'Faure' or 'Ramesh'")
+    npoints, ncoef = int(kw.get("Npoints", 80)), int(kw.get("Ncoeffs", 30))
+    if not (1 <= npoints - 1 <= 256 and 4 <= ncoef <= 64):
+        raise ValueError(who + "1 <= Npoints - 1 <= 256 and 4 <= Ncoeffs <= 64")
+    if first is not None and (npoints, ncoef) != first:
+        raise ValueError(who + f"Npoints / Ncoeffs = {npoints} / {ncoef} differ from member 0's {first[0]} / {first[1]}: "
+                         "they are common to a sweep")
+    t0, tf, dt = kw.get("t0", 0), kw.get("tf", 12), kw.get("dt", 1.5e-2)
+    nt = len(np.arange(t0, tf + dt, dt))
+    g = kw.get("circulation_freevort")
+    nf = len(g) if (g is not None and kw.get("xy_freevort") is not None) else 1
+    if nt < 2:
+        raise ValueError(who + "no time step to run")
+    if nt - 1 > _ffi.ENSEMBLE_MAX_STEPS or nf + 2 * (nt - 1) > _ffi.ENSEMBLE_MAX_WAKE:
+        raise ValueError(who + f"{nt - 1} steps / a wake of up to {nf + 2 * (nt - 1)} vortices is over the limits of a sweep member "
+                         f"({_ffi.ENSEMBLE_MAX_STEPS} steps, {_ffi.ENSEMBLE_MAX_WAKE} vortices); it can be run on its own: LUDVM(...)")
+    return npoints, ncoef
+
+
+def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls=LUDVM, **common):
+    """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
+    return the list of LUDVM objects, in order.  Each carries what a solo
+    `LUDVM(**kw, precision='f64', history='sparse', snapshot_steps=snapshot_steps)` run carries: Cl, Cd, Cm, Cn, Cs, Ct, Fn, Fs, L,
+    D, T, M, LESP, LESP_prev, LEV_shed, itev, ilev, fourier, every circulation[...] entry, and path['TEV' | 'LEV' | 'FREE'] as
+    SparseHistory with rows at snapshot_steps and the last step -- `flowfield` works on a member for any stored step.  A member
+    differs from its solo run by summation order only; its bits do not depend on the other members or on its place in the list.
+
+    Npoints and Ncoeffs are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
+    kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs,
+    a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
+    history='full', checkpoint_*, distributed, devices, march=False, run=False, an engine without ensemble_run.
+
+    Out of scope: fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    split the list per device), members above the limits; a solo run executes exactly as before."""
+    cases = list(cases)
+    if not cases:
+        return []
+    merged, first = [], None
+    for idx, case in enumerate(cases):
+        kw = dict(common)
+        kw.update(case)
+        dims = _check_case(idx, kw, first)
+        first = first or dims
+        merged.append(kw)
+    if engine is None:
+        from .engine import Engine
+        engine = Engine(device)
+    if not hasattr(engine, "ensemble_run"):
+        raise ValueError("sweep: this engine has no ensemble_run")
+    snaps = sorted({int(s) for s in snapshot_steps})
+    dev_snaps = [s for s in snaps if s >= 1]
+    if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
+        raise ValueError(f"sweep: at most {_ffi.ENSEMBLE_MAX_SNAPSHOTS} snapshot steps")
+
+    # host: geometry, kinematics and tables of every member, packed
+    sims, loops = [], []
+    sc, tb, kn, ini, fr = [], [], [], [], []
+    desc = np.zeros([len(merged), _ffi.ENSEMBLE_DESC], dtype=np.int64)
+    kin_off = free_off = row_off = wake_off = 0
+    nrec = len(dev_snaps) + 1
+    for idx, kw in enumerate(merged):
+        kw = dict(kw, precision="f64", history="sparse")
+        sim = cls(**kw, engine=engine, snapshot_steps=snaps, verbose=False, run=False)
+        if sims and (sim.Npoints, sim.Ncoeffs) != (sims[0].Npoints, sims[0].Ncoeffs):       # (a .dat section sets its own)
+            raise ValueError(f"sweep: member {idx}: Npoints / Ncoeffs differ from member 0's: they are common to a sweep")
+        S = sim._loop_begin(resident=False)
+        sim._free_slot = None
+        S.fsl = slice(0, S.nf)
+        S.sb, S.have_next = None, False
+        scalars, tables, kin = sim._march_inputs(S)
+        tev_xy, lev_xy = sim._next_placement(S, 1)
+        free0 = np.array(sim.xy_freevort, dtype=float).reshape(2, S.nf)
+        sc.append(np.asarray(scalars, dtype=float))
+        tb.append(tables)
+        kn.append(kin)
+        ini.append(np.concatenate([[tev_xy[0], lev_xy[0], tev_xy[1], lev_xy[1], sim.LESPcrit, 0.0, 0.0, 0.0], sim.fourier[0, 0, :]]))
+        fr.append(np.concatenate([free0[0], free0[1], np.asarray(sim.circulation_freevort, dtype=float).reshape(-1)]))
+        nt, nf = sim.nt, S.nf
+        desc[idx] = [nt, kin_off, nf, free_off, row_off, wake_off]
+        kin_off, free_off, row_off = kin_off + nt, free_off + nf, row_off + nt - 1
+        wake_off += nrec * 3 * (nf + 2 * (nt - 1))
+        sims.append(sim)
+        loops.append(S)
+    npan, ncoef = sims[0].Npoints - 1, sims[0].Ncoeffs
+
+    # device: one launch
+    rows, wakes, wake_n = engine.ensemble_run(npan, ncoef, np.stack(sc), np.stack(tb), np.concatenate(kn), np.stack(ini),
+                                              np.concatenate(fr), desc, dev_snaps)
+
+    # host: every member's rows into its result arrays, by the routine that stores a solo march
+    for idx, (sim, S) in enumerate(zip(sims, loops)):
+        nt, _, nf, _, r0, w0 = (int(v) for v in desc[idx])
+        cap = nf + 2 * (nt - 1)
+        R = rows[r0:r0 + nt - 1]
+        hist = _RecordedWakes()
+        for r, step in enumerate(dev_snaps + [nt - 1]):
+            n = int(wake_n[idx, r])
+            if n < 0 or (r < len(dev_snaps) and step > nt - 1):
+                continue
+            rec = wakes[w0 + r * 3 * cap:w0 + (r + 1) * 3 * cap]
+            hist.rows[step - 1] = (rec[:n], rec[cap:cap + n])
+        n_shed = int((R[:, 2] != 0).sum())
+        n_end = int(wake_n[idx, nrec - 1])
+        last = wakes[w0 + (nrec - 1) * 3 * cap:w0 + nrec * 3 * cap]
+        st = np.zeros(16 + ncoef)
+        st[0], st[1], st[2] = n_end, nt - 1, n_shed
+        shed_rows = R[R[:, 2] != 0]
+        st[4] = sim.LESPcrit                      # ... with the sign of A0 at the last shedding (:802-805)
+        if len(shed_rows):
+            st[4] = -abs(sim.LESPcrit) if shed_rows[-1, 4] < 0 else abs(sim.LESPcrit)
+        st[5], st[6] = R[:, 0].sum(), R[:, 1].sum()
+        if n_end >= 2:
+            st[12:16] = [last[n_end - 2], last[n_end - 1], last[cap + n_end - 2], last[cap + n_end - 1]]
+        sim._store_march_results(S, 1, nt, st, R, hist)
+        sim.compute_coefficients()
+        if verbose:
+            print(f"sweep: member {idx}: {nt - 1} steps, {sim.itev + 1} TEV, {S.ilev} LEV, mean Cl {sim.Cl.mean():.6f}")
+    return sims

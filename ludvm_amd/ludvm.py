@@ -425,8 +425,9 @@ class LUDVM:
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
-    def _loop_begin(self):
-        """Result arrays (LUDVM.py:615-641), projection tables, the device wake with the free vortices in it."""
+    def _loop_begin(self, resident=True):
+        """Result arrays (LUDVM.py:615-641), projection tables, the device wake with the free vortices in it
+        (resident=False: the engine's resident wake is left alone -- a member of a sweep lives in a slab of its own)."""
         pi, U, c = np.pi, self.Uinf, self.chord
         eng = self.engine
         nt, nv, nf, npan = self.nt, self.nt - 1, self.n_freevort, self.Npoints - 1
@@ -476,14 +477,15 @@ class LUDVM:
         C['IC'] = S.sum_free + U * c * pi * (A0 + A1 / 2)
 
         # device wake, in shedding order: FREE first, then each step's TEV (and LEV when shed)
-        eng.wake_clear()
-        eng.wake_reserve(nf + 2 * nv + npan + 2)
+        if resident:
+            eng.wake_clear()
+            eng.wake_reserve(nf + 2 * nv + npan + 2)
         # A cloud of free vortices (generate_flowfield_turbulence, LUDVM.py:98-130) arrives in no spatial order; the fp32
         # roll-up keeps its accuracy tier on compact 256-vortex blocks (a shed wake's stored order).  The engine names the
         # order it wants (Morton; the identity for a compact or small set): the cloud is STORED in it, `fslot[j]` is the
         # wake slot of the caller's free vortex j, and every path['FREE'] row is returned in the caller's order.
         fslot = None
-        if self.precision == 'f32' and nf >= 2048 and hasattr(eng, 'spatial_order'):
+        if resident and self.precision == 'f32' and nf >= 2048 and hasattr(eng, 'spatial_order'):
             order, reordered, extent = eng.spatial_order(free0[0], free0[1], with_extent=True)
             if extent > (150.0 if reordered else 300.0) * self.v_core > 0.0:
                 # too sparse for its core: no order makes 128-vortex classes compact enough for fp32 offsets to resolve
@@ -498,7 +500,7 @@ class LUDVM:
                 fslot = np.empty(nf, dtype=np.int64)
                 fslot[order] = np.arange(nf)
                 eng.wake_append(free0[0][order], free0[1][order], g_free[order])
-        if fslot is None:
+        if fslot is None and resident:
             eng.wake_append(free0[0], free0[1], g_free)
         S.fslot = fslot
         S.tev_slot = np.zeros(nv, dtype=np.int64)
@@ -536,7 +538,7 @@ class LUDVM:
 
     def _loop_prepare_engine(self, S):
         """Host buffers of the per-step path; tables and kinematics of the device-resident march."""
-        eng, C = self.engine, self.circulation
+        eng = self.engine
         npan = self.Npoints - 1
         # preallocated host buffers for the two device calls of a step (engines that offer them)
         S.sb = eng.step_buffers(npan) if hasattr(eng, 'step_buffers') else None
@@ -548,16 +550,23 @@ class LUDVM:
         S.can_march = (self.march and self.method in ('Faure', 'Ramesh') and hasattr(eng, 'march_run') and npan <= 256
                        and 4 <= self.Ncoeffs <= 64)
         if S.can_march:
-            tables = np.concatenate([S.detadx, self.airfoil['eta_panel'], S.x_gamma, self._cm1, self._wq, S.one_plus_cos_over_sin,
-                                     S.half_c_sin_dth, S.wx, self._cproj.ravel(), self._ssin.ravel()])
-            kin = np.concatenate([self.alpha[:, None], self.alpha_dot[:, None], self.h_dot[:, None], S.foil[:, :, -1],
-                                  S.foil[:, :, 0], S.gpts[:, 0, :], S.gpts[:, 1, :]], axis=1)
-            eng.march_setup(npan, self.Ncoeffs, [self.Uinf, self.chord, self.rho, self.dt, self.piv, self.v_core, C['IC'], S.sum_free,
-                                                  float(self.method == 'Ramesh'), self.maxerror, self.maxiter, self.epsilon], tables, kin)
+            eng.march_setup(npan, self.Ncoeffs, *self._march_inputs(S))
         # with the dense history every step's row is recorded: the march then keeps a snapshot of the wake per step on
         # the device (shorter calls, the snapshots are [steps, 2, wake size])
         S.dense_march = S.can_march and self.history == 'full'
         S.march_chunk = int(getattr(self, '_march_chunk', 512 if S.dense_march else 32768))   # steps per ludvm_march_run call
+
+    def _march_inputs(self, S):
+        """-> (scalars[12], tables, kin[nt, 7 + 2 npan]) as ludvm_march_setup takes them (include/ludvm_hip.h); a sweep packs
+        the same three per member (ludvm_amd/ensemble.py)."""
+        C = self.circulation
+        tables = np.concatenate([S.detadx, self.airfoil['eta_panel'], S.x_gamma, self._cm1, self._wq, S.one_plus_cos_over_sin,
+                                 S.half_c_sin_dth, S.wx, self._cproj.ravel(), self._ssin.ravel()])
+        kin = np.concatenate([self.alpha[:, None], self.alpha_dot[:, None], self.h_dot[:, None], S.foil[:, :, -1],
+                              S.foil[:, :, 0], S.gpts[:, 0, :], S.gpts[:, 1, :]], axis=1)
+        scalars = [self.Uinf, self.chord, self.rho, self.dt, self.piv, self.v_core, C['IC'], S.sum_free,
+                   float(self.method == 'Ramesh'), self.maxerror, self.maxiter, self.epsilon]
+        return scalars, tables, kin
 
     def _progress(self, q, print_dt):
         if (q == 1 or q == self.nt - 1 or q / print_dt == int(q / print_dt)) and self.verbose == True:  # noqa: E712
@@ -618,9 +627,8 @@ class LUDVM:
         would have stored for them (LUDVM.py:765-1090): circulations, Fourier rows, LESP, loads, slot maps -- and,
         with `record` (dense history), the path[...] rows of every step (:1108-1127).
         `place` = [tev_x, lev_x, tev_z, lev_z] of step i.  The loop state S and the result arrays are updated in place."""
-        C, nc, npan, cnt = self.circulation, self.Ncoeffs, self.Npoints - 1, j - i
-        nf, itev, ilev, LEV_shed, tev_slot, lev_slot = S.nf, S.itev, S.ilev, S.LEV_shed, S.tev_slot, S.lev_slot
-        H = self.engine.MARCH_ROW_HEAD
+        nc, cnt = self.Ncoeffs, j - i
+        nf, itev, ilev, LEV_shed = S.nf, S.itev, S.ilev, S.LEV_shed
         n_wake = nf + itev + ilev
         st = np.zeros(16 + nc)
         st[:11] = [n_wake, itev, ilev, float(LEV_shed[i - 1] != -1), S.lesp_crit, S.sum_tev, S.sum_lev] + list(place)
@@ -629,10 +637,23 @@ class LUDVM:
         shed_before = np.cumsum(LEV_shed[:i] != -1)            # LEVs shed in steps 0 .. q (step 0 sheds none)
         anchors = [nf + a + int(shed_before[a]) for a in self.engine.march_anchor_steps(i)]      # (all of them < i)
         st[16:] = self.fourier[i - 1, 0, :]
+        hist = None
         if record:
             R, hist = self.engine.march_run(i, cnt, S.prec_code, st, hist_nmax=n_wake + 2 * cnt, anchors=anchors)
         else:
             R = self.engine.march_run(i, cnt, S.prec_code, st, anchors=anchors)
+        self._store_march_results(S, i, j, st, R, hist)
+
+    def _store_march_results(self, S, i, j, st, R, hist=None):
+        """What time steps [i, j) leave in the result arrays and in the loop state S, from their device rows R
+        (ludvm_march_run's layout; ludvm_ensemble_run returns the same), the state `st` after them (st[0] wake size, st[1]
+        TEVs shed, st[4..6] LESPcrit and the Kelvin sums, st[12..15] the two newest vortices) and -- hist given -- the wake's
+        positions after each recorded step, hist[r, 0 | 1] in wake order."""
+        C, nc, npan, cnt = self.circulation, self.Ncoeffs, self.Npoints - 1, j - i
+        nf, itev, ilev, LEV_shed, tev_slot, lev_slot = S.nf, S.itev, S.ilev, S.LEV_shed, S.tev_slot, S.lev_slot
+        H = self.engine.MARCH_ROW_HEAD
+        n_wake = nf + itev + ilev
+        record = hist is not None
         steps = np.arange(i, j)
         tix = itev + np.arange(cnt)
         shed_v = R[:, 2] != 0
@@ -967,6 +988,13 @@ class LUDVM:
         sim.time_loop(_resume=R)
         sim.compute_coefficients()
         return sim
+
+    @classmethod
+    def sweep(cls, cases, **kwargs):
+        """Many small simulations in one device launch: `ludvm_amd.sweep(cases, **kwargs)` (ludvm_amd/ensemble.py) building
+        members of this class."""
+        from .ensemble import sweep
+        return sweep(cases, cls=cls, **kwargs)
 
     # Newton variants of the reference's 'Ramesh' method.  The downwash is linear in the circulations
     # of the vortices being shed, W = T1 + G_tev T2 + G_lev T3, so the reference's repeated

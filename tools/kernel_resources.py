@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Register / LDS / occupancy table of the pair kernels as hipcc compiles them for gfx950 (no GPU needed)."""
+"""Register / LDS / occupancy table of the pair kernels as hipcc compiles them for gfx950 (no GPU needed).
+    python tools/kernel_resources.py [name pattern] [unit]
+e.g. `python tools/kernel_resources.py march march.hip` for the march's kernels and the ensemble kernel."""
 import os
 import re
 import subprocess
@@ -32,7 +34,8 @@ def resources(extra=(), unit="launch.hip"):
 
 if __name__ == "__main__":
     pat = sys.argv[1] if len(sys.argv) > 1 else "pair_"
-    for k, v in resources().items():
+    unit = sys.argv[2] if len(sys.argv) > 2 else "launch.hip"
+    for k, v in resources(unit=unit).items():
         if pat in k:
             name = re.sub(r"^_ZN5ludvm", "", k)
             print(name[:60].ljust(60), "VGPR", v.get("VGPRs"), "spill", v.get("VGPRs Spill"), "scratch",
