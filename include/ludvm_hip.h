@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define LUDVM_ABI_VERSION 6
+#define LUDVM_ABI_VERSION 7
 
 enum {
   LUDVM_OK = 0,
@@ -362,6 +362,35 @@ int ludvm_march_setup(ludvm_ctx* ctx, int npan, int ncoef, const double* scalars
                       size_t kin_rows);
 int ludvm_march_run(ludvm_ctx* ctx, long long first_step, long long count, int precision, double* state, double* rows,
                     double* hist, size_t hist_nmax, const long long* anchors);
+
+/* ---- velocity probes: time series at fixed points, evaluated in the march (ABI 7) ----------------
+ *
+ * For time step i >= 1 and probe point p, (u, w)_i(p) is the field that convects the wake in step i, evaluated at p:
+ * LUDVM.py:1095-1106 with xp, zp = p,
+ *   induced_velocity(circulation_wake, xw, zw, p) + induced_velocity(circulation_foil, xa, za, p)
+ * -- the sources are the wake BEFORE the Euler update of step i, including the vortices shed in step i at their placement,
+ * and the bound vortices of step i at airfoil_gamma_points[i]; Vatistas core v_core (a probe that coincides with a vortex
+ * gets 0 from it); no freestream term.  (The reference obtains such a signal by calling induced_velocity on the stored
+ * history of every step, which a run too long for the dense history does not have.)  The sums are float64 whatever the
+ * roll-up's precision, each formed in a fixed order that depends on the probe count and on the step's anchor-derived bound
+ * of the wake size only: a run repeats bit for bit, however it is cut into calls.
+ *
+ * ludvm_march_set_probes: valid after ludvm_march_setup (LUDVM_E_STATE otherwise); count <= LUDVM_MARCH_MAX_PROBES points
+ *   (x[k], z[k]); count = 0 removes the probes.  shift_x: NULL, or one x offset per kinematics row (shift_rows must equal
+ *   ludvm_march_setup's kin_rows): in step i probe k sits at (x[k] + shift_x[i], z[k]) -- a frame that translates with the
+ *   pivot.  Everything is validated (finite values included) before anything is changed: a call refused with LUDVM_E_ARG
+ *   leaves the probes that were set -- and the rows of the last run -- as they were.  A call that passes validation and
+ *   then fails in the runtime (LUDVM_E_HIP, LUDVM_E_NOMEM: the buffers are replaced) leaves the context WITHOUT probes.
+ *   ludvm_march_setup forgets any probes.
+ * ludvm_march_read_probes: copies the rows of the LAST ludvm_march_run call as u[rows][count], w[rows][count]; `rows` must
+ *   equal that call's `count` (LUDVM_E_ARG otherwise); LUDVM_E_STATE when no probes are set, or when no ludvm_march_run call
+ *   has succeeded since they were set.
+ * Guarantee: with probes set, `rows`, `state`, `hist` and the resident wake of ludvm_march_run are bit-identical to a call
+ *   without them (the probe kernels read the wake and write only buffers of their own). */
+#define LUDVM_MARCH_MAX_PROBES 4096
+int ludvm_march_set_probes(ludvm_ctx* ctx, const double* x, const double* z, size_t count, const double* shift_x,
+                           size_t shift_rows);
+int ludvm_march_read_probes(ludvm_ctx* ctx, double* u, double* w, size_t rows);
 
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *

@@ -19,7 +19,7 @@ OK, E_ARG, E_HIP, E_NOMEM, E_NODEVICE, E_STATE, E_COMM = range(7)
 PREC_F32, PREC_F32X2, PREC_F64 = 0, 1, 2
 SYM_TILE = 512
 SYM_OWNER_ALIGN = 4      # tiles: an owner's block of the tile ring is a whole number of these quads (include/ludvm_hip.h)
-ABI_VERSION = 6
+ABI_VERSION = 7
 COMM_ID_BYTES = 128
 # limits of ludvm_ensemble_run (include/ludvm_hip.h, LUDVM_ENSEMBLE_*)
 ENSEMBLE_MAX_STEPS = 2048
@@ -27,6 +27,7 @@ ENSEMBLE_MAX_WAKE = 8192
 ENSEMBLE_MAX_SNAPSHOTS = 1024
 ENSEMBLE_INIT_HEAD = 8
 ENSEMBLE_DESC = 6
+MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
 SYM_SCALE_BYTES = 32
 
 _pd, _pf = POINTER(c_double), POINTER(c_float)
@@ -81,6 +82,8 @@ SIGNATURES = {
                         c_int, c_size_t, _pd, _pd, c_size_t, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd],
     "ludvm_march_setup": [c_void_p, c_int, c_int, _pd, _pd, _pd, c_size_t],
     "ludvm_march_run": [c_void_p, c_longlong, c_longlong, c_int, _pd, _pd, _pd, c_size_t, POINTER(c_longlong)],
+    "ludvm_march_set_probes": [c_void_p, _pd, _pd, c_size_t, _pd, c_size_t],
+    "ludvm_march_read_probes": [c_void_p, _pd, _pd, c_size_t],
     "ludvm_ensemble_limits": [c_void_p, POINTER(c_longlong)],
     "ludvm_ensemble_run": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
                            POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,

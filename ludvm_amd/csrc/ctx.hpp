@@ -107,6 +107,12 @@ struct ludvm_ctx {
   hipEvent_t march_ev[2] = {nullptr, nullptr};
   hipStream_t stream_b = nullptr;              // the solve chain beside the roll-up (overlapped march steps)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // velocity probes of the march (ludvm_march_set_probes): positions x[P] | z[P], the per-step x offsets, the partial slabs
+  // of one step (a buffer of their own: the probe kernels never touch `part`), the rows of the last ludvm_march_run call
+  Buf probe_xz, probe_shift, probe_part, probe_out;
+  size_t probe_count = 0;                      // P (0: no probes)
+  size_t probe_rows = 0;                       // steps of the last ludvm_march_run call that left rows (0: none to read)
+  bool probe_shifted = false;
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

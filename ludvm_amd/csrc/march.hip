@@ -15,6 +15,8 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
                       size_t kin_rows) {
   if (!c) return LUDVM_E_ARG;
   c->march_ready = false;
+  c->probe_count = 0;       // a new run: its probes are set after this call (ludvm_march_set_probes)
+  c->probe_rows = 0;
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -106,14 +108,103 @@ void march_workspace(const ludvm_ctx* c, long long n_ub, int precision, size_t n
   part_bytes = std::max(part_bytes, (size_t)q.nsplit * 2 * (size_t)q.nt_pad * 8);
 }
 
+// Launch rule of the probe kernels.  P probes in tiles of 64 (one wavefront each); the sources -- at most ns_ub = n_ub + nfoil,
+// n_ub the step's anchor-derived bound of the wake size after its solve -- in `nsplit` splits of `chunk` sources, a multiple
+// of the 256-source LDS tile, chosen so that tiles x splits comes to about 1024 wavefronts (one per SIMD of the device).  A
+// function of P and n_ub alone: the summation order of a step does not depend on where the calls of a run begin.
+struct ProbePlan { long long ptiles, p_pad, chunk; int nsplit; };
+constexpr long long kProbeWaves = 1024;
+ProbePlan probe_plan(size_t count, long long ns_ub) {
+  ProbePlan p;
+  p.ptiles = ((long long)count + kProbeLanes - 1) / kProbeLanes;
+  p.p_pad = p.ptiles * kProbeLanes;
+  const long long want = std::max<long long>(1, kProbeWaves / p.ptiles);
+  ns_ub = std::max<long long>(ns_ub, 1);
+  p.chunk = std::max<long long>(kProbeTile, ((ns_ub + want - 1) / want + kProbeTile - 1) / kProbeTile * kProbeTile);
+  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
+  return p;
+}
+// the slab of any step: nsplit <= max(1, 1024 / ptiles) whatever the wake size
+size_t probe_slab_bytes(size_t count) {
+  const ProbePlan p = probe_plan(count, 1);
+  return (size_t)std::max<long long>(1, kProbeWaves / p.ptiles) * 2 * (size_t)p.p_pad * 8;
+}
+
+// Probe row `rel` of the call: the field of [0, S->n + nfoil) -- the wake before step s's roll-up, its shed vortices, the
+// staged bound vortices -- at the probes.  Enqueued right behind march_solve of step s on the stream that ran it, so before
+// the roll-up's finisher moves anything.  The slab is the probes' own buffer, written and read only by these two kernels in
+// stream order (the next step's pair follows this step's finisher, which follows this pair).  Reads the wake, writes
+// nothing of it: rows, state, hist and the resident wake keep their bits.
+int march_probe_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s, long long rel, long long rows) {
+  const MarchSetup& m = c->msetup;
+  const size_t P = c->probe_count;
+  const ProbePlan p = probe_plan(P, n_ub + (long long)m.npan);
+  const double* pxz = static_cast<const double*>(c->probe_xz.p);
+  const double* shift = c->probe_shifted ? static_cast<const double*>(c->probe_shift.p) + s : nullptr;
+  double* slab = static_cast<double*>(c->probe_part.p);
+  double* out = static_cast<double*>(c->probe_out.p);
+  hipLaunchKernelGGL(march_probe_partial, dim3((unsigned)p.ptiles, (unsigned)p.nsplit), dim3(kProbeLanes), 0, st, pxz, pxz + P, shift,
+                     (int)P, p.p_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                     static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(march_probe_finish, dim3(blocks_for((long long)(2 * P * 64))), dim3(kBlock), 0, st, (const double*)slab, p.p_pad,
+                     p.nsplit, (int)P, out + (size_t)rel * P, out + ((size_t)rows + (size_t)rel) * P);
+  HIPCHK(c, hipGetLastError());
+  return LUDVM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ludvm_march_set_probes(ludvm_ctx* c, const double* x, const double* z, size_t count, const double* shift_x, size_t shift_rows) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
+  if (count > LUDVM_MARCH_MAX_PROBES) return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_PROBES) + " probes");
+  if (count && (!x || !z)) return fail(c, LUDVM_E_ARG, "null array");
+  if (count && shift_x && shift_rows != c->march_kin_rows)
+    return fail(c, LUDVM_E_ARG, "march: probe offsets must be one per kinematics row");
+  for (size_t k = 0; k < count; ++k)
+    if (!std::isfinite(x[k]) || !std::isfinite(z[k])) return fail(c, LUDVM_E_ARG, "march: probe positions must be finite");
+  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
+    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: probe offsets must be finite");
+  c->probe_count = 0;
+  c->probe_rows = 0;
+  if (count == 0) return LUDVM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->probe_xz, 2 * count * 8));
+  CHK(ensure(c, c->probe_part, probe_slab_bytes(count)));
+  if (shift_x) CHK(ensure(c, c->probe_shift, shift_rows * 8));
+  double* pxz = static_cast<double*>(c->probe_xz.p);
+  HIPCHK(c, hipMemcpyAsync(pxz, x, count * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(pxz + count, z, count * 8, hipMemcpyHostToDevice, c->stream));
+  if (shift_x) HIPCHK(c, hipMemcpyAsync(c->probe_shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->probe_shifted = shift_x != nullptr;
+  c->probe_count = count;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_probes(ludvm_ctx* c, double* u, double* w, size_t rows) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->probe_count == 0) return fail(c, LUDVM_E_STATE, "march: no probes are set");
+  if (c->probe_rows == 0) return fail(c, LUDVM_E_STATE, "march: no ludvm_march_run call has left probe rows");
+  if (!u || !w) return fail(c, LUDVM_E_ARG, "null array");
+  if (rows != c->probe_rows) return fail(c, LUDVM_E_ARG, "march: rows must equal the count of the last ludvm_march_run call");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = rows * c->probe_count;
+  const double* out = static_cast<const double*>(c->probe_out.p);
+  HIPCHK(c, hipMemcpyAsync(u, out, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(w, out + n, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LUDVM_OK;
+}
 
 int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int precision, double* state, double* rows,
                     double* hist, size_t hist_nmax, const long long* anchors) {
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
+  c->probe_rows = 0;
   if (!valid_precision(precision)) return fail(c, LUDVM_E_ARG, "unknown precision");
   if (!state || !rows) return fail(c, LUDVM_E_ARG, "null array");
   if (count < 1 || first_step < 1 || (size_t)(first_step + count) > c->march_kin_rows)
@@ -139,6 +230,8 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   CHK(ensure(c, c->symsc, 128));
   CHK(ensure(c, c->march_rows, (size_t)count * row_doubles * 8));
   if (hist) CHK(ensure(c, c->march_hist, (size_t)count * 2 * hist_nmax * 8));
+  const bool probes = c->probe_count != 0;
+  if (probes) CHK(ensure(c, c->probe_out, (size_t)count * 2 * c->probe_count * 8));      // (the slab: ludvm_march_set_probes)
 
   MarchState hs{};
   hs.n = n0;
@@ -264,6 +357,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
       hipLaunchKernelGGL(march_solve, dim3(1), dim3(kBlock), 0, c->stream, m, S, krow_s, row, s, c->x64, c->z64, c->g64,
                          c->mir(), c->g32, c->progress_dev);
       HIPCHK(c, hipGetLastError());
+      if (probes) CHK(march_probe_launch(c, c->stream, n_ub, s, rel, count));
       MarchSym ms;
       ms.scale = &S->sc[(s + 1) & 1]; ms.bad = &S->sym_bad; ms.n_lo = n_lo + 1; ms.march = overlap_ok;
       CHK(advect_launch(c, (size_t)n_ub, &S->n, m.dt, nfoil, c->march_vcore, precision, nullptr, nullptr, td, ms));
@@ -292,6 +386,8 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
                            c->mir(), c->g32, c->progress_dev);
         if (hipGetLastError() != hipSuccess) rc = fail(c, LUDVM_E_HIP, "march_solve launch failed");
       }
+      // (probes: behind the solve on the second stream, before ev_join lets the finisher move the wake)
+      if (rc == LUDVM_OK && probes) rc = march_probe_launch(c, c->stream_b, n_ub, s, rel, count);
       c->stream = main_stream;
       CHK(rc);
       HIPCHK(c, hipEventRecord(c->ev_join, c->stream_b));
@@ -349,6 +445,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   for (int k = 0; k < 4; ++k) state[12 + k] = tailbuf[k];
   for (int k = 0; k < m.ncoef; ++k) state[16 + k] = hs.prevA[k];
   if (c->timing) CHK(drain_timing(c));
+  if (probes) c->probe_rows = (size_t)count;
   return LUDVM_OK;
 }
 

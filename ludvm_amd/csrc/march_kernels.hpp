@@ -479,4 +479,93 @@ march_finish_sym(long long* acc_u, long long* acc_w, const SymScale* sc, MarchSt
   tail_duty(td, i, n, xn, zn);
 }
 
+// ---- velocity probes (ludvm_march_set_probes) ---------------------------------------------------------------------------------
+// For time step i >= 1 and probe point p, (u, w)_i(p) is the field that convects the wake in step i, evaluated at p: the
+// reference's  induced_velocity(circulation_wake, xw, zw, p) + induced_velocity(circulation_foil, xa, za, p)  of
+// LUDVM.py:1095-1106 with xp, zp = p -- the wake BEFORE the Euler update of step i, the vortices shed in step i at their
+// placement, the bound vortices of step i at airfoil_gamma_points[i]; Vatistas core, no freestream term; a probe that
+// coincides with a vortex gets 0 from it (dx = dz = 0 against a finite core).  Right after march_solve of step i those
+// sources are ONE contiguous range [0, S->n + nfoil) of x64 / z64 / g64, and nothing moves them before the roll-up's
+// finisher, which the probe kernels precede in stream order (ludvm_march_run).  Always float64, like the chord sums.
+//
+// march_probe_partial  grid = probe tiles (64 probes: one per lane of a one-wavefront workgroup) x source splits; every lane
+//                      walks its split's sources in order from LDS tiles (all lanes read the same address: a broadcast),
+//                      its probe's position -- with the step's x offset added -- in registers; the source count is read on
+//                      the device; (split, probe) partial sums go to a slab [split][2][p_pad]
+// march_probe_finish   one wavefront per output column (component x probe): splits lane, lane + 64, ... then the fixed
+//                      shuffle tree of march_chord_finish; writes the step's row of the call's probe buffer
+// The splits are a function of the probe count and of the step's anchor-derived bound alone (probe_plan, march.hip), and
+// every partial sum is formed by one lane in source order: the bits do not depend on how a run is cut into calls.
+constexpr int kProbeLanes = 64;
+constexpr int kProbeTile = 256;
+
+__global__ void __launch_bounds__(kProbeLanes)
+march_probe_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, int count, long long p_pad,
+                    const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
+                    const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
+  __shared__ __attribute__((aligned(16))) double lx[kProbeTile];
+  __shared__ __attribute__((aligned(16))) double lz[kProbeTile];
+  __shared__ __attribute__((aligned(16))) double lg[kProbeTile];
+  // like the solve chain, these waves run beside a roll-up kernel that keeps every SIMD's issue slots busy
+  __builtin_amdgcn_s_setprio(3);
+  const int lane = threadIdx.x;
+  const long long p = (long long)blockIdx.x * kProbeLanes + lane;
+  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
+  const long long s_begin = (long long)blockIdx.y * chunk;
+  long long s_end = s_begin + chunk;
+  if (s_end > ns) s_end = ns;
+  double xp = 0.0, zp = 0.0;
+  if (p < count) {
+    xp = px[p] + (shift ? *shift : 0.0);
+    zp = pz[p];
+  }
+  double au = 0.0, aw = 0.0;
+  for (long long base = s_begin; base < s_end; base += kProbeTile) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kProbeTile / kProbeLanes; ++k) {
+      const int l = lane + k * kProbeLanes;
+      const long long si = base + l;
+      const bool ok = si < s_end;
+      lx[l] = ok ? xs[si] : kPadPosD;
+      lz[l] = ok ? zs[si] : kPadPosD;
+      lg[l] = ok ? gs[si] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < kProbeTile; ++j) {
+      const double dx = xp - lx[j];
+      const double dz = zp - lz[j];
+      const double r2 = __builtin_fma(dz, dz, dx * dx);
+      const double q = __builtin_fma(r2, r2, vc4);
+      const double s = lg[j] * rsqrt_f64(q);
+      au = __builtin_fma(dz, s, au);
+      aw = __builtin_fma(dx, s, aw);
+    }
+  }
+  if (p < count) {
+    // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
+    double* row = slab + (long long)blockIdx.y * 2 * p_pad;
+    row[p] = au * kInv2PiD;
+    row[p_pad + p] = -aw * kInv2PiD;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_probe_finish(const double* slab, long long p_pad, int nsplit, int count, double* out_u, double* out_w) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long gtid = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const long long col = gtid >> 6;
+  const int lane = threadIdx.x & 63;
+  if (col >= 2LL * count) return;   // whole wavefronts leave together
+  const int k = (int)(col / count);
+  const long long p = col - (long long)k * count;
+  const double* c0 = slab + k * p_pad + p;
+  double acc = 0.0;
+  for (int sidx = lane; sidx < nsplit; sidx += 64) acc += c0[(long long)sidx * 2 * p_pad];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (lane == 0) (k == 0 ? out_u : out_w)[p] = acc;
+}
+
 }  // namespace ludvm

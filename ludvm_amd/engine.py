@@ -370,6 +370,7 @@ class Engine:
             raise ValueError("march_setup: wrong table length")
         self._check(self._lib.ludvm_march_setup(self._ctx, int(npan), int(ncoef), _pd(sc), _pd(tb), _pd(kin), kin.shape[0]))
         self._march_dims = (int(npan), int(ncoef))
+        self._march_nprobes = 0          # (ludvm_march_setup forgets any probes)
 
     def march_run(self, first_step, count, precision, state, hist_nmax=0, anchors=None):
         """Advance the resident wake through time steps [first_step, first_step + count) without a host round
@@ -389,6 +390,24 @@ class Engine:
         self._check(self._lib.ludvm_march_run(self._ctx, int(first_step), int(count), _prec(precision), _pd(state), _pd(rows),
                                               _pd(hist), int(hist_nmax), anc))
         return (rows, hist) if hist_nmax else rows
+
+    def march_set_probes(self, x, z, shift_x=None):
+        """Points at which every marched step also evaluates the field that convects the wake (ludvm_march_set_probes);
+        valid after `march_setup`, which forgets them.  shift_x: None, or one x offset per kinematics row -- in step i probe
+        k sits at (x[k] + shift_x[i], z[k]).  Empty x removes the probes."""
+        xs, zs = _f64(x), _f64(z)
+        if len(xs) != len(zs):
+            raise ValueError("march_set_probes: x and z must have the same length")
+        sh = None if shift_x is None else _f64(shift_x)
+        self._check(self._lib.ludvm_march_set_probes(self._ctx, _pd(xs), _pd(zs), len(xs), _pd(sh), 0 if sh is None else len(sh)))
+        self._march_nprobes = len(xs)
+
+    def march_probes(self, count):
+        """(u, w), float64 [count, P]: the probe rows of the last `march_run` call, which ran `count` steps
+        (ludvm_march_read_probes)."""
+        u, w = np.empty([int(count), self._march_nprobes]), np.empty([int(count), self._march_nprobes])
+        self._check(self._lib.ludvm_march_read_probes(self._ctx, _pd(u), _pd(w), int(count)))
+        return u, w
 
     @staticmethod
     def march_anchor_steps(first_step):

@@ -28,6 +28,7 @@ _REFUSED = {
     "devices": (None, "a sweep runs on one GPU (members are independent: split the list per device)"),
     "march": (True, "the members of a sweep are marched on the device"),
     "run": (True, "the members of a sweep are run"),
+    "probes": (None, "a sweep has no velocity probes (a member can be run on its own: LUDVM(..., probes=...))"),
 }
 
 
@@ -50,7 +51,7 @@ def _check_case(idx, kw, first):
         if key in kw:
             raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
     for key, (fine, why) in _REFUSED.items():
-        if key in kw and not (kw[key] is fine or kw[key] == fine):
+        if key in kw and not (kw[key] is fine or (fine is not None and kw[key] == fine)):
             raise ValueError(who + f"{key}={kw[key]!r}: {why}")
     if kw.get("precision", "auto") not in ("auto", "f64"):
         raise ValueError(who + f"precision={kw['precision']!r}: the members of a sweep run in float64 ('auto' or 'f64')")
@@ -87,7 +88,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls
     Npoints and Ncoeffs are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
-    history='full', checkpoint_*, distributed, devices, march=False, run=False, an engine without ensemble_run.
+    history='full', checkpoint_*, distributed, devices, probes, march=False, run=False, an engine without ensemble_run.
 
     Out of scope: fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""

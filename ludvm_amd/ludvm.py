@@ -98,6 +98,15 @@ class LUDVM:
       march      True (default): stretches of time steps whose history row is not recorded run as a
                  device-resident march (Gamma solve on the GPU, no host round trip per step);
                  False: one device round trip per step throughout
+      probes     None (default), or points [2, P] (x row, z row; 1 <= P <= 4096) at which every time step also records the
+                 velocity field that convects the wake in that step (LUDVM.py:1095-1106 with xp, zp = the points: wake before
+                 the step's roll-up incl. the vortices shed in it, plus the step's bound vortices; Vatistas core, no freestream
+                 term): `probe_u`, `probe_w` float64 [nt, P] (row 0: the field of the initial free vortices), `probe_xz` as
+                 given, `probe_positions(step)` -> lab coordinates [2, P].  Evaluated inside the device-resident march (or from
+                 two engine calls per step on the per-step path), always in float64: the signal the reference would compute
+                 from its dense history, for runs that cannot keep one.  One GPU only.  Results are unchanged by it, bit for bit
+      probe_frame  'lab' (default): the points are fixed in the lab frame; 'tunnel': x is measured from the pivot's
+                 x-coordinate -- the lab position at step i is (x + xpiv[i], z) (the frame translates only)
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -118,8 +127,28 @@ class LUDVM:
             from .multi import MultiDeviceLUDVM, normalise_devices
             devs = normalise_devices(devices)
             if len(devs) > 1:
+                if kwargs.get('probes') is not None:
+                    cls._check_probes(kwargs['probes'], kwargs.get('probe_frame', 'lab'))
+                    raise ValueError("probes run on one GPU: not with more than one device in `devices`")
                 return MultiDeviceLUDVM(args, kwargs, devs)
         return super().__new__(cls)
+
+    @staticmethod
+    def _check_probes(probes, probe_frame):
+        """-> float64 [2, P], or ValueError (nothing else has been created yet)."""
+        if probe_frame not in ('lab', 'tunnel'):
+            raise ValueError("probe_frame must be 'lab' or 'tunnel'")
+        try:
+            xz = np.array(probes, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError("probes must be an array-like [2, P] of numbers") from e
+        if xz.ndim != 2 or xz.shape[0] != 2 or xz.shape[1] < 1:
+            raise ValueError(f"probes must be [2, P] with P >= 1 (x row, z row); got shape {xz.shape}")
+        if xz.shape[1] > 4096:
+            raise ValueError(f"probes: at most 4096 points (got {xz.shape[1]})")
+        if not np.isfinite(xz).all():
+            raise ValueError("probes must be finite")
+        return np.ascontiguousarray(xz)
 
     def __init__(self, t0=0, tf=12, dt=1.5e-2, chord=1, rho=1.225, Uinf=1,
                  Npoints=80, Ncoeffs=30, LESPcrit=0.2, Naca='0012',
@@ -128,7 +157,15 @@ class LUDVM:
                  verbose=True, method='Faure',
                  circulation_freevort=None, xy_freevort=None, *,
                  engine=None, device=0, precision='auto', history='auto', snapshot_steps=(), run=True,
-                 checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None):
+                 checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
+                 probes=None, probe_frame='lab'):
+        if probes is not None:
+            # refused before any engine, thread or communicator exists
+            probe_xz = self._check_probes(probes, probe_frame)
+            if distributed is not None and distributed is not False:
+                raise ValueError("probes run on one GPU: not with `distributed`")
+        elif probe_frame not in ('lab', 'tunnel'):
+            raise ValueError("probe_frame must be 'lab' or 'tunnel'")
         if devices is not None:             # (one device: an ordinary single-GPU run on it)
             from .multi import normalise_devices
             device = normalise_devices(devices)[0]
@@ -136,6 +173,9 @@ class LUDVM:
                           LESPcrit=LESPcrit, Naca=Naca, foil_filename=foil_filename, G=G, T=T, alpha_m=alpha_m,
                           alpha_max=alpha_max, k=k, phi=phi, h_max=h_max, method=method, precision=precision,
                           history=history, snapshot_steps=sorted(int(s) for s in snapshot_steps))
+        if probes is not None:              # (a run without probes keeps the attributes -- and the checkpoints -- it had)
+            self._ctor.update(probes=probe_xz.tolist(), probe_frame=probe_frame)
+            self.probe_xz, self.probe_frame = probe_xz, probe_frame
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -421,7 +461,7 @@ class LUDVM:
         __slots__ = (
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
-            'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk',
+            'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
@@ -511,7 +551,20 @@ class LUDVM:
         S.lesp_crit = self.LESPcrit
         S.LEV_shed = -1 * np.ones(nt)
         S.first_step = 1
+        S.probes = getattr(self, 'probe_xz', None)
+        if S.probes is not None:
+            # row 0: the field of the initial free vortices (:1202-1206)
+            self.probe_u, self.probe_w = np.zeros([nt, S.probes.shape[1]]), np.zeros([nt, S.probes.shape[1]])
+            p0 = self.probe_positions(0)
+            self.probe_u[0], self.probe_w[0] = eng.induce(g_free, free0[0], free0[1], p0[0], p0[1], self.v_core, precision='f64')
         return S
+
+    def probe_positions(self, step):
+        """Lab coordinates [2, P] of the probes at time step `step` ('tunnel' frame: x + xpiv[step])."""
+        xz = self.probe_xz.copy()
+        if self.probe_frame == 'tunnel':
+            xz[0] = xz[0] + self.xpiv[int(step)]
+        return xz
 
     def _loop_restore(self, S, R):
         """The loop's state as a checkpoint holds it (`_write_checkpoint_file`)."""
@@ -525,6 +578,8 @@ class LUDVM:
             C[key][...] = R['circ_' + key]
         for name in ('Fn', 'Fs', 'L', 'D', 'T', 'M', 'fourier', 'LESP', 'LESP_prev'):
             getattr(self, name)[...] = R[name]
+        if S.probes is not None:
+            self.probe_u[:S.first_step], self.probe_w[:S.first_step] = R['probe_u'], R['probe_w']
         for key in ('TEV', 'LEV', 'FREE'):
             if self.history == 'full':
                 P[key][:S.first_step] = R['path_' + key]
@@ -551,6 +606,8 @@ class LUDVM:
                        and 4 <= self.Ncoeffs <= 64)
         if S.can_march:
             eng.march_setup(npan, self.Ncoeffs, *self._march_inputs(S))
+            if S.probes is not None:
+                eng.march_set_probes(S.probes[0], S.probes[1], shift_x=self.xpiv if self.probe_frame == 'tunnel' else None)
         # with the dense history every step's row is recorded: the march then keeps a snapshot of the wake per step on
         # the device (shorter calls, the snapshots are [steps, 2, wake size])
         S.dense_march = S.can_march and self.history == 'full'
@@ -605,6 +662,9 @@ class LUDVM:
             j += 1
             if self.checkpoint_every and (j - 1) % self.checkpoint_every == 0:
                 break
+        if S.probes is not None:
+            # one call's probe rows ([steps, 2, P] doubles) stay at or under 256 MB, like the history rows
+            j = min(j, i + max(1, int(getattr(self, '_probe_call_bytes', 256e6) // (16 * S.probes.shape[1]))))
         return j, rec_i
 
     def _march_call(self, S, i, j, rec_i, print_dt):
@@ -642,6 +702,8 @@ class LUDVM:
             R, hist = self.engine.march_run(i, cnt, S.prec_code, st, hist_nmax=n_wake + 2 * cnt, anchors=anchors)
         else:
             R = self.engine.march_run(i, cnt, S.prec_code, st, anchors=anchors)
+        if S.probes is not None:
+            self.probe_u[i:j], self.probe_w[i:j] = self.engine.march_probes(cnt)
         self._store_march_results(S, i, j, st, R, hist)
 
     def _store_march_results(self, S, i, j, st, R, hist=None):
@@ -853,6 +915,15 @@ class LUDVM:
             # the reference also convects LEV slot `ilev` (zero strength, at the origin) on a
             # non-shedding step and stores it in path['LEV'][i]; reproduce that row entry
             new_x.append(0.0); new_z.append(0.0); new_g.append(0.0)
+        if S.probes is not None:
+            # the field that convects the wake in this step, at the probes: the old wake (still all the device holds) plus
+            # one float64 call for the shed vortices and the bound vortices
+            px, pz = self.probe_positions(i)
+            ns = 2 if shed else 1          # (not the phantom LEV slot of a recorded step)
+            uo, wo = eng.wake_induce_on_points(0, n_wake, px, pz, vc)
+            un, wn = eng.induce(np.concatenate([new_g[:ns], dGamma]), np.concatenate([new_x[:ns], xg]), np.concatenate([new_z[:ns], zg]),
+                                px, pz, vc, precision='f64')
+            self.probe_u[i], self.probe_w[i] = uo + un, wo + wn
         n_after = n_wake + len(new_x)
         one_trip = (not record) and sb is not None and i < nt - 1 and hasattr(eng, 'wake_step_into')
         if not one_trip:
@@ -946,6 +1017,8 @@ class LUDVM:
             d['circ_' + key] = C[key]
         for name in ('Fn', 'Fs', 'L', 'D', 'T', 'M', 'fourier', 'LESP', 'LESP_prev'):
             d[name] = getattr(self, name)
+        if S.probes is not None:        # (the definition travels in `ctor`)
+            d['probe_u'], d['probe_w'] = self.probe_u[:next_step], self.probe_w[:next_step]
         if self.history == 'full':
             for key in ('TEV', 'LEV', 'FREE'):
                 d['path_' + key] = P[key][:next_step]
@@ -973,6 +1046,8 @@ class LUDVM:
             if len(devs) > 1:
                 if engine is not None or distributed is not None:
                     raise ValueError("devices=[...] creates the engines and their communicator itself: do not pass engine= / distributed=")
+                if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('probes') is not None:
+                    raise ValueError("probes run on one GPU: this checkpoint cannot be resumed on more than one device")
                 return MultiDeviceLUDVM((), {}, devs, builder=lambda r, eng, grp: cls.resume(
                     path, engine=eng, verbose=verbose and r == 0, checkpoint_every=checkpoint_every, checkpoint_path=checkpoint_path,
                     march=march, distributed=grp))
