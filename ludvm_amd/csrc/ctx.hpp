@@ -1,6 +1,6 @@
 // Shared by the translation units of libludvm_hip.so: the context, error plumbing, the staging arena, and the internal
 // host functions one unit offers the others.  Kernels are NOT here: templates and device helpers live in pair_kernels.hpp /
-// pair_sym_kernels.hpp (includable anywhere); every non-template kernel lives in a header that exactly one unit includes
+// pair_sym_kernels.hpp (includable anywhere; the symmetric launch rule, host and device, in sym_rule.hpp); every non-template kernel lives in a header that exactly one unit includes
 // (sym_prepare_kernels.hpp -> launch.hip, induce_kernels.hpp -> induce.hip, wake_kernels.hpp -> wake.hip, march_kernels.hpp and
 // ensemble_kernels.hpp -> march.hip, field_kernels.hpp -> flowfield.hip, order_kernels.hpp -> order.hip).
 //
@@ -74,7 +74,7 @@ struct ludvm_ctx {
                                              // 4 x 4 from 2^20 grid points and 2 x 4 below; 3 / 4 = always the 2 x 4 / 4 x 4 patch
   long long small_tile_max = 14000;          // direct fp32 launches with at most this many sources use 256-source tiles
   bool sym_quad = true;                      // large symmetric launches: four I tiles per workgroup share each partner tile (LUDVM_SYM_QUAD=0: off)
-  long long sym_quad_min_tiles = 640;        //   ... from this many 512-vortex tiles on (LUDVM_SYM_QUAD_MIN_TILES)
+  long long sym_quad_min_tiles = kSymQuadMinTiles;   //   ... from this many 512-vortex tiles on (LUDVM_SYM_QUAD_MIN_TILES)
   bool few_packed = true;                    // fp64 launches with <= 128 targets: several source splits per workgroup (LUDVM_FEW_PACKED=0: off)
   long long small_tile_max_f64 = 12000;      // fp64 launches with at most this many sources use 128-source tiles
                                              // (roll-up step 52 -> 26 us at 2400 vortices, 87 -> 72 at 8192 [MI355X])
@@ -214,7 +214,7 @@ int induce_device(ludvm_ctx* c, const PairArgs& a, long long nt, long long ns, i
                   long long plan_nt = 0);
 long long sym_threshold(const ludvm_ctx* c, bool march = false);
 bool use_symmetric(const ludvm_ctx* c, long long n, double vc4, bool march = false);
-int sym_tile_t(const ludvm_ctx* c, long long n, bool hilo, bool local = false);
+int sym_tile_t(const ludvm_ctx* c, long long n, bool hilo);
 
 struct SymOperands {
   const float* x; const float* z; const float* g;

@@ -34,7 +34,7 @@ int ludvm_induce_f64(ludvm_ctx* c, const double* xs, const double* zs, const dou
   const bool f64 = precision == LUDVM_PREC_F64;
   bool hilo = precision == LUDVM_PREC_F32X2;
   // the caller passed the same arrays as sources and targets: self-interaction (the targets are not uploaded twice,
-  // and from kSymMinN vortices the symmetric kernel takes it)
+  // and from kSymMinN vortices (sym_rule.hpp) the symmetric kernel takes it)
   const bool self = xt == xs && zt == zs && nt == ns;
   const size_t ntu = self ? 0 : nt;                       // targets uploaded
   const size_t in_doubles = 3 * ns + 2 * ntu, out_doubles = 2 * nt;

@@ -226,37 +226,26 @@ int induce_device(ludvm_ctx* c, const PairArgs& a, long long nt, long long ns, i
   return LUDVM_OK;
 }
 
-constexpr long long kSymMinN = 16384;   // below this the direct kernel's launch is as fast
-// Vortices per lane of the symmetric kernel: 8 (tile 512, 158-162 VGPRs: 3 waves/SIMD) from ~4e4 vortices up, where
-// halving the rotation / LDS-read cost per pair wins 2-7 % (with the rotation steps of a tile pair shared by two or four
-// waves below ~8e4); 4 (tile 256, 70-90 VGPRs) below, where more and smaller tiles balance better, and for hi+lo
-// positions (not instantiated for the 512-vortex tile: hi+lo is instruction-bound either way).
-// Round 6 (profiles/r06_mid_size_variant_table.txt: every candidate forced at 22 sizes, ordered sheet, sustained load): between
-// 35 000 and 44 000 vortices the two tiles alternate within +-2 % with the parity of their tile counts; the one size where the
-// pick lost more (36 000: 512-vortex tiles 3.5 % behind) is what moved the switch from 34 816 to 36 864 = 72 tiles of 512.
-constexpr long long kSymT8MinN = 36864;
 static_assert(64 * 8 == LUDVM_SYM_TILE, "the multi-GPU entry points always use the 512-vortex tile");
 
-// The symmetric kernel accumulates in fixed point, which needs the bound sum|Gamma| / (sqrt(2) v_core) on the raw
-// sums: point vortices (v_core = 0, or so small that v_core^4 vanishes in fp32) take the direct kernel.
-// In the march a symmetric step is an OVERLAPPED step: chord sums and solve run beside the kernel instead of in front
-// of it (~40 us of a ~60 us serial step at 1e4 vortices), so it pays earlier there: from ~11 000 vortices [MI355X]
-// (profiles/r02_march_symmetric_threshold.txt).
-constexpr long long kSymMinNMarch = 11264;
-long long sym_threshold(const ludvm_ctx* c, bool march) {
-  return c->sym_mode == 1 ? (march ? kSymMinNMarch : kSymMinN) : (long long)c->sym_mode;
+// The launch rule itself is sym_rule.hpp; these hand it the context's settings.
+SymKnobs sym_knobs(const ludvm_ctx* c) {
+  SymKnobs k;
+  k.sym_mode = c->sym_mode;
+  k.tile_t = c->tune_sym_t;
+  k.tune_split = c->tune_split;
+  k.tune_rsplit = c->tune_sym_rsplit;
+  k.quad = c->sym_quad;
+  k.quad_min_tiles = c->sym_quad_min_tiles;
+  k.tail_items = c->sym_tail_items;
+  return k;
 }
+long long sym_threshold(const ludvm_ctx* c, bool march) { return sym_min_n(sym_knobs(c), march); }
 bool use_symmetric(const ludvm_ctx* c, long long n, double vc4, bool march) {
-  if (c->sym_mode == 0 || !((float)vc4 > 0.0f)) return false;
-  return n >= sym_threshold(c, march);
+  return sym_use(sym_knobs(c), n, (float)vc4 > 0.0f, march);
 }
-
-int sym_tile_t(const ludvm_ctx* c, long long n, bool hilo, bool local) {
-  (void)local;                        // local origins fit both tiles (a 512-vortex tile keeps its targets twice)
-  if (hilo) return 4;                 // hi+lo positions: 256-vortex tile only
-  if (c->tune_sym_t == 4 || c->tune_sym_t == 8) return c->tune_sym_t;
-  return n >= kSymT8MinN ? 8 : 4;
-}
+// (local origins fit both tiles: a 512-vortex tile keeps its targets twice)
+int sym_tile_t(const ludvm_ctx* c, long long n, bool hilo) { return sym_tile(sym_knobs(c), n, hilo); }
 
 // Symmetric kernel over I tiles [i_first, i_first + i_count) of the tile ring of (x, z, g)[0, n); raw fixed-point
 // sums are ADDED into acc_u / acc_w (n each, zeroed by the caller).  The partition of the work into partial sums
@@ -270,15 +259,14 @@ int launch_sym_tiles(ludvm_ctx* c, int T, const SymOperands& o, long long n, lon
   a.n_dev = n_dev;
   a.xl = o.xl; a.zl = o.zl;
   a.cx = o.cx; a.cz = o.cz;
-  const bool hilo = o.xl && o.zl;
-  if (hilo) T = 4;
-  a.tune_split = c->tune_split;
-  // (hi+lo positions keep one granularity per launch: the mixed form was measured on plain fp32 positions only)
-  a.tune_rsplit = (hilo && c->tune_sym_rsplit == 0) ? -2 : c->tune_sym_rsplit;
+  const SymKnobs k = sym_knobs(c);
+  const SymVariant v = sym_variant(k, n, T, o.xl && o.zl);
+  const SymGeom& gm = v.g;
+  a.tune_split = k.tune_split;
+  a.tune_rsplit = v.tune_rsplit;
   a.shard_rank = (n_dev && sharded) ? c->shard_rank : 0;       // (host-sized launches get their tile block as arguments)
   a.shard_world = (n_dev && sharded) ? c->shard_world : 1;
-  a.tail_items = c->sym_tail_items;
-  const SymGeom gm = sym_geometry(n, T, a.tune_split, a.tune_rsplit, a.tail_items);
+  a.tail_items = k.tail_items;
   a.ntiles = gm.ntiles;
   a.dmax = gm.dmax;
   a.i_first = i_first;
@@ -295,22 +283,12 @@ int launch_sym_tiles(ludvm_ctx* c, int T, const SymOperands& o, long long n, lon
   a.vc4 = (float)vc4;
   // workgroups: 4 / rsplit items (tile, d-chunk) each
   long long blocks = sym_blocks(i_count, gm.ysplit, gm.rsplit, gm.ytail, gm.rbulk, c->xcd_run);
-  if (n_dev) {
-    const long long W = 64LL * T;
-    for (long long nt = std::max<long long>(1, (std::max<long long>(n_lo, 1) + W - 1) / W); nt <= gm.ntiles; ++nt) {
-      const SymGeom q = sym_geometry(nt * W, T, a.tune_split, gm.rsplit == 0 ? -1 : gm.rsplit, a.tail_items);    // the waves-per-item rule fixed by the bound: it picks the kernel
-      blocks = std::max(blocks, sym_blocks(q.ntiles, q.ysplit, gm.rsplit, q.ytail, q.rbulk, c->xcd_run));
-    }
-  }
+  if (n_dev) blocks = std::max(blocks, sym_grid_bound(k, v, false, n_lo, n, c->xcd_run));
   if (!n_dev && i_count == 0) return LUDVM_OK;     // an owner without tiles (fewer tiles than owners)
   blocks = std::max<long long>(blocks, 1);         // (n_dev: the share is decided on the device; surplus waves leave)
   // Large launches: the quad variant (four I tiles of a workgroup share each partner tile: a quarter of the atomics) plus a
-  // launch of the plain kernel restricted to the diagonal tiles.  The choice is a function of the vortex count (the march's
-  // bound) alone, so every owner of a sharded ring makes the same one; owners must own whole quads.
-  const bool one_wave_items = gm.rsplit == 1 || (gm.rsplit == 0 && gm.rbulk == 1);      // what the size rule gives at this size
-  const bool quad = T == 8 && !hilo && gm.ntiles >= 16 &&
-                    (c->tune_sym_rsplit == -4 || (c->sym_quad && one_wave_items && c->tune_sym_rsplit == 0 && gm.ntiles >= c->sym_quad_min_tiles));
-  if (quad) {
+  // launch of the plain kernel restricted to the diagonal tiles; owners of a sharded ring must own whole quads.
+  if (v.quad) {
     if (i_first % 4 != 0 || (i_count % 4 != 0 && i_first + i_count != gm.ntiles))
       return fail(c, LUDVM_E_ARG, "symmetric kernel, quad variant: an owner's tile block must start and end on multiples of 4 tiles");
     TimedLaunch tq{};
@@ -320,13 +298,9 @@ int launch_sym_tiles(ludvm_ctx* c, int T, const SymOperands& o, long long n, lon
     d.diag_only = 1;
     const long long dblocks = std::max<long long>(1, sym_blocks(n_dev ? gm.ntiles : i_count, 1, 1, 0, 1, c->xcd_run));
     hipLaunchKernelGGL((pair_sym_f32<8, false, 1>), dim3((unsigned)dblocks), dim3(kBlock), 0, c->stream, d);
-    const QuadGeom qg = quad_geometry<long long>(n, 8, a.tune_split);
-    long long qblocks = quad_blocks(n_dev ? gm.ntiles : i_count, qg.ysplit, c->xcd_run);
-    if (n_dev) {      // the device derives the chunks from its own vortex count: cover every count the bounds allow
-      const long long W = 64LL * 8;
-      for (long long nt = std::max<long long>(1, (std::max<long long>(n_lo, 1) + W - 1) / W); nt < gm.ntiles; ++nt)
-        qblocks = std::max(qblocks, quad_blocks(nt, quad_geometry<long long>(nt * W, 8, a.tune_split).ysplit, c->xcd_run));
-    }
+    long long qblocks = quad_blocks(n_dev ? gm.ntiles : i_count, v.q.ysplit, c->xcd_run);
+    // (the device derives the chunks from its own vortex count)
+    if (n_dev) qblocks = std::max(qblocks, sym_grid_bound(k, v, true, n_lo, n, c->xcd_run));
     hipLaunchKernelGGL((pair_sym_quad_f32<8>), dim3((unsigned)std::max<long long>(qblocks, 1)), dim3(kBlock), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     CHK(timed_end(c, tq, act));
@@ -344,8 +318,8 @@ int launch_sym_tiles(ludvm_ctx* c, int T, const SymOperands& o, long long n, lon
     case 2: hipLaunchKernelGGL((pair_sym_f32<TT, HH, 2>), grid, blk, 0, c->stream, a); break;                 \
     default: hipLaunchKernelGGL((pair_sym_f32<TT, HH, 4>), grid, blk, 0, c->stream, a); break;                \
   }
-  if (hilo) { LUDVM_SYM_LAUNCH(4, true) }
-  else if (T == 8) { LUDVM_SYM_LAUNCH(8, false) }
+  if (v.hilo) { LUDVM_SYM_LAUNCH(4, true) }
+  else if (v.T == 8) { LUDVM_SYM_LAUNCH(8, false) }
   else { LUDVM_SYM_LAUNCH(4, false) }
 #undef LUDVM_SYM_LAUNCH
   HIPCHK(c, hipGetLastError());
@@ -369,7 +343,7 @@ int acc_buffer(ludvm_ctx* c, long long nt_pad, long long** acc) {
 
 bool sharded_at(const ludvm_ctx* c, long long n) { return (c->shard_world > 1 || c->comm_force) && n >= c->shard_min_n; }
 
-// tile block of a shard owner (whole quads of 4 tiles: pair_sym_kernels.hpp, shard_block)
+// tile block of a shard owner (whole quads of 4 tiles: sym_rule.hpp, shard_block)
 void shard_tiles(const ludvm_ctx* c, long long ntiles, long long* first, long long* count) {
   unsigned long long f, cnt;
   shard_block((unsigned long long)ntiles, c->shard_rank, c->shard_world, &f, &cnt);
@@ -412,7 +386,7 @@ int launch_sym(ludvm_ctx* c, SymOperands o, long long n, double vc4, long long* 
   }
   const bool sharded = sharded_at(c, n);      // (n: exact, or the march's bound -- the same number on every owner)
   if (sharded) o.bad = acc - 2;               // counted where the all-reduce sees it
-  const int T = sym_tile_t(c, n, o.xl && o.zl, o.cx != nullptr);
+  const int T = sym_tile_t(c, n, o.xl && o.zl);
   const long long ntiles = (n + 64LL * T - 1) / (64LL * T);
   long long first = 0, count = ntiles;
   if (sharded) shard_tiles(c, ntiles, &first, &count);

@@ -392,7 +392,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
       CHK(rc);
       HIPCHK(c, hipEventRecord(c->ev_join, c->stream_b));
       const long long nb = std::max<long long>(n_before, 1);
-      const int T = sym_tile_t(c, nb, hilo, !hilo);
+      const int T = sym_tile_t(c, nb, hilo);
       const long long ntiles = (nb + 64LL * T - 1) / (64LL * T);
       SymOperands o{};
       o.g = c->g32;

@@ -6,18 +6,25 @@
 // ops + 1 v_rsq_f32 per ordered pair (24 issue cycles per 64 lanes on CDNA4); evaluating each
 // UNORDERED pair once costs 11 ops + 1 rsq per TWO ordered pairs (15 cycles per ordered pair).
 //
-// Wave-autonomous systolic scheme (no LDS, no barriers, no cross-lane reductions):
+// Systolic scheme: a wave's rotation loop needs no barrier and no cross-lane reduction; LDS holds the partner tile, and
+// workgroup barriers appear only where several waves share a work item (below):
 //   * vortices are cut into tiles of W = 64*T; a wavefront owns one tile I: lane l keeps T targets
 //     (x, z, Gamma, accumulators) in registers for its whole life;
-//   * for each partner tile J the lane loads T vortices of J the same way, with their own
-//     accumulators; lane l then evaluates its T x T pairs IN REGISTERS, updating both sides, and the
-//     J set (x, z, Gamma and its accumulators) is rotated one lane with v_mov_b32_dpp wave_rol:1;
-//     after 64 rotations every i of I has met every j of J and the J accumulators are back home;
+//   * each partner tile J is staged in an LDS slab (wave-private in pair_sym_f32, one per workgroup in the quad variant);
+//     at rotation step k lane l reads the T vortices of J's home lane l + k from the slab (ds_read_b128 at a per-lane
+//     rotating address), evaluates its T x T pairs in registers, updating both sides, and hands the 2 T J-side
+//     accumulators -- the only data that travels between lanes -- one lane on with v_mov_b32_dpp wave_rol:1; after 64
+//     steps every i of I has met every j of J and the J accumulators are back home;
 //   * tile pairs are enumerated cyclically, J = I + d (mod NT), d = 1 .. (NT-1)/2, so every unordered
 //     tile pair is visited once and every wave has the same amount of work; d = 0 (the diagonal tile,
-//     which holds the self pairs) is evaluated with the ordered formula.  Because the work of a tile I
+//     which holds the self pairs) runs through the SAME rotation code with its J-side sums dropped: every ordered
+//     pair of the tile is met from both lanes, so the I side alone is complete.  Because the work of a tile I
 //     depends on I alone, a GPU that owns a contiguous block of I tiles does exactly 1/G of the job
-//     (multi-GPU: the raw sums are then reduce-scattered, see ludvm_amd/sharded.py);
+//     (multi-GPU: the raw integer sums are then all-reduced, see ludvm_amd/sharded.py);
+//   * at mid sizes the 64 rotation steps of a tile pair are shared by 2 or 4 waves of a workgroup, whose partial sums
+//     are added through LDS in wave order (two workgroup barriers per round) before one set of atomics leaves; the quad
+//     variant does the same for four I tiles that share a partner tile.  Which of these a launch uses is a function
+//     of the vortex count alone: sym_rule.hpp;
 //   * results are accumulated into acc_u / acc_w (zeroed by the caller) as 64-BIT FIXED-POINT INTEGERS: each
 //     wave's partial sum -- an fp32 number computed in a fixed order -- is scaled by a per-launch power of two,
 //     truncated to an integer and added with global_atomic_add_x2.  Integer addition is associative, so the
@@ -29,6 +36,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pair_kernels.hpp"
+#include "sym_rule.hpp"      // which variant serves a launch, and its geometry (host and device)
 
 namespace ludvm {
 
@@ -70,176 +78,6 @@ struct SymArgs {
   // [i_first, i_first + i_count) is derived on the device from the tile count: tiles [NT r / G, NT (r + 1) / G)
   int shard_rank, shard_world;
 };
-
-// Launch geometry as a function of the vortex count alone (not of the owner's share, not of a host-side bound):
-// the partition of the work into partial sums -- and with it every bit of the result -- is then the same for a
-// march step sized from an upper bound, for one GPU and for G GPUs that own I-tile blocks of the same ring.
-constexpr long long kSymTargetWaves = 8 * 65536;   // (I, d-chunk) work items aimed for over the whole ring
-constexpr long long kSymMaxSplit = 64;
-constexpr long long kSymMaxSplitTuned = 1024;      // what ludvm_set_tuning may ask for (measurements)
-constexpr long long kXcds = 8;                        // XCDs of an MI355X: workgroup b is dispatched to XCD b % 8
-constexpr long long kSymMaxRsplit = 4;
-constexpr long long kSymMinItems = 10500;          // measured (profiles/r02_atomics_cost_and_lds_reduction.txt, table 4)
-// Mixed granularity (rsplit = 0): a launch ends when its last waves do, and a launch of equal work items drains over about
-// half an item's lifetime.  So the items that are dispatched LAST -- those of the highest d-chunks, in every owner's order
-// -- are worked by four waves each (a quarter of the rotation steps per wave, partial sums added through LDS), the bulk
-// before them by as many waves per item as the size rule gives (`rbulk` = 1 or 2; where the rule gives four there is
-// nothing finer and the launch keeps one granularity).  Which items those are is a function of the vortex count alone (their
-// d-chunk), so the partition into partial sums is the same for every owner of a sharded ring.  History [MI355X]: the first
-// form (bulk always by single waves, 3072 items for the end, chunk counts that could leave the end empty) lost as often
-// as it won (profiles/r03_mixed_granularity_negative_result.txt) and was shelved; with the bulk following the rule, no empty
-// chunks and 1536 items for the end it is never slower than one granularity under sustained load and 1-5 % faster from
-// 57 000 vortices up to the quad variant's range (profiles/r03_mixed_granularity_by_rule.txt), and is the default there.
-// ludvm_set_sym_tuning(.., -1) / LUDVM_SYM_MIXED=1: at every size; -2 / LUDVM_SYM_MIXED=0: nowhere.
-constexpr long long kSymTailItems = 1536;          // (half of 256 CUs x 4 SIMDs x 3 waves: measured, see above)
-struct SymGeom { long long ntiles, dmax, dtot; int ysplit, rsplit, ytail, rbulk; };
-// Placement of a launch's (unit, d-chunk) work items on the 8 XCDs (unit = I tile, or quad of I tiles): workgroup b runs
-// on XCD b % 8.  The launch's `ys` d-chunks are cut into at most 8 RUNS of K = ceil(ys / 8) consecutive chunks, and in run r
-// XCD x takes eighth (x + r) % 8 of the units.  Within a run an XCD works on neighbouring units whose ring offsets grow
-// chunk by chunk, i.e. on overlapping partner tiles, which its L2 serves (round 2's point: memory-side fetches 2 GB ->
-// 0.03 GB per N = 2^20 launch); and because the eighths ROTATE from run to run, every XCD meets every eighth once: all get
-// the same number of items to within K - 1.  With a fixed eighth per XCD (rounds 2 and 3 until this) a unit count that is
-// not a multiple of 8 left seven XCDs waiting for the eighth one: 129 tiles = 7 x 16 + 17, 6 % of the launch; 489 quads
-// (N = 1e6) = 7 x 61 + 62, 1.4 % [MI355X].  (Rotating with EVERY chunk balances to within one item, and was measured
-// first: same speed, but every chunk then meets new partner tiles: 1.0 GB of fetches per N = 1e6 launch instead of 0.03.)
-struct XcdShare { unsigned lo, n; };
-__host__ __device__ inline XcdShare xcd_share(unsigned units, unsigned e) {
-  const unsigned lo = (unsigned)((unsigned long long)units * e / (unsigned)kXcds);
-  return XcdShare{lo, (unsigned)((unsigned long long)units * (e + 1) / (unsigned)kXcds) - lo};
-}
-__host__ __device__ inline unsigned xcd_run(unsigned ys, int k) {
-  return k > 0 ? (unsigned)k : (ys > 0 ? (ys + (unsigned)kXcds - 1) / (unsigned)kXcds : 1);
-}
-// items of XCD x in chunks [y0, y0 + ny) of a launch of ys chunks
-__host__ __device__ inline unsigned long long xcd_items(unsigned units, unsigned ys, unsigned x, unsigned y0, unsigned ny,
-                                                         int k = 0) {
-  const unsigned K = xcd_run(ys, k);
-  unsigned long long t = 0;
-  for (unsigned y = y0; y < y0 + ny;) {
-    const unsigned r = y / K, y_end = (r + 1) * K < y0 + ny ? (r + 1) * K : y0 + ny;
-    t += (unsigned long long)xcd_share(units, (x + r) % (unsigned)kXcds).n * (y_end - y);
-    y = y_end;
-  }
-  return t;
-}
-// item q of XCD x's list over chunks [y0, y0 + ny) (run by run, chunk-major within a run): its chunk and unit; false
-// beyond the list
-__host__ __device__ inline bool xcd_item(unsigned units, unsigned ys, unsigned x, unsigned y0, unsigned ny, unsigned q,
-                                         unsigned& y_out, unsigned& unit, int k = 0) {
-  const unsigned K = xcd_run(ys, k);
-  y_out = y0; unit = 0;
-  for (unsigned y = y0; y < y0 + ny;) {
-    const unsigned r = y / K, y_end = (r + 1) * K < y0 + ny ? (r + 1) * K : y0 + ny;
-    const XcdShare s = xcd_share(units, (x + r) % (unsigned)kXcds);
-    const unsigned cnt = s.n * (y_end - y);
-    if (q < cnt) {               // (s.n > 0 here)
-      const unsigned c = q / s.n;
-      y_out = y + c;
-      unit = s.lo + (q - c * s.n);
-      return true;
-    }
-    q -= cnt;
-    y = y_end;
-  }
-  return false;
-}
-// Workgroups per XCD of a launch over i_count I tiles (the largest XCD's; surplus workgroups leave at once).  With
-// rsplit = 0 an XCD's first workgroups hold 4 / rbulk bulk items each (d-chunks below ysplit - ytail), the rest one
-// four-wave item each.
-__host__ __device__ inline long long sym_blocks_xcd(long long i_count, long long ysplit, int rsplit, long long ytail,
-                                                    int rbulk = 1, int k = 0) {
-  long long most = 0;
-  for (unsigned x = 0; x < (unsigned)kXcds; ++x) {
-    long long wg;
-    if (rsplit == 0) {
-      const unsigned y1 = (unsigned)(ysplit - ytail);
-      wg = ((long long)xcd_items((unsigned)i_count, (unsigned)ysplit, x, 0, y1, k) * rbulk + 3) / 4 +
-           (long long)xcd_items((unsigned)i_count, (unsigned)ysplit, x, y1, (unsigned)ytail, k);
-    } else {
-      const long long ipb = 4 / rsplit;
-      wg = ((long long)xcd_items((unsigned)i_count, (unsigned)ysplit, x, 0, (unsigned)ysplit, k) + ipb - 1) / ipb;
-    }
-    most = wg > most ? wg : most;
-  }
-  return most;
-}
-__host__ __device__ inline long long sym_blocks(long long i_count, long long ysplit, int rsplit, long long ytail = 0,
-                                                int rbulk = 1, int k = 0) {
-  return kXcds * sym_blocks_xcd(i_count, ysplit, rsplit, ytail, rbulk, k);
-}
-
-// Tile block of owner `rank` of `world` on a ring of ntiles tiles: whole quads of 4 consecutive tiles (the quad variant of
-// the kernel adds the partial sums of a quad's four waves in fp32 before they are converted, so a quad must not be cut
-// between two owners; the last block ends with the ring)
-__host__ __device__ inline void shard_block(unsigned long long ntiles, int rank, int world, unsigned long long* first,
-                                            unsigned long long* count) {
-  const unsigned long long quads = (ntiles + 3) / 4;
-  unsigned long long lo = 4 * (quads * (unsigned long long)rank / (unsigned long long)world);
-  unsigned long long hi = 4 * (quads * (unsigned long long)(rank + 1) / (unsigned long long)world);
-  if (lo > ntiles) lo = ntiles;
-  if (hi > ntiles) hi = ntiles;
-  *first = lo;
-  *count = hi - lo;
-}
-
-// (I: long long on the host, unsigned on the device -- the kernel's prologue runs once per wave and a 64-bit division
-// costs ~100 instructions there; both give the same numbers for n < 2^31)
-template <typename I>
-__host__ __device__ inline void sym_geometry_t(I n, int T, int tune_split, int tune_rsplit, I tail_items, I& ntiles, I& dmax,
-                                               I& dtot, int& ysplit, int& rsplit, int& ytail, int& rbulk) {
-  const I W = (I)(64 * T);
-  ntiles = (n + W - 1) / W;
-  dmax = ntiles > 0 ? (ntiles - 1) / 2 : 0;
-  dtot = dmax + ((ntiles % 2 == 0 && ntiles > 1) ? 1 : 0);
-  const I nt1 = ntiles > 0 ? ntiles : 1;
-  // (kSymTargetWaves / nt1 rounded up is at least kSymMaxSplit whenever nt1 <= kSymTargetWaves / kSymMaxSplit: no division)
-  I ys = tune_split > 0 ? (I)tune_split
-                        : (nt1 <= (I)(kSymTargetWaves / kSymMaxSplit) ? (I)kSymMaxSplit : ((I)kSymTargetWaves + nt1 - 1) / nt1);
-  if (ys > (I)kSymMaxSplit && tune_split <= 0) ys = (I)kSymMaxSplit;
-  if (ys > (I)kSymMaxSplitTuned) ys = (I)kSymMaxSplitTuned;
-  if (ys > dtot) ys = dtot;
-  if (ys < 1) ys = 1;
-  // no empty chunks: with `per` offsets per chunk, ceil(dtot / per) chunks cover the ring (96 offsets in 64 chunks would be 48
-  // chunks of 2 and 16 empty ones -- waves that leave at once, and a mixed launch's fine-grained end without any work)
-  if (dtot > 0) {
-    const I per0 = (dtot + ys - 1) / ys;
-    ys = (dtot + per0 - 1) / per0;
-  }
-  I rs = 1;
-  ytail = 0;
-  rbulk = 1;
-  if (tune_rsplit == -4) {                     // the quad variant, whatever the size: single-wave geometry
-    rs = 1;
-  } else if (tune_rsplit == 1 || tune_rsplit == 2 || tune_rsplit == 4) {
-    rs = (I)tune_rsplit;
-  } else if (tune_rsplit == -1) {              // mixed: the last d-chunks by four waves per item
-    rs = 0;
-    const I yt = (tail_items + nt1 - 1) / nt1;
-    ytail = (int)(yt > ys ? ys : yt);
-    I rb = 1;                                  // the bulk before them by as many waves per item as the size rule gives
-    while (rb < (I)kSymMaxRsplit && nt1 * ys * rb < (I)kSymMinItems) rb *= 2;
-    rbulk = (int)rb;
-  } else {                                     // by size: the smallest number of waves per item that gives enough work items
-    while (rs < (I)kSymMaxRsplit && nt1 * ys * rs < (I)kSymMinItems) rs *= 2;
-    // ... and, where that leaves room below four waves per item, the items dispatched last finer than the bulk (mixed
-    // granularity).  tune_rsplit = -2: one granularity per launch, as until round 3
-    if (tune_rsplit != -2 && rs < (I)kSymMaxRsplit) {
-      rbulk = (int)rs;
-      rs = 0;
-      const I yt = (tail_items + nt1 - 1) / nt1;
-      ytail = (int)(yt > ys ? ys : yt);
-    }
-  }
-  ysplit = (int)ys;
-  rsplit = (int)rs;
-}
-__host__ __device__ inline SymGeom sym_geometry(long long n, int T, int tune_split, int tune_rsplit,
-                                                 long long tail_items = kSymTailItems) {
-  SymGeom g;
-  sym_geometry_t<long long>(n, T, tune_split, tune_rsplit, tail_items, g.ntiles, g.dmax, g.dtot, g.ysplit, g.rsplit, g.ytail,
-                            g.rbulk);
-  return g;
-}
 
 // acc += trunc(v * scale): order-independent accumulation of an fp32 partial sum (rounded toward zero to a whole unit of
 // 1 / scale, i.e. 2^-61 of the bound on the sum: nine decimal digits below the fp32 rounding of the partial itself).
@@ -740,70 +578,10 @@ pair_sym_f32(SymArgs a) {
 // the single-wave kernel (whose every tile pair sends its own), i.e. of the launch's memory-side write traffic, for two
 // workgroup barriers per round (measured cost of those, by themselves: 0.1-0.25 % at N = 1e6).  Wave w misses the offsets
 // D - w outside 1 .. dtot at the two ends of the D range (three partly empty rounds per quad and launch), so the variant
-// is used from ~1000 tiles up, where that is < 0.5 % of a quad's rounds.  The diagonal tiles (the self pairs) are left
-// to a launch of pair_sym_f32 restricted to them (SymArgs::diag_only).  Owners of a sharded ring must own whole quads
-// (blocks of 4 tiles): the fp32 sum of four partials is not the integer sum of their conversions.
+// is used from 640 tiles up (kSymQuadMinTiles, sym_rule.hpp), where that is < 1 % of a quad's ~320 rounds.  The diagonal
+// tiles (the self pairs) are left to a launch of pair_sym_f32 restricted to them (SymArgs::diag_only).  Owners of a sharded
+// ring must own whole quads (blocks of 4 tiles): the fp32 sum of four partials is not the integer sum of their conversions.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr unsigned kQuad = 4;
-constexpr unsigned kQuadSplit = 128;
-struct QuadGeom { unsigned ntiles, dmax, dtot, Dtot; int ysplit, per, nlong, pshort; };
-template <typename I>
-__host__ __device__ inline QuadGeom quad_geometry(I n, int T, int tune_split) {
-  QuadGeom g;
-  const I W = (I)(64 * T);
-  const I nt = (n + W - 1) / W;
-  g.ntiles = (unsigned)nt;
-  g.dmax = nt > 0 ? (unsigned)((nt - 1) / 2) : 0;
-  g.dtot = g.dmax + ((nt % 2 == 0 && nt > 1) ? 1u : 0u);
-  g.Dtot = g.dtot + (kQuad - 1);
-  // d-chunks per quad.  An item of `per` rounds lives per x ~0.17 ms; a launch drains over about half the lifetime of the
-  // items dispatched LAST, while every item pays ~4 % of one round for its own targets (loads, I-side conversions and
-  // atomics).  Uniform chunks (measured at N = 1e6, same box: 64 chunks 112.0 ms, 128: 111.6, 256: 111.6;
-  // tools/ab_quad_chunks.sh) cannot have both small; so the chunks TAPER: with u = Dtot / 128 rounded up, the first seven
-  // eighths of the offsets go in chunks of 2 u rounds and the last eighth -- the highest chunk numbers, which every XCD
-  // dispatches last -- in chunks of u / 4 (at least 1) rounds.  A function of the vortex count alone, like everything
-  // about the partition.  ludvm_set_tuning(.., k > 0) asks for k uniform chunks instead (measurements).
-  if (tune_split > 0) {
-    unsigned ys = (unsigned)tune_split;
-    if (ys > (unsigned)kSymMaxSplitTuned) ys = (unsigned)kSymMaxSplitTuned;
-    if (ys > g.Dtot) ys = g.Dtot;
-    if (ys < 1) ys = 1;
-    g.per = (int)((g.Dtot + ys - 1) / ys);
-    g.ysplit = (int)((g.Dtot + (unsigned)g.per - 1) / (unsigned)g.per);     // (no empty chunk at the end)
-    g.nlong = g.ysplit;
-    g.pshort = g.per;
-    return g;
-  }
-  const unsigned u = (g.Dtot + kQuadSplit - 1) / kQuadSplit;
-  const unsigned P = 2 * (u > 0 ? u : 1), ps = u / 4 > 0 ? u / 4 : 1;
-  const unsigned nlong = (g.Dtot - g.Dtot / 8) / P;
-  const unsigned rest = g.Dtot - nlong * P;
-  g.per = (int)P;
-  g.pshort = (int)ps;
-  g.nlong = (int)nlong;
-  g.ysplit = (int)(nlong + (rest + ps - 1) / ps);
-  if (g.ysplit < 1) g.ysplit = 1;
-  return g;
-}
-// ring offsets D in [lo, hi) of d-chunk yq of a quad
-__host__ __device__ inline void quad_chunk(const QuadGeom& g, unsigned yq, int& lo, int& hi) {
-  const bool lg = (int)yq < g.nlong;
-  lo = 1 + (lg ? (int)yq * g.per : g.nlong * g.per + ((int)yq - g.nlong) * g.pshort);
-  hi = lo + (lg ? g.per : g.pshort);
-  if (hi > (int)g.Dtot + 1) hi = (int)g.Dtot + 1;
-}
-// workgroups of a quad launch over I tiles [i_first, i_first + i_count) (i_first a multiple of 4): one per (quad, d-chunk),
-// the same number for each XCD
-__host__ __device__ inline long long quad_blocks(long long i_count, int ysplit, int k = 0) {
-  const unsigned quads = (unsigned)((i_count + kQuad - 1) / kQuad);
-  long long most = 0;
-  for (unsigned x = 0; x < (unsigned)kXcds; ++x) {
-    const long long wg = (long long)xcd_items(quads, (unsigned)ysplit, x, 0, (unsigned)ysplit, k);
-    most = wg > most ? wg : most;
-  }
-  return kXcds * most;
-}
-
 template <int T>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3)))
 pair_sym_quad_f32(SymArgs a) {
@@ -853,6 +631,11 @@ pair_sym_quad_f32(SymArgs a) {
   float* const lg = slab[2];
 
   // ---- my targets (as pair_sym_f32) ----------------------------------------------------------------------------------
+  // ("as pair_sym_f32" means the same lines, repeated: sharing them through device functions was tried and costs registers.
+  // The inner t loop alone -- pk_sub_sel to the bw[m] fma -- as a __forceinline__ template over the register arrays makes every
+  // T = 8 instantiation spill: 168 VGPRs and 120-256 bytes/lane of scratch against 133-165 VGPRs and none; the whole `for k`
+  // rotation loop 280-364 bytes/lane; this kernel from 152 VGPRs without scratch to 168 with 120-364 bytes/lane.  Plain
+  // `inline` behaves like __forceinline__.)
   f32x2 gp[H], au[T], aw[T];
   f32x2 xq[2][H], zq[2][H];
   {

@@ -219,7 +219,7 @@ def test_library_exports_the_c_abi_and_nothing_else():
 
 def test_every_non_template_kernel_header_belongs_to_one_unit():
     """A non-template __global__ function defined in a header that two units include would be defined twice.  Templates and
-    device helpers live in pair_kernels.hpp / pair_sym_kernels.hpp (includable anywhere, no plain kernel inside); each of the
+    device helpers live in pair_kernels.hpp / pair_sym_kernels.hpp / sym_rule.hpp (includable anywhere, no plain kernel inside); each of the
     other kernel headers is included by exactly one .hip file."""
     import glob
     csrc = os.path.join(ROOT, "ludvm_amd", "csrc")
@@ -230,7 +230,7 @@ def test_every_non_template_kernel_header_belongs_to_one_unit():
         users = sorted(u for u, text in units.items() if f'#include "{hdr}"' in text)
         assert users == [owner], (hdr, users)
         assert f'#include "{hdr}"' not in open(os.path.join(csrc, "ctx.hpp")).read()
-    for shared in ("pair_kernels.hpp", "pair_sym_kernels.hpp", "march_types.hpp"):
+    for shared in ("pair_kernels.hpp", "pair_sym_kernels.hpp", "sym_rule.hpp", "march_types.hpp"):
         text = open(os.path.join(csrc, shared)).read()
         # every kernel in a shared header is a template (its __global__ line is preceded by a template line)
         lines = text.splitlines()

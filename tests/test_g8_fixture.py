@@ -4,8 +4,7 @@ threshold.  A threshold that moves fails here: move the case pair with it and re
 The GPU tier runs the same cases through the production entry points (tests/test_gpu_g8.py)."""
 import os
 import re
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -17,6 +16,8 @@ from oracle import ludvm_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ludvm_amd", "csrc")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import sym_rule  # noqa: E402
 REGEN = "regenerate G8 with the case pair at the new value (oracle/g8_cases.py, python oracle/gen_golden.py g8)"
 
 
@@ -87,6 +88,8 @@ def test_g8_c_oracle_matches_the_reference(g8):
 
 
 def _library_constants():
+    """The symmetric rule's thresholds from the rule itself (tools/sym_rule.py), the direct kernel's plan constants from the source."""
+    rule = sym_rule.constants()
     launch = open(os.path.join(CSRC, "launch.hip")).read()
     ctx = open(os.path.join(CSRC, "ctx.hpp")).read()
 
@@ -95,49 +98,27 @@ def _library_constants():
         assert len(m) == 1, (pattern, m)
         return conv(m[0])
     return {
-        "kSymMinN": one(r"constexpr long long kSymMinN = (\d+);", launch),
-        "kSymT8MinN": one(r"constexpr long long kSymT8MinN = (\d+);", launch),
+        "kSymMinN": rule["kSymMinN"],
+        "kSymT8MinN": rule["kSymT8MinN"],
         "kPatch4MinTargets": 1 << one(r"constexpr long long kPatch4MinTargets = 1LL << (\d+);", launch),
         "tpl2_min_targets": one(r"p\.tpl = nt >= (\d+) \? 2 : 1;", launch),
         "kOrderMin": one(r"constexpr size_t kOrderMin = (\d+);", ctx),
         "kSmallSidePairsF64": one(r"constexpr double kSmallSidePairsF64 = ([0-9.]+);", ctx, float),
         "small_tile_max": one(r"long long small_tile_max = (\d+);", ctx),
-        "sym_quad_min_tiles": one(r"long long sym_quad_min_tiles = (\d+);", ctx),
+        "sym_quad_min_tiles": rule["kSymQuadMinTiles"],
         "kMaxExtentOverCore": one(r"constexpr double kMaxExtentOverCore = ([0-9.]+);", ctx, float),
         "kMaxExtentOverCoreCloud": one(r"constexpr double kMaxExtentOverCoreCloud = ([0-9.]+);", ctx, float),
     }
 
 
-def _first_quad_size(tmp_path, t8, min_tiles):
-    """The smallest vortex count whose symmetric launch takes the quad variant under the default rule: T = 8, at least
-    `min_tiles` 512-vortex tiles, and items of one wave (launch.hip, launch_sym_tiles), from the library's sym_geometry."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = tmp_path / "quad.hip"
-    src.write_text('#include <cstdio>\n#include "pair_sym_kernels.hpp"\nint main() {\n'
-                   f'  for (long long n = {t8}; n < 4000000; ++n) {{\n'
-                   '    const ludvm::SymGeom g = ludvm::sym_geometry(n, 8, 0, 0);\n'
-                   '    const bool one_wave_items = g.rsplit == 1 || (g.rsplit == 0 && g.rbulk == 1);\n'
-                   f'    if (g.ntiles >= 16 && one_wave_items && g.ntiles >= {min_tiles}) {{ std::printf("%lld\\n", n); return 0; }}\n'
-                   '  }\n  return 1;\n}\n')
-    exe = tmp_path / "quad"
-    p = subprocess.run([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", f"-I{CSRC}", "-o", str(exe), str(src)],
-                       capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, "no quad launch below 4e6 vortices"
-    return int(r.stdout.split()[0])
-
-
-def test_g8_pairs_straddle_the_librarys_thresholds(tmp_path):
+def test_g8_pairs_straddle_the_librarys_thresholds():
     """Each pair of G8 cases is (t - 1, t), t = the first size on the far side of the library's current threshold."""
     k = _library_constants()
     first = {
         "small_tile_max": k["small_tile_max"] + 1,           # launch.hip make_plan: ns <= small_tile_max -> 256-source tiles
         "kSymMinN": k["kSymMinN"],                           # use_symmetric: n >= kSymMinN
         "kSymT8MinN": k["kSymT8MinN"],                       # sym_tile_t: n >= kSymT8MinN -> T = 8
-        "sym_quad_min_tiles": _first_quad_size(tmp_path, k["kSymT8MinN"], k["sym_quad_min_tiles"]),
+        "sym_quad_min_tiles": sym_rule.rule(range(1, 4000000), first_quad=True)[0].n,    # the first size the rule itself marks quad
         "kOrderMin": k["kOrderMin"],                         # ludvm_induce_f64: min(ns, nt) < kOrderMin -> float64 / hi+lo
         "kSmallSidePairsF64": int(k["kSmallSidePairsF64"] // 512) + 1,     # ns * 512 <= 2^28 -> float64 (512 targets)
         "tpl2_min_targets": k["tpl2_min_targets"],           # make_plan: nt >= 131072 -> 2 targets per lane
@@ -179,3 +160,22 @@ def test_g8_grid_and_extent_cases_sit_on_their_sides():
             assert ratio > (1 + margin[reordered]) * bound, (c["name"], ratio, bound, REGEN)
         else:
             assert ratio < (1 - margin[reordered]) * bound, (c["name"], ratio, bound, REGEN)
+
+
+def test_the_rule_takes_each_g8_threshold_pair_to_its_two_routes():
+    """What the launch rule itself (ludvm_amd/csrc/sym_rule.hpp through tools/sym_rule.py) says at the pairs of self-interaction
+    cases: each side gets the route its case is in the table for -- direct | symmetric, 256- | 512-vortex tiles, plain | quad --
+    and the march turns symmetric at its own, lower size.  DESIGN 4.2's quad geometry at the headline size."""
+    sizes = [G8.BY_NAME[name]["ns"] for lo, hi, const in G8.PAIRS[1:4] for name in (lo, hi)]
+    assert sizes == [16383, 16384, 36863, 36864, 327168, 327169]
+    route = [(bool(r.symmetric), r.T, bool(r.quad), r.kernel) for r in sym_rule.rule(sizes)]
+    assert route[0][0] is False and route[0][3] is None                                  # the direct kernel
+    assert route[1] == route[2] == (True, 4, False, "pair_sym_f32<4, false, 4, true>")
+    assert route[3] == (True, 8, False, "pair_sym_f32<8, false, 4, true>")
+    assert route[4] == (True, 8, False, "pair_sym_f32<8, false, 0, true>")               # (mixed, the bulk by single waves)
+    assert route[5] == (True, 8, True, "pair_sym_quad_f32<8>")
+    below, above = sym_rule.rule([11263, 11264], march=True)
+    assert not below.symmetric and above.symmetric and (above.T, above.kernel) == (4, "pair_sym_f32<4, false, 4, true>")
+    assert not any(r.symmetric for r in sym_rule.rule([11263, 11264]))                   # ... outside the march: from kSymMinN
+    big, = sym_rule.rule([1000000])
+    assert big.quad and (big.quad_chunks, big.quad_long, big.quad_per, big.quad_pershort) == (119, 53, 16, 2)     # 53 + 66 = 119

@@ -42,7 +42,7 @@ def test_roofline_table_recomputes_from_profiles(rnd, t8_switch):
     # the direct kernel's distance from its 54 % ceiling is the held clock: >= 95 % of the issue model
     assert float(direct[7]) > 0.95
     # config 2: the rows ARE the run -- their kernels are the symmetric kernels of the full run's statistics file, their
-    # launches are that file's call counts, and the steps the library's rule (restated in tools/roofline_table.py) gives each
+    # launches are that file's call counts, and the steps the library's rule (tools/sym_rule.py, with the round's switch) gives each
     # variant add up to the run (round 6: a variant may serve more than one range of wake sizes -- the waves-per-item rule
     # follows the parity of the tile count -- so the rows name their ranges instead of assuming one each)
     import csv
@@ -64,7 +64,7 @@ def test_roofline_table_recomputes_from_profiles(rnd, t8_switch):
         assert 0.55 < frac(c) < 0.75, c                                      # mid sizes: between 0.58 and 0.71 credited
         total += calls
     assert total == 50000
-    # the T = 8 tile takes over at 36 864 vortices (launch.hip, kSymT8MinN; 34 816 through round 5), whatever the proxy once showed
+    # the T = 8 tile takes over at kSymT8MinN vortices (sym_rule.hpp; 34 816 through round 5), whatever the proxy once showed
     assert abs(int(re.search(r"wakes of (\d+)-", cfg2[2][0]).group(1)) - t8_switch) < 1500
     # ... and the four-waves-per-item kernel comes back below the switch (the tile count's parity): two ranges
     assert " and " in cfg2[0][0] and " and " in cfg2[2][0] and " and " not in cfg2[1][0]
@@ -128,43 +128,25 @@ def test_scaling_table_divides_by_the_same_work_figure():
     assert "config4_one_gpu.value" in two[0]["scaling_denominator"]
 
 
-def test_the_tables_rule_is_the_librarys_rule(tmp_path):
-    """DESIGN section 5's config-2 rows and profiles/r06_mid_size_variant_table.txt attribute steps / mark picks by a Python
-    restatement of the library's launch rule (tools/roofline_table.py::config2_rows, tools/r06_mid_size_sweep.py::rule_pick).
-    The rule itself is host-callable C++ (pair_sym_kernels.hpp: sym_geometry; launch.hip: kSymT8MinN): a small host program
-    built from the library's own header prints it for a ladder of wake sizes, and the restatements must agree everywhere."""
+def test_the_tables_rule_is_the_librarys_rule():
+    """DESIGN section 5's config-2 rows and profiles/r06_mid_size_variant_table.txt attribute steps / mark picks by the library's
+    launch rule, which is stated once (ludvm_amd/csrc/sym_rule.hpp) and asked through tools/sym_rule.py, which compiles that very
+    file: no restatement is left to compare, only the rule's own properties over a ladder of wake sizes."""
     import re
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    csrc = os.path.join(ROOT, "ludvm_amd", "csrc")
-    t8 = int(re.search(r"constexpr long long kSymT8MinN = (\d+);", open(os.path.join(csrc, "launch.hip")).read()).group(1))
-    src = tmp_path / "rule.hip"
-    src.write_text('#include <cstdio>\n#include "pair_sym_kernels.hpp"\nint main() {\n'
-                   f'  for (long long n = 11264; n <= 70000; n += 97) {{\n    const int T = n >= {t8} ? 8 : 4;\n'
-                   '    const ludvm::SymGeom g = ludvm::sym_geometry(n, T, 0, 0);\n'
-                   '    std::printf("%lld %d %d\\n", n, T, g.rsplit);\n  }\n  return 0;\n}\n')
-    exe = tmp_path / "rule"
-    p = subprocess.run([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", f"-I{csrc}", "-o", str(exe), str(src)],
-                       capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    lib = {int(a): (int(b), int(c)) for a, b, c in (l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True,
-                                                                                      timeout=60).stdout.splitlines())}
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import sym_rule
+    t8 = sym_rule.constants()["kSymT8MinN"]
+    lib = sym_rule.rule(range(11264, 70001, 97), march=True)
     assert len(lib) > 600
-    # restatement 1: the sweep's rule_pick (cut out of the tool: importing it would need an engine)
-    text = open(os.path.join(ROOT, "tools", "r06_mid_size_sweep.py")).read()
-    ns = {"os": os}
-    exec(text[text.index("K_TARGET_WAVES, K_MAX_SPLIT"):text.index("CANDS =")], ns)
-    assert ns["K_T8_MIN_N"] == t8
-    # restatement 2: roofline_table's variant(), same cut
-    text2 = open(os.path.join(ROOT, "tools", "roofline_table.py")).read()
-    body = text2[text2.index("    def variant(n):"):text2.index("    served = {}")]
-    ns2 = {"t8": t8}
-    exec("def make(t8):\n" + body + "    return variant\n", ns2)
-    variant = ns2["make"](t8)
-    for n, (T, rs) in lib.items():
+    for r in lib:
         # rsplit: 0 = mixed granularity (the size rule left room below four waves per item), 4 = four waves per item
-        assert rs in (0, 4), (n, rs)
-        assert ns["rule_pick"](n) == (T, "mixed" if rs == 0 else "x4"), n
-        assert variant(n) == f"pair_sym_f32<{T}, false, {rs}, true>", n
+        assert r.symmetric and not r.quad and r.rsplit in (0, 4), r
+        assert r.T == (8 if r.n >= t8 else 4), r            # T switches exactly at the constant
+        assert r.kernel == f"pair_sym_f32<{r.T}, false, {r.rsplit}, true>", r
+    # the dump is built from the header the library's units include, and they define none of its constants themselves
+    csrc = os.path.dirname(sym_rule.HEADER)
+    read = lambda name: open(os.path.join(csrc, name)).read()      # noqa: E731
+    assert os.path.samefile(csrc, os.path.join(ROOT, "ludvm_amd", "csrc")) and '#include "sym_rule.hpp"' in read("pair_sym_kernels.hpp")
+    assert '#include "pair_sym_kernels.hpp"' in read("ctx.hpp") and '#include "ctx.hpp"' in read("launch.hip")
+    assert not re.search(r"constexpr[^;=]*\b(kSym\w+|kXcds|kQuad\w*) =", read("launch.hip") + read("ctx.hpp"))
+    assert "sym_quad_min_tiles = kSymQuadMinTiles;" in read("ctx.hpp")

@@ -9,7 +9,7 @@ wake, fp32 on local origins) per candidate and size, back-to-back steps under su
     T8 x4      pair_sym_f32<8, false, 4>
     direct     pair_f32<.., LOCAL>         every ordered pair
     rule       what the library picks (T = 8 from 36 864 vortices -- 34 816 until this sweep; waves per item by size)  -- must equal the marked candidate
-The rule's pick is recomputed here from the constants of pair_sym_kernels.hpp (sym_geometry_t) and marked with *.
+The rule's pick is the library's own header's (tools/sym_rule.py; T8_MIN_N=n: with the T = 8 switch at n) and is marked with *.
     python tools/r06_mid_size_sweep.py [sizes in thousands ...]  > profiles/r06_mid_size_variant_table.txt"""
 import os
 import sys
@@ -21,27 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("LUDVM_HIP_LIB", os.path.join(ROOT, "ludvm_amd", "csrc", "libludvm_hip_exp.so"))
 from ludvm_amd import Engine  # noqa: E402
-
-K_TARGET_WAVES, K_MAX_SPLIT, K_MAX_RSPLIT, K_MIN_ITEMS, K_T8_MIN_N = 8 * 65536, 64, 4, 10500, int(os.environ.get('T8_MIN_N', '36864'))
-
-
-def rule_pick(n):
-    """(T, 'mixed' | 'x4' | 'x2' | 'x1') as sym_tile_t / sym_geometry_t choose for n vortices (tune_* = 0)."""
-    T = 8 if n >= K_T8_MIN_N else 4
-    W = 64 * T
-    nt = max(1, (n + W - 1) // W)
-    dmax = (nt - 1) // 2
-    dtot = dmax + (1 if (nt % 2 == 0 and nt > 1) else 0)
-    ys = K_MAX_SPLIT if nt <= K_TARGET_WAVES // K_MAX_SPLIT else (K_TARGET_WAVES + nt - 1) // nt
-    ys = max(1, min(ys, K_MAX_SPLIT, dtot))
-    if dtot > 0:
-        per0 = (dtot + ys - 1) // ys
-        ys = (dtot + per0 - 1) // per0
-    rs = 1
-    while rs < K_MAX_RSPLIT and nt * ys * rs < K_MIN_ITEMS:
-        rs *= 2
-    return T, ("mixed" if rs < K_MAX_RSPLIT else "x4")
-
+import sym_rule  # noqa: E402
 
 CANDS = [("T4 mixed", 4, -1), ("T4 x4", 4, 4), ("T8 mixed", 8, -1), ("T8 x4", 8, 4), ("direct", 0, 0), ("rule", 0, 0)]
 if os.environ.get("SWEEP_MORE"):            # two and one waves per item too (not among VERDICT r5 item 4's candidates)
@@ -83,9 +63,8 @@ print()
 print("microseconds per roll-up step (median of three 0.3 s blocks); * = the rule's pick, ! = a candidate more than 2 % faster than it")
 print(f"{'vortices':>9} | " + " | ".join(f"{name:>10}" for name, _, _ in CANDS) + " | rule = pick?  fastest")
 worst = 0.0
-for n in sizes:
-    T, how = rule_pick(n)
-    pick = f"T{T} {how}"
+for n, r in zip(sizes, sym_rule.rule(sizes, t8_switch=int(os.environ.get("T8_MIN_N", "0")))):
+    pick = f"T{r.T} {'mixed' if r.rsplit == 0 else f'x{r.rsplit}'}"
     tp = table[(n, pick)]
     cells = []
     for name, _, _ in CANDS:

@@ -12,6 +12,8 @@ import csv
 import os
 import sys
 
+import sym_rule
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PEAK = 157.3e12
 SIMDS = 256 * 4
@@ -34,7 +36,7 @@ ROWS = [
 ]
 
 
-T8_SWITCH = {"r05": 34816}
+T8_SWITCH = {"r05": 34816}      # rounds whose T = 8 switch was not today's
 
 
 def stats(prefix):
@@ -76,31 +78,17 @@ def config2_rows(rnd):
         t = (step - step_of[k]) / 250.0
         return every[k] + t * (every[k + 1] - every[k])
     st = stats(p)
-    # Which kernel served which step: the library's own rule (launch.hip: sym_tile_t; pair_sym_kernels.hpp: sym_geometry_t),
-    # restated here, applied to the wake size of every step.  Round 6: rounds 3-5 assumed that each variant serves ONE contiguous
+    # Which kernel served which step: the library's own rule (ludvm_amd/csrc/sym_rule.hpp through tools/sym_rule.py, with the
+    # round's T = 8 switch), applied to the wake size of every step.  Round 6: rounds 3-5 assumed that each variant serves ONE contiguous
     # range of steps; the waves-per-item rule follows the tile count's parity where the d-chunks stop dividing evenly, so
     # <4,.,4> comes back between ~32 900 and the T = 8 switch and <8,.,4> for the last ~900 steps -- the old attribution put
     # those launches' pairs into the wrong rows (the call counts below are checked against the statistics file instead).
-    t8 = T8_SWITCH.get(rnd, 36864)
-
-    def variant(n):
-        if n < 11264:
-            return "pair_f32<1, 256, false, 0, true>"
-        T = 8 if n >= t8 else 4
-        W = 64 * T
-        nt = max(1, (n + W - 1) // W)
-        dtot = (nt - 1) // 2 + (1 if (nt % 2 == 0 and nt > 1) else 0)
-        ys = max(1, min(64, dtot))
-        if dtot > 0:
-            per0 = (dtot + ys - 1) // ys
-            ys = (dtot + per0 - 1) // per0
-        rs = 1
-        while rs < 4 and nt * ys * rs < 10500:
-            rs *= 2
-        return f"pair_sym_f32<{T}, false, {0 if rs < 4 else 4}, true>"
+    sizes = [int(wake_at(s_)) for s_ in range(1, run["steps"] + 1)]
+    by_size = {r.n: r.kernel or "pair_f32<1, 256, false, 0, true>"            # (below the march's threshold: the direct kernel)
+               for r in sym_rule.rule(sorted(set(sizes)), march=True, t8_switch=T8_SWITCH.get(rnd))}
     served = {}
-    for s_ in range(1, run["steps"] + 1):
-        served.setdefault(variant(int(wake_at(s_))), []).append(s_)
+    for s_, n in enumerate(sizes, 1):
+        served.setdefault(by_size[n], []).append(s_)
     rows = []
     for short in ("pair_sym_f32<4, false, 4, true>", "pair_sym_f32<4, false, 0, true>", "pair_sym_f32<8, false, 4, true>",
                   "pair_sym_f32<8, false, 0, true>"):
