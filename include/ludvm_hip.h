@@ -443,6 +443,36 @@ int ludvm_ensemble_run(ludvm_ctx* ctx, size_t members, int npan, int ncoef, cons
                        size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
                        size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n);
 
+/* ---- velocity probes in an ensemble: one set of points, a time series per member ----------------------------------
+ *
+ * ludvm_ensemble_run_probed is ludvm_ensemble_run with the probes of ludvm_march_set_probes evaluated inside the one launch.
+ * The definition is the same (LUDVM.py:1095-1106 with xp, zp = the probe): for member m, step i >= 1 and probe p, the field
+ * of the member's wake before the Euler update of step i -- the vortices shed in step i at their placement included -- plus
+ * the bound vortices of step i; Vatistas core, no freestream term, float64.  Row 0 is the field of the member's free vortices.
+ *   probe_x, probe_z [nprobe]   the points, common to the batch; nprobe <= LUDVM_ENSEMBLE_MAX_PROBES (a quarter of the solo
+ *                               limit: a member's workgroup is meant to stay around a second)
+ *   shift_x                     NULL, or one x offset per kinematics row (shift_rows must equal kin_rows): in step i of member
+ *                               m probe k sits at (probe_x[k] + shift_x[kin_off + i], probe_z[k])
+ *   probe_u, probe_w (host)     [kin_rows][nprobe]: member m's time level i is row kin_off + i, row 0 included; rows of `kin`
+ *                               that no member owns are 0
+ * Every other argument, output, limit and guarantee is ludvm_ensemble_run's, and those outputs are bit-identical to a call
+ * without probes: the probe phase reads the member's wake and writes only the probe rows.  Each probe sum is formed in an
+ * order that depends on nprobe and on the member's own wake size only, so a member's probe bits do not depend on the batch
+ * either; a member differs from ludvm_march_run(LUDVM_PREC_F64) with the same probes by summation order only.  nprobe = 0 is
+ * ludvm_ensemble_run itself (the probe arguments are not looked at).  Nothing is kept on the context: there is no state to
+ * set, read back or forget.  Checked on the host before anything touches the device (LUDVM_E_ARG): nprobe over the limit,
+ * null arrays, shift_rows != kin_rows, a point or offset that is not finite, and 2 * 8 * kin_rows * nprobe bytes of probe
+ * rows over 1 GiB (the message gives the size: split the batch).  A sharded context answers LUDVM_E_STATE.
+ * The entry point is an addition to ABI 7 -- no existing signature or layout changes, LUDVM_ABI_VERSION and
+ * LUDVM_ENSEMBLE_DESC stay as they are: a caller that may meet an older library of ABI 7 detects it by its symbol. */
+#define LUDVM_ENSEMBLE_MAX_PROBES 1024
+int ludvm_ensemble_run_probed(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                              const double* tables, const double* kin, size_t kin_rows, const double* init,
+                              const double* free_xzg, size_t free_count, const long long* desc, const long long* snap_steps,
+                              size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
+                              long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
+                              const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w);
+
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 
 /* Grid targets generated on the device, x-major ravel like np.meshgrid(indexing='ij')

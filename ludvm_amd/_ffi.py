@@ -27,6 +27,8 @@ ENSEMBLE_MAX_WAKE = 8192
 ENSEMBLE_MAX_SNAPSHOTS = 1024
 ENSEMBLE_INIT_HEAD = 8
 ENSEMBLE_DESC = 6
+ENSEMBLE_MAX_PROBES = 1024     # LUDVM_ENSEMBLE_MAX_PROBES
+ENSEMBLE_PROBE_BYTES = 1 << 30  # most bytes of probe rows (2 * 8 * kinematics rows * probes) one ludvm_ensemble_run_probed call returns
 MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
 SYM_SCALE_BYTES = 32
 
@@ -88,6 +90,9 @@ SIGNATURES = {
     "ludvm_ensemble_run": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
                            POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
                            POINTER(c_longlong)],
+    "ludvm_ensemble_run_probed": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
+                                  POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
+                                  POINTER(c_longlong), _pd, _pd, c_size_t, _pd, c_size_t, _pd, _pd],
     "ludvm_flowfield_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
                             c_double, _pf, _pf],
     "ludvm_flowfield_vorticity_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
@@ -104,6 +109,9 @@ SIGNATURES = {
     "ludvm_kernel_timing": [c_void_p, c_int],
     "ludvm_kernel_time_ms": [c_void_p, c_int, POINTER(c_double), POINTER(c_longlong)],
 }
+
+# added to ABI 7 without a new version number: a library of ABI 7 built before them is detected by the missing symbol
+ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed",)
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 
@@ -174,6 +182,8 @@ def load(path=None):
     _pin_hip_runtime()
     lib = ctypes.CDLL(p)
     for name, argtypes in SIGNATURES.items():
+        if name in ADDED_IN_ABI_7 and not hasattr(lib, name):
+            continue                            # (the engine method that needs it says so)
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_char_p if name == "ludvm_last_error" else c_int

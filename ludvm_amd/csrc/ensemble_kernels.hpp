@@ -16,7 +16,14 @@
 //                      position a pair still has to read is ever overwritten
 //   4. placement       of the next step's TEV / candidate LEV by the threads that have just moved the newest vortices;
 //                      snapshot of the wake on the listed steps and after the last one
+// With velocity probes (ensemble_march<true>; the definition of march_probe_partial, reference LUDVM.py:1095-1106 with xp, zp
+// = the probe), between 2 and 3:
+//   2p. probes         wake (this step's shed vortices included, before the Euler update) + bound vortices -> the P probe
+//                      points of the sweep, shifted by the member's own offset of the step; row `step` of the member's probe
+//                      rows.  Row 0 -- the field of the free vortices -- is written before the first step.  The phase reads
+//                      the slab and writes nothing but the probe rows: ensemble_march<false> does not contain it.
 //
+
 // Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
 // walks the sources in index order; the fixed trees of block_sum_n; slices combined in slice order).  No atomics, nothing
 // is shared between workgroups, no workgroup waits for another: a member's bits do not depend on the batch, on its index
@@ -46,6 +53,11 @@ struct EnsembleMember {
   double* rows;                 // nt - 1 rows of kMarchRowHead + 2 ncoef + 2 npan doubles
   double* rec;                  // nsnap + 1 wake records of x[cap] | z[cap] | g[cap]: the snapshot steps, then the last step
   long long* rec_n;             // ... and their sizes (-1: the member has no such step)
+  // velocity probes (ensemble_march<true> only)
+  const double* px; const double* pz;   // the P probe points, common to the batch
+  long long P;
+  const double* shift;          // nt x offsets of the probes, one per time level of this member, or null
+  double* pu_rows; double* pw_rows;     // nt rows of P doubles each
 };
 
 // One Vatistas pair, pair_f64's arithmetic
@@ -108,6 +120,46 @@ __device__ __forceinline__ void ens_pair_sums(const double* __restrict__ xs, con
   }
 }
 
+// Probe rows of one time level: sources [0, ns) of the member's slab -> (u, w) at the P probes, each shifted by `shift` in
+// x.  Probes in tiles of kBlock.  A tile of more than kBlock / 2 probes: a probe per lane, the roll-up's prefetching walk.
+// A smaller one: up to kEnsSlicesMax lanes share a probe like the chord sums, every lane sums its slice of each source
+// tile in index order, and the slices are added in slice order through pu / pw.  All threads of the workgroup call this;
+// it ends in a barrier (the caller restages lx / lz / lg, and pu / pw are free again).
+__device__ __forceinline__ void ens_probe_row(const EnsembleMember& E, const double* __restrict__ xs, const double* __restrict__ zs,
+                                              const double* __restrict__ gs, long long ns, double shift, double vc4,
+                                              double* __restrict__ urow, double* __restrict__ wrow, double* lx, double* lz,
+                                              double* lg, double (*pu)[kBlock / 2], double (*pw)[kBlock / 2]) {
+  const int j = threadIdx.x;
+  const int P = (int)E.P;
+  for (int t0 = 0; t0 < P; t0 += kBlock) {
+    const int cnt = P - t0 < kBlock ? P - t0 : kBlock;
+    if (cnt > kBlock / 2) {
+      const bool mine = j < cnt;
+      const double xp = mine ? E.px[t0 + j] + shift : 0.0, zp = mine ? E.pz[t0 + j] : 0.0;
+      double au, aw;
+      ens_pair_sums<false>(xs, zs, gs, ns, xp, zp, vc4, mine, 0, 1, lx, lz, lg, au, aw);
+      if (mine) { urow[t0 + j] = au * kInv2PiD; wrow[t0 + j] = -aw * kInv2PiD; }
+    } else {
+      int slices = kBlock / cnt;
+      if (slices > kEnsSlicesMax) slices = kEnsSlicesMax;
+      const int slice = j / cnt, q = j - slice * cnt;
+      const bool mine = slice < slices;
+      const double xp = mine ? E.px[t0 + q] + shift : 0.0, zp = mine ? E.pz[t0 + q] : 0.0;
+      double au, aw;
+      ens_pair_sums<true>(xs, zs, gs, ns, xp, zp, vc4, mine, slice, slices, lx, lz, lg, au, aw);
+      double su = au * kInv2PiD, sw = -aw * kInv2PiD;
+      if (mine && slice > 0) { pu[slice - 1][q] = su; pw[slice - 1][q] = sw; }
+      __syncthreads();
+      if (slice == 0) {
+        for (int r = 1; r < slices; ++r) { su += pu[r - 1][q]; sw += pw[r - 1][q]; }
+        urow[t0 + q] = su; wrow[t0 + q] = sw;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+template <bool PROBES>
 __global__ void __launch_bounds__(kBlock)
 ensemble_march(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap) {
   __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
@@ -145,6 +197,8 @@ ensemble_march(const EnsembleMember* __restrict__ members, const long long* __re
   double lesp_crit = E.init[4], sum_tev = 0.0, sum_lev = 0.0;
   int snap_i = 0;
   __syncthreads();
+  if constexpr (PROBES)        // row 0: the field of the free vortices
+    ens_probe_row(E, xc, zc, g, E.nfree, E.shift ? E.shift[0] : 0.0, m.vc4, E.pu_rows, E.pw_rows, lx, lz, lg, pu, pw);
 
   for (long long step = 1; step < nt; ++step) {
     const double* kin = E.kin + (size_t)step * krow;
@@ -317,6 +371,11 @@ ensemble_march(const EnsembleMember* __restrict__ members, const long long* __re
     sum_tev += g_tev;
     sum_lev += g_lev;
     __syncthreads();
+
+    // ---- 2p. probes: the sources of the roll-up below, at the probe points (:1095-1106) -----------------------------------
+    if constexpr (PROBES)
+      ens_probe_row(E, xc, zc, g, n + npan, E.shift ? E.shift[step] : 0.0, m.vc4, E.pu_rows + (size_t)step * (size_t)E.P,
+                    E.pw_rows + (size_t)step * (size_t)E.P, lx, lz, lg, pu, pw);
 
     // ---- 3. roll-up (:1095-1127) and 4. placement of the coming step (:672-681, :788-800) -------------------------------
     const double* kin_next = step + 1 < nt ? kin + krow : nullptr;

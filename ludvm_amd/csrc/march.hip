@@ -462,14 +462,35 @@ int ludvm_ensemble_limits(ludvm_ctx* c, long long* limits3) {
   return LUDVM_OK;
 }
 
-int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
-                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
-                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
-                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n) {
+}  // extern "C"
+
+namespace {
+
+// ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at) and ludvm_ensemble_run_probed
+int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                      const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                      size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                      size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
+                      const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
+                      double* probe_w) {
   if (!c) return LUDVM_E_ARG;
   if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
     return fail(c, LUDVM_E_STATE, "ensemble: the context is sharded; members are independent -- split the list per device");
   if (members == 0) return LUDVM_OK;
+  if (nprobe) {
+    if (nprobe > LUDVM_ENSEMBLE_MAX_PROBES)
+      return fail(c, LUDVM_E_ARG, "ensemble: at most " + std::to_string(LUDVM_ENSEMBLE_MAX_PROBES) + " probes");
+    if (!probe_x || !probe_z || !probe_u || !probe_w) return fail(c, LUDVM_E_ARG, "null array");
+    if (shift_x && shift_rows != kin_rows) return fail(c, LUDVM_E_ARG, "ensemble: probe offsets must be one per kinematics row");
+    if (kin_rows > (((size_t)1 << 30) / 16) / nprobe)
+      return fail(c, LUDVM_E_ARG, "ensemble: " + std::to_string(16.0 * (double)kin_rows * (double)nprobe / (1 << 20)) + " MiB of probe rows (2 x 8 x " +
+                                      std::to_string(kin_rows) + " kinematics rows x " + std::to_string(nprobe) +
+                                      " probes) are over 1 GiB; split the batch");
+    for (size_t k = 0; k < nprobe; ++k)
+      if (!std::isfinite(probe_x[k]) || !std::isfinite(probe_z[k])) return fail(c, LUDVM_E_ARG, "ensemble: probe positions must be finite");
+    for (size_t k = 0; shift_x && k < shift_rows; ++k)
+      if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "ensemble: probe offsets must be finite");
+  }
   if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
     return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
@@ -513,11 +534,14 @@ int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const 
   const size_t in_tab = Arena::need(members * tab_doubles, 8), in_kin = Arena::need(kin_rows * krow, 8);
   const size_t in_init = Arena::need(members * init_doubles, 8), in_free = Arena::need(3 * free_count + 1, 8);
   const size_t in_snap = Arena::need(nsnap + 1, 8), in_mem = Arena::need(members, sizeof(EnsembleMember));
-  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem));
+  // (probes: points and offsets behind the inputs, rows behind the outputs)
+  const size_t in_probe = nprobe ? 2 * Arena::need(nprobe, 8) + (shift_x ? Arena::need(shift_rows, 8) : 0) : 0;
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe));
   CHK(ensure(c, c->ens_work, work_doubles * 8));
   const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
   const size_t out_n = Arena::need(members * nrec, 8);
-  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n));
+  const size_t out_probe = nprobe ? 2 * Arena::need(kin_rows * nprobe, 8) : 0;
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe));
   Arena in(c->ens_in.p), out(c->ens_out.p);
   double* d_tab = in.take<double>(members * tab_doubles);
   double* d_kin = in.take<double>(kin_rows * krow);
@@ -528,6 +552,14 @@ int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const 
   double* d_rows = out.take<double>(rows_count * row_doubles);
   double* d_wakes = out.take<double>(wake_doubles);
   long long* d_n = out.take<long long>(members * nrec);
+  double *d_px = nullptr, *d_pz = nullptr, *d_shift = nullptr, *d_pu = nullptr, *d_pw = nullptr;
+  if (nprobe) {
+    d_px = in.take<double>(nprobe);
+    d_pz = in.take<double>(nprobe);
+    if (shift_x) d_shift = in.take<double>(shift_rows);
+    d_pu = out.take<double>(kin_rows * nprobe);
+    d_pw = out.take<double>(kin_rows * nprobe);
+  }
 
   std::vector<EnsembleMember> hm(members);
   double* work = static_cast<double*>(c->ens_work.p);
@@ -556,6 +588,10 @@ int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const 
     e.rows = d_rows + (size_t)d[4] * row_doubles;
     e.rec = d_wakes + (size_t)d[5];
     e.rec_n = d_n + mi * nrec;
+    e.px = d_px; e.pz = d_pz; e.P = (long long)nprobe;
+    e.shift = d_shift ? d_shift + (size_t)d[1] : nullptr;
+    e.pu_rows = nprobe ? d_pu + (size_t)d[1] * nprobe : nullptr;
+    e.pw_rows = nprobe ? d_pw + (size_t)d[1] * nprobe : nullptr;
   }
   HIPCHK(c, hipMemcpyAsync(d_tab, tables, members * tab_doubles * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_kin, kin, kin_rows * krow * 8, hipMemcpyHostToDevice, c->stream));
@@ -563,15 +599,55 @@ int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const 
   if (free_count) HIPCHK(c, hipMemcpyAsync(d_free, free_xzg, 3 * free_count * 8, hipMemcpyHostToDevice, c->stream));
   if (nsnap) HIPCHK(c, hipMemcpyAsync(d_snap, snap_steps, nsnap * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_mem, hm.data(), members * sizeof(EnsembleMember), hipMemcpyHostToDevice, c->stream));
+  if (nprobe) {
+    HIPCHK(c, hipMemcpyAsync(d_px, probe_x, nprobe * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_pz, probe_z, nprobe * 8, hipMemcpyHostToDevice, c->stream));
+    if (shift_x) HIPCHK(c, hipMemcpyAsync(d_shift, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+    // (rows of `kin` that no member owns stay 0)
+    HIPCHK(c, hipMemsetAsync(d_pu, 0, kin_rows * nprobe * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_pw, 0, kin_rows * nprobe * 8, c->stream));
+  }
   // ONE launch: a workgroup per member, all of its time steps inside
-  hipLaunchKernelGGL(ensemble_march, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
-                     (const long long*)d_snap, (int)nsnap);
+  if (nprobe)
+    hipLaunchKernelGGL(ensemble_march<true>, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
+                       (const long long*)d_snap, (int)nsnap);
+  else
+    hipLaunchKernelGGL(ensemble_march<false>, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
+                       (const long long*)d_snap, (int)nsnap);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(rows, d_rows, rows_count * row_doubles * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(wakes, d_wakes, wake_doubles * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(wake_n, d_n, members * nrec * 8, hipMemcpyDeviceToHost, c->stream));
+  if (nprobe) {
+    HIPCHK(c, hipMemcpyAsync(probe_u, d_pu, kin_rows * nprobe * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(probe_w, d_pw, kin_rows * nprobe * 8, hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm lives on this frame)
   return LUDVM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ludvm_ensemble_run(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n) {
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, nullptr, nullptr, 0, nullptr, 0, nullptr,
+                           nullptr);
+}
+
+int ludvm_ensemble_run_probed(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                              const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                              size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                              size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
+                              const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
+                              double* probe_w) {
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
+                           shift_rows, probe_u, probe_w);
 }
 
 }  // extern "C"

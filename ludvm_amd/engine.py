@@ -427,6 +427,22 @@ class Engine:
         [members, 8 + ncoef]; free_xzg: 3 * (free vortices of all members) doubles; desc [members, 6] int64 = nt, kin_off,
         nfree, free_off, row_off, wake_off; snap_steps: increasing steps >= 1.
         -> (rows [sum(nt - 1), 12 + 2 ncoef + 2 npan], wakes (float64, flat), wake_n [members, len(snap_steps) + 1])."""
+        return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, None)
+
+    def ensemble_run_probed(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=(), *, probe_x, probe_z,
+                            shift_x=None):
+        """`ensemble_run` with velocity probes evaluated inside the launch (ludvm_ensemble_run_probed): probe_x, probe_z [P]
+        are common to the batch; shift_x: None, or one x offset per row of `kin` -- in step i of a member probe k sits at
+        (probe_x[k] + shift_x[kin_off + i], probe_z[k]).
+        -> (rows, wakes, wake_n, probe_u, probe_w) with probe_u / probe_w [rows of kin, P]: a member's time level i is row
+        kin_off + i (row 0: the field of its free vortices)."""
+        px, pz = _f64(probe_x), _f64(probe_z)
+        if len(px) != len(pz):
+            raise ValueError("ensemble_run_probed: probe_x and probe_z must have the same length")
+        sh = None if shift_x is None else _f64(shift_x)
+        return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, (px, pz, sh))
+
+    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes):
         npan, ncoef = int(npan), int(ncoef)
         desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
         members = desc.shape[0]
@@ -444,11 +460,19 @@ class Engine:
         wakes = np.empty(wake_doubles)
         wake_n = np.empty([members, nrec], dtype=np.int64)
         pll = POINTER(c_longlong)
-        self._check(self._lib.ludvm_ensemble_run(
-            self._ctx, members, npan, ncoef, _pd(sc), len(sc), _pd(tb), _pd(kin), kin.shape[0], _pd(ini), _pd(fr), len(fr) // 3,
-            desc.ctypes.data_as(pll), snaps.ctypes.data_as(pll), len(snaps), _pd(rows), rows_count, _pd(wakes), wake_doubles,
-            wake_n.ctypes.data_as(pll)))
-        return rows, wakes, wake_n
+        args = (self._ctx, members, npan, ncoef, _pd(sc), len(sc), _pd(tb), _pd(kin), kin.shape[0], _pd(ini), _pd(fr), len(fr) // 3,
+                desc.ctypes.data_as(pll), snaps.ctypes.data_as(pll), len(snaps), _pd(rows), rows_count, _pd(wakes), wake_doubles,
+                wake_n.ctypes.data_as(pll))
+        if probes is None:
+            self._check(self._lib.ludvm_ensemble_run(*args))
+            return rows, wakes, wake_n
+        px, pz, sh = probes
+        if not hasattr(self._lib, "ludvm_ensemble_run_probed"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_ensemble_run_probed")
+        pu, pw = np.empty([kin.shape[0], len(px)]), np.empty([kin.shape[0], len(px)])
+        self._check(self._lib.ludvm_ensemble_run_probed(*args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh),
+                                                        _pd(pu), _pd(pw)))
+        return rows, wakes, wake_n, pu, pw
 
     # -- flow field ------------------------------------------------------------------------------
     def flowfield(self, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core):

@@ -1,4 +1,5 @@
-"""`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run).
+"""`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run; with velocity probes
+Engine.ensemble_run_probed / ludvm_ensemble_run_probed).
 
 A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
 'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
@@ -28,7 +29,6 @@ _REFUSED = {
     "devices": (None, "a sweep runs on one GPU (members are independent: split the list per device)"),
     "march": (True, "the members of a sweep are marched on the device"),
     "run": (True, "the members of a sweep are run"),
-    "probes": (None, "a sweep has no velocity probes (a member can be run on its own: LUDVM(..., probes=...))"),
 }
 
 
@@ -47,7 +47,7 @@ class _RecordedWakes:
 def _check_case(idx, kw, first):
     """Everything that can be refused from the keywords alone (no device, no engine call)."""
     who = f"sweep: member {idx}: "
-    for key in ("engine", "device", "snapshot_steps", "verbose"):
+    for key in ("engine", "device", "snapshot_steps", "verbose", "probes", "probe_frame"):
         if key in kw:
             raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
     for key, (fine, why) in _REFUSED.items():
@@ -77,7 +77,25 @@ def _check_case(idx, kw, first):
     return npoints, ncoef
 
 
-def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls=LUDVM, **common):
+def _check_sweep_probes(probes, probe_frame, merged):
+    """The sweep's probe points [2, P] (None: no probes), refused from the keywords alone like a member's."""
+    if probes is None:
+        if probe_frame not in ("lab", "tunnel"):
+            raise ValueError("probe_frame must be 'lab' or 'tunnel'")
+        return None
+    xz = LUDVM._check_probes(probes, probe_frame)
+    if xz.shape[1] > _ffi.ENSEMBLE_MAX_PROBES:
+        raise ValueError(f"sweep: probes: at most {_ffi.ENSEMBLE_MAX_PROBES} points in a sweep (got {xz.shape[1]}); a member can "
+                         "be run on its own with up to 4096: LUDVM(..., probes=...)")
+    rows = sum(len(np.arange(kw.get("t0", 0), kw.get("tf", 12) + kw.get("dt", 1.5e-2), kw.get("dt", 1.5e-2))) for kw in merged)
+    size = 2 * 8 * rows * xz.shape[1]
+    if size > _ffi.ENSEMBLE_PROBE_BYTES:
+        raise ValueError(f"sweep: probes: {rows} time levels x {xz.shape[1]} points are {size} bytes ({size / 2**30:.2f} GiB) of "
+                         f"probe rows, over the {_ffi.ENSEMBLE_PROBE_BYTES >> 30} GiB one launch returns: split the case list")
+    return xz
+
+
+def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", verbose=False, cls=LUDVM, **common):
     """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
     return the list of LUDVM objects, in order.  Each carries what a solo
     `LUDVM(**kw, precision='f64', history='sparse', snapshot_steps=snapshot_steps)` run carries: Cl, Cd, Cm, Cn, Cs, Ct, Fn, Fs, L,
@@ -85,12 +103,21 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls
     SparseHistory with rows at snapshot_steps and the last step -- `flowfield` works on a member for any stored step.  A member
     differs from its solo run by summation order only; its bits do not depend on the other members or on its place in the list.
 
+    probes: None, or points [2, P] (x row, z row; 1 <= P <= 1024) common to the sweep, like LUDVM(..., probes=...): every member
+    also carries `probe_u`, `probe_w` float64 [nt, P] -- the field that convects its wake in each step, evaluated at the points
+    inside the one launch (row 0: the field of its free vortices) -- with `probe_xz`, `probe_frame` and `probe_positions(step)`.
+    probe_frame='tunnel' measures x from each member's own pivot (x + xpiv[step]: xpiv depends on the member's Uinf and dt).
+    Everything else a member returns is bit-identical to the sweep without probes.
+
     Npoints and Ncoeffs are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
-    history='full', checkpoint_*, distributed, devices, probes, march=False, run=False, an engine without ensemble_run.
+    history='full', checkpoint_*, distributed, devices, march=False, run=False, an engine without ensemble_run; `probes` or
+    `probe_frame` inside a member's dict (they belong to the sweep), more than 1024 probes, points that are not finite, a
+    probe_frame other than 'lab' / 'tunnel', an engine without ensemble_run_probed, and probe rows (16 bytes x all members' time
+    levels x P) over 1 GiB: split the case list.
 
-    Out of scope: fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe sets, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     cases = list(cases)
     if not cases:
@@ -102,11 +129,14 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls
         dims = _check_case(idx, kw, first)
         first = first or dims
         merged.append(kw)
+    probe_xz = _check_sweep_probes(probes, probe_frame, merged)
     if engine is None:
         from .engine import Engine
         engine = Engine(device)
     if not hasattr(engine, "ensemble_run"):
         raise ValueError("sweep: this engine has no ensemble_run")
+    if probe_xz is not None and not hasattr(engine, "ensemble_run_probed"):
+        raise ValueError("sweep: probes: this engine has no ensemble_run_probed")
     snaps = sorted({int(s) for s in snapshot_steps})
     dev_snaps = [s for s in snaps if s >= 1]
     if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
@@ -114,7 +144,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls
 
     # host: geometry, kinematics and tables of every member, packed
     sims, loops = [], []
-    sc, tb, kn, ini, fr = [], [], [], [], []
+    sc, tb, kn, ini, fr, shift = [], [], [], [], [], []
     desc = np.zeros([len(merged), _ffi.ENSEMBLE_DESC], dtype=np.int64)
     kin_off = free_off = row_off = wake_off = 0
     nrec = len(dev_snaps) + 1
@@ -135,6 +165,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls
         kn.append(kin)
         ini.append(np.concatenate([[tev_xy[0], lev_xy[0], tev_xy[1], lev_xy[1], sim.LESPcrit, 0.0, 0.0, 0.0], sim.fourier[0, 0, :]]))
         fr.append(np.concatenate([free0[0], free0[1], np.asarray(sim.circulation_freevort, dtype=float).reshape(-1)]))
+        if probe_xz is not None:
+            sim.probe_xz, sim.probe_frame = probe_xz.copy(), probe_frame
+            shift.append(np.asarray(sim.xpiv, dtype=float))
         nt, nf = sim.nt, S.nf
         desc[idx] = [nt, kin_off, nf, free_off, row_off, wake_off]
         kin_off, free_off, row_off = kin_off + nt, free_off + nf, row_off + nt - 1
@@ -144,12 +177,18 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), verbose=False, cls
     npan, ncoef = sims[0].Npoints - 1, sims[0].Ncoeffs
 
     # device: one launch
-    rows, wakes, wake_n = engine.ensemble_run(npan, ncoef, np.stack(sc), np.stack(tb), np.concatenate(kn), np.stack(ini),
-                                              np.concatenate(fr), desc, dev_snaps)
+    packed = (npan, ncoef, np.stack(sc), np.stack(tb), np.concatenate(kn), np.stack(ini), np.concatenate(fr), desc, dev_snaps)
+    if probe_xz is None:
+        rows, wakes, wake_n = engine.ensemble_run(*packed)
+    else:
+        rows, wakes, wake_n, pu, pw = engine.ensemble_run_probed(
+            *packed, probe_x=probe_xz[0], probe_z=probe_xz[1], shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
 
     # host: every member's rows into its result arrays, by the routine that stores a solo march
     for idx, (sim, S) in enumerate(zip(sims, loops)):
-        nt, _, nf, _, r0, w0 = (int(v) for v in desc[idx])
+        nt, k0, nf, _, r0, w0 = (int(v) for v in desc[idx])
+        if probe_xz is not None:
+            sim.probe_u, sim.probe_w = pu[k0:k0 + nt].copy(), pw[k0:k0 + nt].copy()
         cap = nf + 2 * (nt - 1)
         R = rows[r0:r0 + nt - 1]
         hist = _RecordedWakes()

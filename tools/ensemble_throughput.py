@@ -6,7 +6,15 @@ repeated): wall time of `sweep` split into host packing / device call (host cloc
 uploads, ONE kernel, downloads) / host unpacking; member-steps and pairs per second of the device call; and B x the solo
 `time_loop` time (march, float64, sparse history; geometry and kinematics excluded) measured in the same command, the two
 alternated.  Every shape is warmed up first; a small B is repeated inside a timed window until the window is about a second;
-min and median over the repetitions.  The profiler is off (kernel time: tools/profile_cmd.sh on this script with --sizes 256)."""
+min and median over the repetitions.  The profiler is off (kernel time: tools/profile_cmd.sh on this script with --sizes 256).
+
+    python tools/ensemble_throughput.py --probes-leg [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_probes_cost.txt
+What velocity probes in a sweep cost: the device call of 256 copies of config 1, packed once, without probes on
+this build and -- with --parent-lib, a build of the commit before the probes (tools/build_variant.sh) -- on that one, the
+two alternated in one process; then with a rake of P = 64 and of P = 1024 points in the tunnel frame (P = 1024: 128 copies,
+and 128 copies without probes beside them -- the probe rows of 256 would be over the 1 GiB one call returns).  Kernel time is
+not in this output: rocprofv3 --kernel-trace --stats on this command with --reps 2 --window 0.1 names the two
+instantiations (and the parent's kernel) apart."""
 import argparse
 import os
 import sys
@@ -22,6 +30,8 @@ ap.add_argument("--sizes", type=int, nargs="*", default=[1, 16, 64, 256, 1024, 4
 ap.add_argument("--mixed", type=int, default=1024, help="members of the mixed sweep (0: skip)")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--window", type=float, default=1.0, help="seconds a timed window should last")
+ap.add_argument("--probes-leg", action="store_true", help="the cost of probes in a sweep instead of the size ladder")
+ap.add_argument("--parent-lib", default="", help="probes leg: a build of the commit before the probes, timed beside this one")
 a = ap.parse_args()
 
 from ludvm_amd import LUDVM, Engine, sweep  # noqa: E402
@@ -103,6 +113,92 @@ def measure(label, cases, solo_cases):
           f"whole sweep {solo.min() / wall.min():.1f}x", flush=True)
 
 
+def probes_leg():
+    """Device call only: the members are packed once (what `sweep` hands the engine is kept) and the call is repeated."""
+    import torch
+    kept = {}
+    plain_call = inner
+
+    def keep(*args, **kw):
+        kept[len(args[7])] = args
+        return plain_call(*args, **kw)
+    eng.ensemble_run = keep
+    sims = {B: sweep([dict(CONFIG1)] * B, engine=eng) for B in (256, 128)}
+    del eng.ensemble_run
+    engines = {"this build": eng}
+    if a.parent_lib:
+        engines["parent build"] = Engine(0, lib_path=os.path.abspath(a.parent_lib))
+
+    def variant(which, B, P):
+        e, packed = engines[which], kept[B]
+        if P == 0:
+            return lambda: e.ensemble_run(*packed)
+        # a rake behind the foil in the frame of the pivot, P points over z in [-2, 2]
+        px, pz = np.full(P, 2.0), np.linspace(-2.0, 2.0, P)
+        shift = np.concatenate([s.xpiv for s in sims[B]])
+        return lambda: e.ensemble_run_probed(*packed, probe_x=px, probe_z=pz, shift_x=shift)
+    order = ([("parent build", 256, 0)] if a.parent_lib else []) + [("this build", 256, 0), ("this build", 256, 64),
+                                                                    ("this build", 128, 0), ("this build", 128, 1024)]
+    calls = {v: variant(*v) for v in order}
+    reps_in = {}
+    for v, f in calls.items():                        # warm-up of every shape (buffers grow here)
+        f()
+        t0 = time.perf_counter()
+        f()
+        reps_in[v] = max(1, int(a.window / (time.perf_counter() - t0)))
+    T = {v: [] for v in order}
+    for _ in range(a.reps):                           # the variants alternated
+        for v, f in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps_in[v]):
+                f()
+            T[v].append((time.perf_counter() - t0) / reps_in[v] * 1e3)
+    print("# probes leg: device call (host clock around the synchronous entry point: uploads, ONE kernel, downloads) of B copies\n"
+          "# of config 1 packed once; ms per call, min / median / max over the windows and the build's own spread (max - min) / min")
+    base = {}
+    for v in order:
+        which, B, P = v
+        t = np.array(T[v])
+        s1 = sims[B][0]
+        steps = B * (s1.nt - 1)
+        line = (f"{which:<13} B {B:4d}  P {P:5d}  windows of {reps_in[v]:3d}  device call {t.min():9.3f} / {np.median(t):9.3f} / "
+                f"{t.max():9.3f}  spread {(t.max() - t.min()) / t.min() * 100:5.2f} %")
+        if P == 0:
+            base[(which, B)] = t
+        else:
+            # sources a probe sees in step s: the wake after the solve + the bound vortices
+            shed = (s1.LEV_shed[1:] != -1).astype(np.int64)
+            nsrc = s1.n_freevort + np.arange(1, s1.nt) + np.cumsum(shed) + s1.Npoints - 1
+            pairs = B * P * int(nsrc.sum() + s1.n_freevort)
+            added = np.median(t) - np.median(base[(which, B)])
+            line += (f"\n{'':13} added {added:9.3f} ms per call = {added / (s1.nt - 1) * 1e3:8.3f} us per step (of every member, side by "
+                     f"side); {pairs:.3e} probe pairs, {pairs / (added * 1e-3):.3e} pairs/s of the added time; roll-up pairs of the "
+                     f"call {B * pairs_of(s1):.3e}: P / mean wake size = {P / (nsrc.mean() - s1.Npoints + 1):.2f}")
+            # the return copy alone: two arrays of [rows of kin, P] doubles, device -> pageable host memory
+            n = B * s1.nt * P
+            d = torch.empty(n, dtype=torch.float64, device="cuda")
+            h = [np.empty(n), np.empty(n)]
+            cp = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(2):
+                    torch.from_numpy(h[k]).copy_(d)
+                torch.cuda.synchronize()
+                cp.append((time.perf_counter() - t0) * 1e3)
+            line += f"\n{'':13} return copy of the probe rows alone ({2 * n * 8 / 2**20:.1f} MiB, device -> pageable host): {min(cp[1:]):9.3f} ms"
+        print(line, flush=True)
+    if a.parent_lib:
+        p, n = base[("parent build", 256)], base[("this build", 256)]
+        print(f"unprobed device call, this build against the parent build: median {np.median(n) / np.median(p):.4f} x; the parent's own windows "
+              f"span {p.min():.3f} .. {p.max():.3f} ms, this build's {n.min():.3f} .. {n.max():.3f} ms: "
+              f"{'inside' if p.min() <= np.median(n) <= p.max() else 'OUTSIDE'} the parent's run-to-run spread")
+
+
+if a.probes_leg:
+    eng.ensemble_run = inner
+    probes_leg()
+    sys.exit(0)
 for B in a.sizes:
     measure(f"config 1 x {B}", [dict(CONFIG1)] * B, [dict(CONFIG1)])
 if a.mixed:

@@ -6,7 +6,11 @@ prints one JSON line: sha256 of the (u, w) bits of self-interaction calls at siz
     python tools/result_hash.py --timeloop [--ludvm-module ludvm_amd._ludvm_before]
 fingerprints whole runs of the class instead (loads, circulations, LEV shedding, the final wake): the README case marched and
 per step in f64 and f32, a Ramesh run, a run with a free-vortex cloud, and config 2's first 6000 steps -- to A/B two versions
-of ludvm_amd/ludvm.py (a refactoring must not move a bit)."""
+of ludvm_amd/ludvm.py (a refactoring must not move a bit).
+    python tools/result_hash.py --ensemble [--lib path/to/libludvm_hip.so]
+fingerprints a sweep WITHOUT probes -- the 12-member grid of tests/test_gpu_ensemble.py, snapshot steps 1, 2, 10, 50: every
+member's loads, circulations, Fourier coefficients, LEV shedding and recorded wakes -- to A/B ensemble_march<false> against
+the kernel of the commit before the probes (profiles/ensemble_probes_result_hash.json)."""
 import argparse
 import hashlib
 import json
@@ -21,6 +25,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--lib", default="")
 ap.add_argument("--sizes", type=int, nargs="*", default=[20000, 40000, 70000, 200000, 400000, 600001, 1000000])
 ap.add_argument("--timeloop", action="store_true")
+ap.add_argument("--ensemble", action="store_true")
 ap.add_argument("--ludvm-module", default="ludvm_amd.ludvm")
 a = ap.parse_args()
 from ludvm_amd import _ffi  # noqa: E402
@@ -30,6 +35,31 @@ import torch  # noqa: E402
 from ludvm_amd import Engine  # noqa: E402
 
 eng = Engine(0)
+if a.ensemble:
+    import warnings
+    from ludvm_amd import sweep
+    common = dict(t0=0, tf=10, dt=5e-2, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012")
+    cases = [dict(LESPcrit=l, alpha_max=am) for l in (0.1, 0.2, 0.3, 10) for am in (10, 20)]
+    cases += [dict(dt=2.5e-2), dict(k=0.4 * np.pi), dict(Naca="2412"), dict(method="Ramesh")]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        sims = sweep(cases, engine=eng, snapshot_steps=(1, 2, 10, 50), **common)
+    out = {"lib": os.path.relpath(_ffi.LIB_PATH, ROOT), "members": len(sims)}
+    total = hashlib.sha256()
+    for m, sim in enumerate(sims):
+        h = hashlib.sha256()
+        C = sim.circulation
+        parts = [sim.Cl, sim.Cd, sim.Cm, sim.Fn, sim.Fs, sim.M, sim.LESP, sim.LESP_prev, sim.LEV_shed, sim.fourier, C["TEV"], C["LEV"],
+                 C["bound"], C["airfoil"], C["gamma_airfoil"]]
+        for key in ("TEV", "LEV", "FREE"):
+            parts += [sim.path[key][s] for s in sim.path[key].steps()]
+        for v in parts:
+            h.update(np.ascontiguousarray(v, dtype=np.float64).tobytes())
+        out[f"member_{m}"] = h.hexdigest()[:16]
+        total.update(h.digest())
+    out["all"] = total.hexdigest()[:16]
+    print(json.dumps(out))
+    sys.exit(0)
 if a.timeloop:
     import importlib
     LUDVM = importlib.import_module(a.ludvm_module).LUDVM
