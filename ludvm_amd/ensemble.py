@@ -60,8 +60,10 @@ def _check_case(idx, kw, first):
     if kw.get("method", "Faure") not in ("Faure", "Ramesh"):
         raise ValueError(who + "method must be 'Faure' or 'Ramesh'")
     npoints, ncoef = int(kw.get("Npoints", 80)), int(kw.get("Ncoeffs", 30))
-    if not (1 <= npoints - 1 <= 256 and 4 <= ncoef <= 64):
-        raise ValueError(who + "1 <= Npoints - 1 <= 256 and 4 <= Ncoeffs <= 64")
+    if npoints < 3:
+        raise ValueError(who + f"Npoints={npoints}: a section has at least 3 points (2 panels)")
+    if not (npoints - 1 <= 256 and 4 <= ncoef <= 64):
+        raise ValueError(who + f"Npoints={npoints}, Ncoeffs={ncoef}: a sweep takes 3 <= Npoints <= 257 and 4 <= Ncoeffs <= 64")
     if first is not None and (npoints, ncoef) != first:
         raise ValueError(who + f"Npoints / Ncoeffs = {npoints} / {ncoef} differ from member 0's {first[0]} / {first[1]}: "
                          "they are common to a sweep")
@@ -109,8 +111,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     probe_frame='tunnel' measures x from each member's own pivot (x + xpiv[step]: xpiv depends on the member's Uinf and dt).
     Everything else a member returns is bit-identical to the sweep without probes.
 
-    Npoints and Ncoeffs are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
-    kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs,
+    Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
+    kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
     history='full', checkpoint_*, distributed, devices, march=False, run=False, an engine without ensemble_run; `probes` or
     `probe_frame` inside a member's dict (they belong to the sweep), more than 1024 probes, points that are not finite, a

@@ -166,6 +166,11 @@ class LUDVM:
                 raise ValueError("probes run on one GPU: not with `distributed`")
         elif probe_frame not in ('lab', 'tunnel'):
             raise ValueError("probe_frame must be 'lab' or 'tunnel'")
+        # the smallest section the method runs: two panels; the loads read A0 .. A3 (LUDVM.py:1035-1090)
+        if Npoints < 3:
+            raise ValueError(f"Npoints={Npoints}: a section has at least 3 points (2 panels)")
+        if Ncoeffs < 4:
+            raise ValueError(f"Ncoeffs={Ncoeffs}: at least 4 Fourier coefficients (the loads use A0 .. A3)")
         if devices is not None:             # (one device: an ordinary single-GPU run on it)
             from .multi import normalise_devices
             device = normalise_devices(devices)[0]

@@ -23,7 +23,11 @@ Fixture groups:
                          tile sizes, targets per lane, grid patches, float64, hi+lo, Morton order).  Only outputs are
                          stored: the inputs regenerate from the case table (its digest is kept per case).
                              python oracle/gen_golden.py g8    # this group alone
-G2-G5 run the unmodified reference class with oracle/airfoils_standin on sys.path (zero camber,
+  G9 edge runs        -- the unmodified reference class run on the cases of oracle/g9_cases.py: panel counts on both sides of
+                         every edge of the sweep's and the march's chord-sum lane arithmetic, 4 .. 64 Fourier coefficients,
+                         free-vortex counts around the source tiles, and a wake that fills a sweep member's slab exactly.
+                             python oracle/gen_golden.py g9    # this group alone
+G2-G5 and G9 run the unmodified reference class with oracle/airfoils_standin on sys.path (zero camber,
 valid for the symmetric NACA0012 all BASELINE configs use).
 """
 import os
@@ -285,7 +289,31 @@ def g8_fp32_routes():
     print("G8:", len(G8.CASES), "cases,", os.path.getsize(path), "bytes")
 
 
+def g9_edge_runs():
+    """The G9 cases (oracle/g9_cases.py): loads, LESP, circulations and one set of wake rows per case and method."""
+    import time
+    if ROOT not in sys.path:
+        sys.path.append(ROOT)
+    from oracle import g9_cases as G9
+    t0 = time.time()
+    flat = {}
+    for c in G9.CASES:
+        for method in c["methods"]:
+            if not G9.in_fixture(c, method):
+                continue
+            sim = run_reference(G9.kwargs(c, method))
+            for k, v in G9.pack(sim, c).items():
+                flat[f"{G9.key(c, method)}/{k}"] = v
+            print(f"G9 {G9.key(c, method)}: nt {sim.nt} itev {sim.itev} ilev {sim.ilev}  ({time.time() - t0:.0f} s)", flush=True)
+    path = os.path.join(OUT, "g9_edge_runs.npz")
+    np.savez_compressed(path, **flat)
+    print("G9:", len(G9.CASES), "cases,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "g9":
+        g9_edge_runs()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "g7":
         g7_config2_regime()
         sys.exit(0)
@@ -298,5 +326,6 @@ if __name__ == "__main__":
     g6_generators()
     g7_config2_regime()
     g8_fp32_routes()
+    g9_edge_runs()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("total fixture bytes:", tot)

@@ -218,6 +218,21 @@ def test_sweep_refusals_make_no_engine_call(cases, common, word):
     assert eng.ncalls == []
 
 
+@pytest.mark.parametrize("kw,word", [(dict(Npoints=2), "Npoints=2"), (dict(Npoints=1), "Npoints=1"), (dict(Npoints=258), "Npoints=258"),
+                                     (dict(Ncoeffs=3), "Ncoeffs=3"), (dict(Ncoeffs=65), "Ncoeffs=65")])
+def test_sweep_refuses_sections_and_coefficient_counts_it_cannot_run_by_name(kw, word):
+    """Npoints = 2 (one panel) used to pass the keyword check and fail in the constructor with a bare IndexError; the smallest
+    and largest shapes a sweep takes pass it (Npoints = 3 / 257, Ncoeffs = 4 / 64)."""
+    from ludvm_amd import sweep
+    from ludvm_amd.ensemble import _check_case
+    eng = Counting()
+    with pytest.raises(ValueError, match="member 1.*" + word):
+        sweep([dict(tf=1, **{k: 30 if k == "Ncoeffs" else 81 for k in kw}), dict(tf=1, **kw)], engine=eng)
+    assert eng.ncalls == []
+    assert _check_case(0, dict(CONFIG1, tf=1, Npoints=3, Ncoeffs=4), None) == (3, 4)
+    assert _check_case(0, dict(CONFIG1, tf=1, Npoints=257, Ncoeffs=64), None) == (257, 64)
+
+
 def test_sweep_refuses_an_engine_without_ensemble_run_and_returns_nothing_for_no_cases():
     from ludvm_amd import LUDVM, sweep
     eng = Counting(with_ensemble=False)

@@ -138,6 +138,18 @@ def test_constructor_validation():
         LUDVM(**dict(CONFIG1, method="Newton", tf=0.2), engine=FakeEngine(), verbose=False)
 
 
+def test_constructor_refuses_one_panel_and_fewer_than_four_coefficients_by_name():
+    """Npoints = 2 used to end in a bare IndexError (like the reference), Ncoeffs = 3 in "not enough values to unpack" inside
+    the time loop; both are refused before any engine call, and the smallest shape that runs, Npoints = 3 with Ncoeffs = 4, runs."""
+    for kw, word in ((dict(Npoints=2), "Npoints=2"), (dict(Npoints=0), "Npoints=0"), (dict(Ncoeffs=3), "Ncoeffs=3")):
+        eng = FakeEngine()
+        with pytest.raises(ValueError, match=word):
+            LUDVM(**dict(CONFIG1, tf=0.2, **kw), engine=eng, verbose=False)
+        assert not any(eng.calls.values())
+    s = LUDVM(**dict(CONFIG1, tf=0.2, Npoints=3, Ncoeffs=4), engine=FakeEngine(), verbose=False)
+    assert s.fourier.shape == (5, 2, 4) and np.isfinite(s.Cl).all() and np.abs(s.Cl[1:]).max() > 0
+
+
 @pytest.mark.parametrize("history", ["full", "sparse"])
 def test_checkpoint_resume_is_bitwise_with_a_deterministic_engine(tmp_path, sim1, history):
     ck = str(tmp_path / "run.npz")
