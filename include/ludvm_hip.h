@@ -392,6 +392,47 @@ int ludvm_march_set_probes(ludvm_ctx* ctx, const double* x, const double* z, siz
                            size_t shift_rows);
 int ludvm_march_read_probes(ludvm_ctx* ctx, double* u, double* w, size_t rows);
 
+/* ---- passive tracers: particles advected inside the march (an addition to ABI 7: detect it by symbol) ----------
+ *
+ * A tracer is a probe that moves with what it measures.  Tracer m has a seed (xs, zs) and a release step r_m >= 1; with
+ * shift[i] the frame offset of step i (0 without shift_x):
+ *   step i <  r_m: held -- its position of step i is (xs + shift[i], zs), and it takes part in no pair sum;
+ *   step i >= r_m: start = (xs + shift[i], zs) if i == r_m, otherwise its position after step i - 1;
+ *                  its position after step i is  start + dt * (u, w)_i(start),
+ * (u, w)_i being EXACTLY the probes' field above: the wake before the Euler update of step i with the vortices shed in step
+ * i at their placement, plus the bound vortices of step i; Vatistas core, no freestream term, float64 whatever the roll-up's
+ * precision.  With r_m = 1 and no shift this is, to rounding, the trajectory the reference gives a free vortex of zero
+ * circulation seeded at the same point (path['FREE'], convected by LUDVM.py:1120-1127) -- without making the particle a
+ * source of the roll-up, without growing the wake, and with release during the run.  Forward Euler, like the reference's
+ * wake.  Every sum is formed in a fixed order that depends on the tracer count and on the step's anchor-derived bound of the
+ * wake size only: a trajectory repeats bit for bit, however a run is cut into calls.
+ *
+ * ludvm_march_set_tracers: valid after ludvm_march_setup (LUDVM_E_STATE otherwise); count <= LUDVM_MARCH_MAX_TRACERS;
+ *   count = 0 removes the tracers.  release: NULL (all 1), or one step >= 1 per tracer.  shift_x: NULL, or one x offset per
+ *   kinematics row (shift_rows must equal ludvm_march_setup's kin_rows).  cur_x, cur_z: NULL (start from the seeds:
+ *   (xs + shift_x[0], zs)), or the current positions -- what ludvm_march_tracer_state returned when a run is continued.
+ *   record_steps[nrecord]: the time steps whose positions ludvm_march_run keeps for ludvm_march_read_tracers, strictly
+ *   ascending, 1 <= step < kin_rows (nrecord = 0: none).  Everything is validated (finite values, release >= 1 included)
+ *   before anything is changed: a call refused with LUDVM_E_ARG leaves the tracers that were set -- their positions and the
+ *   rows of the last run -- as they were.  A call that passes validation and then fails in the runtime (LUDVM_E_HIP,
+ *   LUDVM_E_NOMEM: the buffers are replaced) leaves the context WITHOUT tracers.  ludvm_march_setup forgets any tracers.
+ *   A ludvm_march_run call that fails leaves the tracers' positions undefined: set them again.
+ * ludvm_march_read_tracers: the recorded rows of the LAST ludvm_march_run call -- those of record_steps inside
+ *   [first_step, first_step + count) -- as x[rows][count], z[rows][count] with their step numbers in steps_out[rows];
+ *   *nrows_out = rows (also when rows_cap < rows, which is LUDVM_E_ARG and copies nothing; rows = 0 copies nothing and is
+ *   LUDVM_OK).  LUDVM_E_STATE when no tracers are set, or when no ludvm_march_run call has succeeded since they were set.
+ * ludvm_march_tracer_state: the current positions x[count], z[count] (after the last step run; held tracers at their seed
+ *   with the last step's offset) -- for checkpoints and the final state.  LUDVM_E_STATE when no tracers are set.
+ * Guarantee: with tracers set, `rows`, `state`, `hist`, the resident wake and any probe rows of ludvm_march_run are
+ *   bit-identical to a call without them (the tracer kernels read the wake and write only buffers of their own).
+ * Limits: one device (not in ludvm_ensemble_run, not sharded); float64 sums only; tracers do not interact with the foil. */
+#define LUDVM_MARCH_MAX_TRACERS 262144
+int ludvm_march_set_tracers(ludvm_ctx* ctx, const double* seed_x, const double* seed_z, const long long* release, size_t count,
+                            const double* shift_x, size_t shift_rows, const double* cur_x, const double* cur_z,
+                            const long long* record_steps, size_t nrecord);
+int ludvm_march_read_tracers(ludvm_ctx* ctx, double* x, double* z, size_t rows_cap, long long* steps_out, size_t* nrows_out);
+int ludvm_march_tracer_state(ludvm_ctx* ctx, double* x, double* z);
+
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *
  * A parameter sweep (LESPcrit, k, alpha_max, dt, a gust vortex, 'Faure' / 'Ramesh') is `members` independent simulations,

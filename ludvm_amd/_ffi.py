@@ -30,6 +30,7 @@ ENSEMBLE_DESC = 6
 ENSEMBLE_MAX_PROBES = 1024     # LUDVM_ENSEMBLE_MAX_PROBES
 ENSEMBLE_PROBE_BYTES = 1 << 30  # most bytes of probe rows (2 * 8 * kinematics rows * probes) one ludvm_ensemble_run_probed call returns
 MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
+MARCH_MAX_TRACERS = 262144  # LUDVM_MARCH_MAX_TRACERS
 SYM_SCALE_BYTES = 32
 
 _pd, _pf = POINTER(c_double), POINTER(c_float)
@@ -86,6 +87,10 @@ SIGNATURES = {
     "ludvm_march_run": [c_void_p, c_longlong, c_longlong, c_int, _pd, _pd, _pd, c_size_t, POINTER(c_longlong)],
     "ludvm_march_set_probes": [c_void_p, _pd, _pd, c_size_t, _pd, c_size_t],
     "ludvm_march_read_probes": [c_void_p, _pd, _pd, c_size_t],
+    "ludvm_march_set_tracers": [c_void_p, _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, _pd, POINTER(c_longlong),
+                                c_size_t],
+    "ludvm_march_read_tracers": [c_void_p, _pd, _pd, c_size_t, POINTER(c_longlong), POINTER(c_size_t)],
+    "ludvm_march_tracer_state": [c_void_p, _pd, _pd],
     "ludvm_ensemble_limits": [c_void_p, POINTER(c_longlong)],
     "ludvm_ensemble_run": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
                            POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
@@ -111,7 +116,7 @@ SIGNATURES = {
 }
 
 # added to ABI 7 without a new version number: a library of ABI 7 built before them is detected by the missing symbol
-ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed",)
+ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm_march_read_tracers", "ludvm_march_tracer_state")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -113,6 +113,15 @@ struct ludvm_ctx {
   size_t probe_count = 0;                      // P (0: no probes)
   size_t probe_rows = 0;                       // steps of the last ludvm_march_run call that left rows (0: none to read)
   bool probe_shifted = false;
+  // passive tracers of the march (ludvm_march_set_tracers): seeds x[M] | z[M], release steps [M] and the earliest release
+  // of every tile, the per-step x offsets, the resident positions x[M] | z[M], the partial slabs of one step, the recorded
+  // rows of the last ludvm_march_run call x[rows][M] | z[rows][M] -- buffers of the tracers' own, like the probes'
+  Buf tracer_seed, tracer_release, tracer_shift, tracer_cur, tracer_part, tracer_out;
+  size_t tracer_count = 0;                     // M (0: no tracers)
+  bool tracer_shifted = false;
+  bool tracer_ran = false;                     // a ludvm_march_run call has succeeded since the tracers were set
+  std::vector<long long> tracer_record;        // steps whose rows are recorded, ascending
+  std::vector<long long> tracer_rows;          // the recorded steps of the last ludvm_march_run call
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

@@ -17,6 +17,10 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->march_ready = false;
   c->probe_count = 0;       // a new run: its probes are set after this call (ludvm_march_set_probes)
   c->probe_rows = 0;
+  c->tracer_count = 0;      // ... and its tracers (ludvm_march_set_tracers)
+  c->tracer_ran = false;
+  c->tracer_record.clear();
+  c->tracer_rows.clear();
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -153,9 +157,152 @@ int march_probe_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s
   return LUDVM_OK;
 }
 
+// Launch rule of the tracer kernels.  M tracers in tiles of kTracerTile (256 lanes x kTracerPerLane); the sources -- at most
+// ns_ub = n_ub + nfoil, n_ub the step's anchor-derived bound of the wake size after its solve -- in `nsplit` splits of `chunk`
+// sources, a multiple of the 256-source LDS tile, chosen so that tiles x splits comes to about 1024 workgroups (four per
+// CU), with at most 64 splits (the finisher adds them one after the other).  A function of M and n_ub alone: the summation
+// order of a step does not depend on where the calls of a run begin.
+struct TracerPlan { long long ttiles, m_pad, chunk; int nsplit; };
+constexpr long long kTracerGroups = 1024, kTracerMaxSplit = 64;
+long long tracer_want(long long ttiles) { return std::min(kTracerMaxSplit, std::max<long long>(1, kTracerGroups / ttiles)); }
+TracerPlan tracer_plan(size_t count, long long ns_ub) {
+  TracerPlan p;
+  p.ttiles = ((long long)count + kTracerTile - 1) / kTracerTile;
+  p.m_pad = p.ttiles * kTracerTile;
+  const long long want = tracer_want(p.ttiles);
+  ns_ub = std::max<long long>(ns_ub, 1);
+  p.chunk = std::max<long long>(kTracerSrcTile, ((ns_ub + want - 1) / want + kTracerSrcTile - 1) / kTracerSrcTile * kTracerSrcTile);
+  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
+  return p;
+}
+// the slab of any step: nsplit <= tracer_want(ttiles) whatever the wake size (at most 8 MiB)
+size_t tracer_slab_bytes(size_t count) {
+  const TracerPlan p = tracer_plan(count, 1);
+  return (size_t)tracer_want(p.ttiles) * 2 * (size_t)p.m_pad * 8;
+}
+
+// The tracers' Euler step of time step s (rec_row >= 0: also row rec_row of the call's record): enqueued where the probes
+// are, behind march_solve of step s on the stream that ran it and behind the probe kernels when both are set, so before the
+// roll-up's finisher moves anything.  The slab, the positions and the record are the tracers' own buffers, touched only by
+// these two kernels in stream order.  Reads the wake, writes nothing of it: rows, state, hist, the resident wake and the
+// probe rows keep their bits.
+int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s, long long rec_row, size_t rec_rows) {
+  const MarchSetup& m = c->msetup;
+  const size_t M = c->tracer_count;
+  const TracerPlan p = tracer_plan(M, n_ub + (long long)m.npan);
+  const double* seed = static_cast<const double*>(c->tracer_seed.p);
+  const long long* release = static_cast<const long long*>(c->tracer_release.p);
+  const double* shift = c->tracer_shifted ? static_cast<const double*>(c->tracer_shift.p) + s : nullptr;
+  double* cur = static_cast<double*>(c->tracer_cur.p);
+  double* slab = static_cast<double*>(c->tracer_part.p);
+  double* out = static_cast<double*>(c->tracer_out.p);
+  hipLaunchKernelGGL(march_tracer_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M, release,
+                     release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.m_pad,
+                     (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                     static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  HIPCHK(c, hipGetLastError());
+  double* rec_x = rec_row >= 0 ? out + (size_t)rec_row * M : nullptr;
+  double* rec_z = rec_row >= 0 ? out + (rec_rows + (size_t)rec_row) * M : nullptr;
+  hipLaunchKernelGGL(march_tracer_finish, dim3(blocks_for((long long)M)), dim3(kBlock), 0, st, (const double*)slab, p.m_pad, p.nsplit,
+                     seed, seed + M, release, shift, s, (long long)M, m.dt, cur, cur + M, rec_x, rec_z);
+  HIPCHK(c, hipGetLastError());
+  return LUDVM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* seed_z, const long long* release, size_t count,
+                            const double* shift_x, size_t shift_rows, const double* cur_x, const double* cur_z,
+                            const long long* record_steps, size_t nrecord) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
+  if (count > LUDVM_MARCH_MAX_TRACERS) return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_TRACERS) + " tracers");
+  if (count && (!seed_x || !seed_z)) return fail(c, LUDVM_E_ARG, "null array");
+  if (count && ((cur_x == nullptr) != (cur_z == nullptr))) return fail(c, LUDVM_E_ARG, "march: tracer positions need both cur_x and cur_z");
+  if (count && nrecord && !record_steps) return fail(c, LUDVM_E_ARG, "null array");
+  if (count && shift_x && shift_rows != c->march_kin_rows)
+    return fail(c, LUDVM_E_ARG, "march: tracer offsets must be one per kinematics row");
+  for (size_t k = 0; k < count; ++k) {
+    if (!std::isfinite(seed_x[k]) || !std::isfinite(seed_z[k])) return fail(c, LUDVM_E_ARG, "march: tracer seeds must be finite");
+    if (cur_x && (!std::isfinite(cur_x[k]) || !std::isfinite(cur_z[k]))) return fail(c, LUDVM_E_ARG, "march: tracer positions must be finite");
+    if (release && release[k] < 1) return fail(c, LUDVM_E_ARG, "march: tracer release steps must be >= 1");
+  }
+  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
+    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: tracer offsets must be finite");
+  for (size_t k = 0; count && k < nrecord; ++k)
+    if (record_steps[k] < 1 || (size_t)record_steps[k] >= c->march_kin_rows || (k && record_steps[k] <= record_steps[k - 1]))
+      return fail(c, LUDVM_E_ARG, "march: tracer record steps must be ascending and inside the kinematics table");
+  c->tracer_count = 0;
+  c->tracer_ran = false;
+  c->tracer_record.clear();
+  c->tracer_rows.clear();
+  if (count == 0) return LUDVM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const TracerPlan p = tracer_plan(count, 1);
+  // host images: release steps (NULL: all 1) with the earliest release of every tile behind them; the first positions
+  std::vector<long long> rel(count + (size_t)p.ttiles);
+  for (size_t k = 0; k < count; ++k) rel[k] = release ? release[k] : 1;
+  for (long long t = 0; t < p.ttiles; ++t) {
+    const size_t lo = (size_t)t * kTracerTile, hi = std::min(count, lo + (size_t)kTracerTile);
+    rel[count + (size_t)t] = *std::min_element(rel.begin() + lo, rel.begin() + hi);
+  }
+  std::vector<double> cur(2 * count);
+  for (size_t k = 0; k < count; ++k) {
+    cur[k] = cur_x ? cur_x[k] : seed_x[k] + (shift_x ? shift_x[0] : 0.0);
+    cur[count + k] = cur_z ? cur_z[k] : seed_z[k];
+  }
+  CHK(ensure(c, c->tracer_seed, 2 * count * 8));
+  CHK(ensure(c, c->tracer_release, rel.size() * 8));
+  CHK(ensure(c, c->tracer_cur, 2 * count * 8));
+  CHK(ensure(c, c->tracer_part, tracer_slab_bytes(count)));
+  if (shift_x) CHK(ensure(c, c->tracer_shift, shift_rows * 8));
+  double* seed = static_cast<double*>(c->tracer_seed.p);
+  HIPCHK(c, hipMemcpyAsync(seed, seed_x, count * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(seed + count, seed_z, count * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->tracer_release.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->tracer_cur.p, cur.data(), 2 * count * 8, hipMemcpyHostToDevice, c->stream));
+  if (shift_x) HIPCHK(c, hipMemcpyAsync(c->tracer_shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (rel and cur live on this frame)
+  c->tracer_shifted = shift_x != nullptr;
+  c->tracer_record.assign(record_steps, record_steps + nrecord);
+  c->tracer_count = count;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_tracers(ludvm_ctx* c, double* x, double* z, size_t rows_cap, long long* steps_out, size_t* nrows_out) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (!c->tracer_ran) return fail(c, LUDVM_E_STATE, "march: no ludvm_march_run call has succeeded since the tracers were set");
+  if (!nrows_out) return fail(c, LUDVM_E_ARG, "null array");
+  const size_t rows = c->tracer_rows.size();
+  *nrows_out = rows;
+  if (rows_cap < rows) return fail(c, LUDVM_E_ARG, "march: the last ludvm_march_run call recorded " + std::to_string(rows) + " tracer rows");
+  if (rows == 0) return LUDVM_OK;
+  if (!x || !z || !steps_out) return fail(c, LUDVM_E_ARG, "null array");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = rows * c->tracer_count;
+  const double* out = static_cast<const double*>(c->tracer_out.p);
+  HIPCHK(c, hipMemcpyAsync(x, out, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(z, out + n, n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < rows; ++k) steps_out[k] = c->tracer_rows[k];
+  return LUDVM_OK;
+}
+
+int ludvm_march_tracer_state(ludvm_ctx* c, double* x, double* z) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (!x || !z) return fail(c, LUDVM_E_ARG, "null array");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t M = c->tracer_count;
+  const double* cur = static_cast<const double*>(c->tracer_cur.p);
+  HIPCHK(c, hipMemcpyAsync(x, cur, M * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(z, cur + M, M * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LUDVM_OK;
+}
 
 int ludvm_march_set_probes(ludvm_ctx* c, const double* x, const double* z, size_t count, const double* shift_x, size_t shift_rows) {
   if (!c) return LUDVM_E_ARG;
@@ -205,6 +352,8 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
   c->probe_rows = 0;
+  c->tracer_ran = false;
+  c->tracer_rows.clear();
   if (!valid_precision(precision)) return fail(c, LUDVM_E_ARG, "unknown precision");
   if (!state || !rows) return fail(c, LUDVM_E_ARG, "null array");
   if (count < 1 || first_step < 1 || (size_t)(first_step + count) > c->march_kin_rows)
@@ -232,6 +381,14 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   if (hist) CHK(ensure(c, c->march_hist, (size_t)count * 2 * hist_nmax * 8));
   const bool probes = c->probe_count != 0;
   if (probes) CHK(ensure(c, c->probe_out, (size_t)count * 2 * c->probe_count * 8));      // (the slab: ludvm_march_set_probes)
+  const bool tracers = c->tracer_count != 0;
+  std::vector<long long> trec;      // the call's recorded tracer steps, ascending: row k of the record is step trec[k]
+  if (tracers) {
+    for (long long r : c->tracer_record)
+      if (r >= first_step && r < first_step + count) trec.push_back(r);
+    if (!trec.empty()) CHK(ensure(c, c->tracer_out, trec.size() * 2 * c->tracer_count * 8));
+  }
+  size_t trec_at = 0;               // the next recorded step
 
   MarchState hs{};
   hs.n = n0;
@@ -358,6 +515,11 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
                          c->mir(), c->g32, c->progress_dev);
       HIPCHK(c, hipGetLastError());
       if (probes) CHK(march_probe_launch(c, c->stream, n_ub, s, rel, count));
+      if (tracers) {
+        const bool rec = trec_at < trec.size() && trec[trec_at] == s;
+        CHK(march_tracer_launch(c, c->stream, n_ub, s, rec ? (long long)trec_at : -1, trec.size()));
+        trec_at += rec;
+      }
       MarchSym ms;
       ms.scale = &S->sc[(s + 1) & 1]; ms.bad = &S->sym_bad; ms.n_lo = n_lo + 1; ms.march = overlap_ok;
       CHK(advect_launch(c, (size_t)n_ub, &S->n, m.dt, nfoil, c->march_vcore, precision, nullptr, nullptr, td, ms));
@@ -388,6 +550,11 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
       }
       // (probes: behind the solve on the second stream, before ev_join lets the finisher move the wake)
       if (rc == LUDVM_OK && probes) rc = march_probe_launch(c, c->stream_b, n_ub, s, rel, count);
+      if (rc == LUDVM_OK && tracers) {
+        const bool rec = trec_at < trec.size() && trec[trec_at] == s;
+        rc = march_tracer_launch(c, c->stream_b, n_ub, s, rec ? (long long)trec_at : -1, trec.size());
+        trec_at += rec;
+      }
       c->stream = main_stream;
       CHK(rc);
       HIPCHK(c, hipEventRecord(c->ev_join, c->stream_b));
@@ -446,6 +613,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   for (int k = 0; k < m.ncoef; ++k) state[16 + k] = hs.prevA[k];
   if (c->timing) CHK(drain_timing(c));
   if (probes) c->probe_rows = (size_t)count;
+  if (tracers) { c->tracer_rows = trec; c->tracer_ran = true; }
   return LUDVM_OK;
 }
 

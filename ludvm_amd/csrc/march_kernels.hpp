@@ -568,4 +568,139 @@ march_probe_finish(const double* slab, long long p_pad, int nsplit, int count, d
   if (lane == 0) (k == 0 ? out_u : out_w)[p] = acc;
 }
 
+// ---- passive tracers (ludvm_march_set_tracers) -----------------------------------------------------------------------------------
+// A tracer is a probe that moves with what it measures.  Tracer m has a seed (xs, zs) and a release step r_m >= 1; with
+// shift[i] the frame offset of step i (0 in the lab frame):
+//   step i <  r_m   held: its position of step i is (xs + shift[i], zs); it takes part in no pair sum
+//   step i >= r_m   start = (xs + shift[i], zs) if i == r_m, else its position after step i - 1;
+//                   position after step i = start + dt (u, w)_i(start)
+// (u, w)_i is the probes' field (above): the sources [0, S->n + nfoil) right behind march_solve of step i, Vatistas core, no
+// freestream term, float64 -- the forward-Euler step the roll-up gives a wake vortex of zero circulation (LUDVM.py:1120-1127).
+//
+// march_tracer_partial  grid = tracer tiles (kTracerTile = 256 lanes x kTracerPerLane tracers: tracer t0 + k * 256 + lane in
+//                       register set k of the lane) x source splits; 256-source tiles staged in LDS, every broadcast read of a
+//                       source serves kTracerPerLane pairs; pair_f64's arithmetic; the source count is read on the device;
+//                       (split, tracer) partial sums to a slab [split][2][m_pad] of the tracers' own.  A tile whose earliest
+//                       release (tile_min, precomputed by the host) is after step i leaves at once; a held lane of a mixed
+//                       tile walks along at the pad position and stores nothing
+// march_tracer_finish   one lane per tracer: splits 0, 1, 2, ... in that order, `start` by the rule above, the new position
+//                       into the resident cur_x / cur_z (held: seed + shift[i]) and -- rec_x given -- into the call's row
+// The splits are a function of the tracer count and of the step's anchor-derived bound alone (tracer_plan, march.hip), every
+// partial sum is formed by one lane in source order and the splits are combined in split order: a trajectory repeats bit
+// for bit however a run is cut into calls.  Both kernels write the tracers' buffers only.
+constexpr int kTracerPerLane = 2;
+constexpr int kTracerTile = kBlock * kTracerPerLane;
+constexpr int kTracerSrcTile = 256;
+
+__device__ __forceinline__ void tracer_start(const double* __restrict__ seed_x, const double* __restrict__ seed_z,
+                                             const double* cur_x, const double* cur_z, long long m, long long rel, long long step,
+                                             double sh, double& x, double& z) {
+  if (rel == step) {
+    x = seed_x[m] + sh;
+    z = seed_z[m];
+  } else {
+    x = cur_x[m];
+    z = cur_z[m];
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_tracer_partial(const double* __restrict__ seed_x, const double* __restrict__ seed_z, const long long* __restrict__ release,
+                     const long long* __restrict__ tile_min, const double* cur_x, const double* cur_z, const double* shift,
+                     long long step, long long count, long long m_pad, const double* __restrict__ xs, const double* __restrict__ zs,
+                     const double* __restrict__ gs, const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
+  __shared__ __attribute__((aligned(16))) double lx[kTracerSrcTile];
+  __shared__ __attribute__((aligned(16))) double lz[kTracerSrcTile];
+  __shared__ __attribute__((aligned(16))) double lg[kTracerSrcTile];
+  if (tile_min[blockIdx.x] > step) return;         // every tracer of the tile is still held (uniform: before any barrier)
+  __builtin_amdgcn_s_setprio(3);
+  const int tid = threadIdx.x;
+  const long long t0 = (long long)blockIdx.x * kTracerTile + tid;
+  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
+  const long long s_begin = (long long)blockIdx.y * chunk;
+  long long s_end = s_begin + chunk;
+  if (s_end > ns) s_end = ns;
+  const double sh = shift ? *shift : 0.0;
+  double xp[kTracerPerLane], zp[kTracerPerLane], au[kTracerPerLane], aw[kTracerPerLane];
+  bool free_[kTracerPerLane];
+#pragma unroll
+  for (int k = 0; k < kTracerPerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    xp[k] = kPadPosD; zp[k] = kPadPosD; au[k] = 0.0; aw[k] = 0.0;
+    free_[k] = false;
+    if (m < count) {
+      const long long rel = release[m];
+      free_[k] = rel <= step;
+      if (free_[k]) tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, xp[k], zp[k]);
+    }
+  }
+  for (long long base = s_begin; base < s_end; base += kTracerSrcTile) {
+    __syncthreads();
+    {
+      const long long si = base + tid;
+      const bool ok = si < s_end;
+      lx[tid] = ok ? xs[si] : kPadPosD;
+      lz[tid] = ok ? zs[si] : kPadPosD;
+      lg[tid] = ok ? gs[si] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < kTracerSrcTile; ++j) {
+      const double sx = lx[j], sz = lz[j], sg = lg[j];
+#pragma unroll
+      for (int k = 0; k < kTracerPerLane; ++k) {
+        const double dx = xp[k] - sx;
+        const double dz = zp[k] - sz;
+        const double r2 = __builtin_fma(dz, dz, dx * dx);
+        const double q = __builtin_fma(r2, r2, vc4);
+        const double s = sg * rsqrt_f64(q);
+        au[k] = __builtin_fma(dz, s, au[k]);
+        aw[k] = __builtin_fma(dx, s, aw[k]);
+      }
+    }
+  }
+  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
+  double* row = slab + (long long)blockIdx.y * 2 * m_pad;
+#pragma unroll
+  for (int k = 0; k < kTracerPerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    if (free_[k]) {
+      row[m] = au[k] * kInv2PiD;
+      row[m_pad + m] = -aw[k] * kInv2PiD;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_tracer_finish(const double* slab, long long m_pad, int nsplit, const double* __restrict__ seed_x,
+                    const double* __restrict__ seed_z, const long long* __restrict__ release, const double* shift, long long step,
+                    long long count, double dt, double* cur_x, double* cur_z, double* rec_x, double* rec_z) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (m >= count) return;
+  const double sh = shift ? *shift : 0.0;
+  const long long rel = release[m];
+  double x, z;
+  if (rel > step) {
+    x = seed_x[m] + sh;
+    z = seed_z[m];
+  } else {
+    tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, x, z);
+    double u = 0.0, w = 0.0;
+    const double* c0 = slab + m;
+    for (int sidx = 0; sidx < nsplit; ++sidx) {
+      u += c0[(long long)sidx * 2 * m_pad];
+      w += c0[(long long)sidx * 2 * m_pad + m_pad];
+    }
+    x = __builtin_fma(dt, u, x);
+    z = __builtin_fma(dt, w, z);
+  }
+  cur_x[m] = x;
+  cur_z[m] = z;
+  if (rec_x) {
+    rec_x[m] = x;
+    rec_z[m] = z;
+  }
+}
+
 }  // namespace ludvm

@@ -371,6 +371,7 @@ class Engine:
         self._check(self._lib.ludvm_march_setup(self._ctx, int(npan), int(ncoef), _pd(sc), _pd(tb), _pd(kin), kin.shape[0]))
         self._march_dims = (int(npan), int(ncoef))
         self._march_nprobes = 0          # (ludvm_march_setup forgets any probes)
+        self._march_ntracers = 0         # (... and any tracers)
 
     def march_run(self, first_step, count, precision, state, hist_nmax=0, anchors=None):
         """Advance the resident wake through time steps [first_step, first_step + count) without a host round
@@ -387,6 +388,7 @@ class Engine:
         anc = None
         if anchors is not None:
             anc = (ctypes.c_longlong * 4)(*[int(v) for v in anchors])
+        self._march_last = (int(first_step), int(count))
         self._check(self._lib.ludvm_march_run(self._ctx, int(first_step), int(count), _prec(precision), _pd(state), _pd(rows),
                                               _pd(hist), int(hist_nmax), anc))
         return (rows, hist) if hist_nmax else rows
@@ -408,6 +410,54 @@ class Engine:
         u, w = np.empty([int(count), self._march_nprobes]), np.empty([int(count), self._march_nprobes])
         self._check(self._lib.ludvm_march_read_probes(self._ctx, _pd(u), _pd(w), int(count)))
         return u, w
+
+    def march_set_tracers(self, seed_x, seed_z, release=None, shift_x=None, cur=None, record_steps=()):
+        """Passive tracers advected by every marched step (ludvm_march_set_tracers); valid after `march_setup`, which forgets
+        them.  release: None (all released at step 1), or one step >= 1 per tracer -- before it a tracer is held at its
+        seed.  shift_x: None, or one x offset per kinematics row (the seed of step i is (x + shift_x[i], z)).  cur: None
+        (start from the seeds), or the current positions [2, M] of a run that is continued.  record_steps: the time steps,
+        ascending, whose positions `march_run` keeps for `march_tracers`.  Empty seeds remove the tracers."""
+        if not hasattr(self._lib, "ludvm_march_set_tracers"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_tracers")
+        xs, zs = _f64(seed_x), _f64(seed_z)
+        if len(xs) != len(zs):
+            raise ValueError("march_set_tracers: seed_x and seed_z must have the same length")
+        rel = None if release is None else np.ascontiguousarray(release, dtype=np.int64).reshape(-1)
+        if rel is not None and len(rel) != len(xs):
+            raise ValueError("march_set_tracers: one release step per tracer")
+        sh = None if shift_x is None else _f64(shift_x)
+        cx = cz = None
+        if cur is not None:
+            cur = np.asarray(cur, dtype=np.float64)
+            if cur.shape != (2, len(xs)):
+                raise ValueError("march_set_tracers: cur must be [2, M]")
+            cx, cz = _f64(cur[0]), _f64(cur[1])
+        rec = np.ascontiguousarray(list(record_steps), dtype=np.int64).reshape(-1)
+        pl = POINTER(c_longlong)
+        self._check(self._lib.ludvm_march_set_tracers(
+            self._ctx, _pd(xs), _pd(zs), None if rel is None else rel.ctypes.data_as(pl), len(xs), _pd(sh),
+            0 if sh is None else len(sh), _pd(cx), _pd(cz), rec.ctypes.data_as(pl) if len(rec) else None, len(rec)))
+        self._march_ntracers = len(xs)
+        self._march_tracer_record = rec
+
+    def march_tracers(self):
+        """(steps int64 [R], xz float64 [R, 2, M]): the tracer rows the last `march_run` call recorded, with their time steps
+        (ludvm_march_read_tracers)."""
+        first, count = self._march_last
+        rec = self._march_tracer_record
+        M, cap = self._march_ntracers, int(np.count_nonzero((rec >= first) & (rec < first + count)))
+        x, z = np.empty([cap, M]), np.empty([cap, M])
+        steps, n = np.zeros(max(cap, 1), dtype=np.int64), c_size_t(0)
+        self._check(self._lib.ludvm_march_read_tracers(self._ctx, _pd(x), _pd(z), cap, steps.ctypes.data_as(POINTER(c_longlong)),
+                                                       byref(n)))
+        r = int(n.value)
+        return steps[:r].copy(), np.stack([x[:r], z[:r]], axis=1)
+
+    def march_tracer_state(self):
+        """float64 [2, M]: the tracers' current positions (ludvm_march_tracer_state)."""
+        xz = np.empty([2, self._march_ntracers])
+        self._check(self._lib.ludvm_march_tracer_state(self._ctx, _pd(xz[0]), _pd(xz[1])))
+        return xz
 
     @staticmethod
     def march_anchor_steps(first_step):

@@ -29,6 +29,7 @@ _REFUSED = {
     "devices": (None, "a sweep runs on one GPU (members are independent: split the list per device)"),
     "march": (True, "the members of a sweep are marched on the device"),
     "run": (True, "the members of a sweep are run"),
+    "tracers": (None, "a sweep has no tracers (a member can be run on its own: LUDVM(..., tracers=...))"),
 }
 
 
@@ -114,12 +115,12 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
-    history='full', checkpoint_*, distributed, devices, march=False, run=False, an engine without ensemble_run; `probes` or
+    history='full', checkpoint_*, distributed, devices, tracers, march=False, run=False, an engine without ensemble_run; `probes` or
     `probe_frame` inside a member's dict (they belong to the sweep), more than 1024 probes, points that are not finite, a
     probe_frame other than 'lab' / 'tunnel', an engine without ensemble_run_probed, and probe rows (16 bytes x all members' time
     levels x P) over 1 GiB: split the case list.
 
-    Out of scope: per-member probe sets, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe sets, tracers, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     cases = list(cases)
     if not cases:

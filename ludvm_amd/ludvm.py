@@ -107,6 +107,23 @@ class LUDVM:
                  from its dense history, for runs that cannot keep one.  One GPU only.  Results are unchanged by it, bit for bit
       probe_frame  'lab' (default): the points are fixed in the lab frame; 'tunnel': x is measured from the pivot's
                  x-coordinate -- the lab position at step i is (x + xpiv[i], z) (the frame translates only)
+      tracers    None (default), or seeds [2, M] (x row, z row; 1 <= M <= 262144) of passive tracers: particles advected by
+                 the field that convects the wake, inside the device-resident march (or from two engine calls per step on
+                 the per-step path), always in float64.  Tracer m is held at its seed until its release step r_m >= 1; in
+                 step i >= r_m it moves from `start` -- the seed if i == r_m, else its position after step i - 1 -- to
+                 start + dt (u, w)_i(start), (u, w)_i being exactly the field of `probes`.  Released at step 1 in the lab
+                 frame this is, to rounding, the path['FREE'] trajectory of a zero-circulation free vortex at the same
+                 seed -- but a tracer is no source of the roll-up, does not grow the wake, can be released during the run
+                 and needs no dense history.  Results: `tracer_path`, a SparseHistory step -> [2, M] (row 0, the seeds,
+                 always present), `tracer_last` [2, M] (positions after the final step), `tracer_xz`, `tracer_release`,
+                 `tracer_frame` as given, `tracer_released(step)` -> bool [M].  Every other result is unchanged, bit for
+                 bit.  Out of scope: tracers in a sweep, on several GPUs, fp32 tracer sums, higher-order time integration
+                 (the reference's wake is forward Euler, and the tracers follow it), tracers that interact with the foil
+      tracer_release  None (all 1), or one integer release step >= 1 per tracer (a step >= nt: never released)
+      tracer_frame  'lab' (default): seeds fixed in the lab frame; 'tunnel': a held tracer rides with the pivot -- its seed
+                 at step i is (x + xpiv[i], z) -- and is released into the lab frame from there
+      tracer_steps  time steps whose positions `tracer_path` keeps; None (default): every step when the run keeps a dense
+                 history, snapshot_steps and the last step otherwise
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -130,6 +147,9 @@ class LUDVM:
                 if kwargs.get('probes') is not None:
                     cls._check_probes(kwargs['probes'], kwargs.get('probe_frame', 'lab'))
                     raise ValueError("probes run on one GPU: not with more than one device in `devices`")
+                if kwargs.get('tracers') is not None:
+                    cls._check_tracers(kwargs['tracers'], kwargs.get('tracer_release'), kwargs.get('tracer_frame', 'lab'))
+                    raise ValueError("tracers run on one GPU: not with more than one device in `devices`")
                 return MultiDeviceLUDVM(args, kwargs, devs)
         return super().__new__(cls)
 
@@ -150,6 +170,47 @@ class LUDVM:
             raise ValueError("probes must be finite")
         return np.ascontiguousarray(xz)
 
+    @staticmethod
+    def _check_tracers(tracers, tracer_release, tracer_frame, tracer_steps=None, nt=None):
+        """-> (float64 [2, M], int64 [M], sorted steps or None), or ValueError (nothing else has been created yet)."""
+        if tracer_frame not in ('lab', 'tunnel'):
+            raise ValueError("tracer_frame must be 'lab' or 'tunnel'")
+        try:
+            xz = np.array(tracers, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError("tracers must be an array-like [2, M] of numbers") from e
+        if xz.ndim != 2 or xz.shape[0] != 2 or xz.shape[1] < 1:
+            raise ValueError(f"tracers must be [2, M] with M >= 1 (x row, z row); got shape {xz.shape}")
+        M = xz.shape[1]
+        if M > 262144:
+            raise ValueError(f"tracers: at most 262144 (got {M})")
+        if not np.isfinite(xz).all():
+            raise ValueError("tracers must be finite")
+        if tracer_release is None:
+            rel = np.ones(M, dtype=np.int64)
+        else:
+            try:
+                rel = np.asarray(tracer_release)
+            except (TypeError, ValueError) as e:
+                raise ValueError("tracer_release must be integers [M]") from e
+            if rel.dtype.kind not in 'iu' or rel.shape != (M,):
+                raise ValueError(f"tracer_release must be integers [M] with M = {M} (one release step per tracer)")
+            if rel.min() < 1:
+                raise ValueError("tracer_release: release steps are >= 1")
+            rel = rel.astype(np.int64)
+        steps = None
+        if tracer_steps is not None:
+            try:
+                raw = [s for s in tracer_steps]
+                steps = sorted({int(s) for s in raw})
+            except (TypeError, ValueError) as e:
+                raise ValueError("tracer_steps must be an iterable of time steps") from e
+            if any(int(s) != s for s in raw):
+                raise ValueError("tracer_steps must be integers")
+            if nt is not None and steps and (steps[0] < 0 or steps[-1] >= nt):
+                raise ValueError(f"tracer_steps must lie in [0, {nt})")
+        return np.ascontiguousarray(xz), rel, steps
+
     def __init__(self, t0=0, tf=12, dt=1.5e-2, chord=1, rho=1.225, Uinf=1,
                  Npoints=80, Ncoeffs=30, LESPcrit=0.2, Naca='0012',
                  foil_filename=None, G=1, T=2, alpha_m=0,
@@ -158,7 +219,7 @@ class LUDVM:
                  circulation_freevort=None, xy_freevort=None, *,
                  engine=None, device=0, precision='auto', history='auto', snapshot_steps=(), run=True,
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
-                 probes=None, probe_frame='lab'):
+                 probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -166,6 +227,16 @@ class LUDVM:
                 raise ValueError("probes run on one GPU: not with `distributed`")
         elif probe_frame not in ('lab', 'tunnel'):
             raise ValueError("probe_frame must be 'lab' or 'tunnel'")
+        if tracers is not None:
+            # refused before any engine, thread or communicator exists
+            tracer_xz, tracer_rel, tracer_rec = self._check_tracers(tracers, tracer_release, tracer_frame, tracer_steps,
+                                                                    nt=len(np.arange(t0, tf + dt, dt)))
+            if distributed is not None and distributed is not False:
+                raise ValueError("tracers run on one GPU: not with `distributed`")
+        elif tracer_frame not in ('lab', 'tunnel'):
+            raise ValueError("tracer_frame must be 'lab' or 'tunnel'")
+        elif tracer_release is not None or tracer_steps is not None:
+            raise ValueError("tracer_release / tracer_steps need `tracers`")
         # the smallest section the method runs: two panels; the loads read A0 .. A3 (LUDVM.py:1035-1090)
         if Npoints < 3:
             raise ValueError(f"Npoints={Npoints}: a section has at least 3 points (2 panels)")
@@ -181,6 +252,11 @@ class LUDVM:
         if probes is not None:              # (a run without probes keeps the attributes -- and the checkpoints -- it had)
             self._ctor.update(probes=probe_xz.tolist(), probe_frame=probe_frame)
             self.probe_xz, self.probe_frame = probe_xz, probe_frame
+        if tracers is not None:             # (likewise)
+            self._ctor.update(tracers=tracer_xz.tolist(), tracer_release=tracer_rel.tolist(), tracer_frame=tracer_frame,
+                              tracer_steps=tracer_rec)
+            self.tracer_xz, self.tracer_release, self.tracer_frame = tracer_xz, tracer_rel, tracer_frame
+            self._tracer_steps = tracer_rec
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -454,6 +530,8 @@ class LUDVM:
                         continue
                 self._host_step(S, i, print_dt)
                 i += 1
+            if S.tracers is not None:
+                self.tracer_last = eng.march_tracer_state() if S.can_march else S.tcur
         finally:
             if self._shard is not None:
                 self._shard.detach(eng)
@@ -467,6 +545,7 @@ class LUDVM:
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
             'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
+            'tracers', 'trec', 'tcur',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
@@ -562,7 +641,29 @@ class LUDVM:
             self.probe_u, self.probe_w = np.zeros([nt, S.probes.shape[1]]), np.zeros([nt, S.probes.shape[1]])
             p0 = self.probe_positions(0)
             self.probe_u[0], self.probe_w[0] = eng.induce(g_free, free0[0], free0[1], p0[0], p0[1], self.v_core, precision='f64')
+        S.tracers = getattr(self, 'tracer_xz', None)
+        S.trec = S.tcur = None
+        if S.tracers is not None:
+            # recorded steps >= 1 (row 0, the seeds, is always kept); the positions the loop carries
+            rec = self._tracer_steps
+            if rec is None:
+                rec = range(1, nt) if full else sorted(self.snapshot_steps | {nt - 1})
+            S.trec = np.array([q for q in rec if 1 <= q < nt], dtype=np.int64)
+            self.tracer_path = SparseHistory(nt)
+            S.tcur = self._tracer_seeds(0)
+            self.tracer_path.store(0, S.tcur.copy())
         return S
+
+    def _tracer_seeds(self, step):
+        """Lab coordinates [2, M] of the seeds at time step `step` ('tunnel' frame: x + xpiv[step])."""
+        xz = self.tracer_xz.copy()
+        if self.tracer_frame == 'tunnel':
+            xz[0] = xz[0] + self.xpiv[int(step)]
+        return xz
+
+    def tracer_released(self, step):
+        """bool [M]: the tracers that move in time step `step` (released at or before it)."""
+        return self.tracer_release <= int(step)
 
     def probe_positions(self, step):
         """Lab coordinates [2, P] of the probes at time step `step` ('tunnel' frame: x + xpiv[step])."""
@@ -585,6 +686,10 @@ class LUDVM:
             getattr(self, name)[...] = R[name]
         if S.probes is not None:
             self.probe_u[:S.first_step], self.probe_w[:S.first_step] = R['probe_u'], R['probe_w']
+        if S.tracers is not None:
+            S.tcur = R['tracer_cur'].copy()
+            for srow, row in zip(R['tracer_rows_steps'], R['tracer_rows']):
+                self.tracer_path.store(int(srow), row.copy())
         for key in ('TEV', 'LEV', 'FREE'):
             if self.history == 'full':
                 P[key][:S.first_step] = R['path_' + key]
@@ -600,6 +705,8 @@ class LUDVM:
         """Host buffers of the per-step path; tables and kinematics of the device-resident march."""
         eng = self.engine
         npan = self.Npoints - 1
+        if S.tracers is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracers'):
+            raise RuntimeError("tracers: this engine marches but has no march_set_tracers (pass march=False for the per-step path)")
         # preallocated host buffers for the two device calls of a step (engines that offer them)
         S.sb = eng.step_buffers(npan) if hasattr(eng, 'step_buffers') else None
         S.prec_code = {'f32': 0, 'f32x2': 1, 'f64': 2}[self.precision]
@@ -613,6 +720,9 @@ class LUDVM:
             eng.march_setup(npan, self.Ncoeffs, *self._march_inputs(S))
             if S.probes is not None:
                 eng.march_set_probes(S.probes[0], S.probes[1], shift_x=self.xpiv if self.probe_frame == 'tunnel' else None)
+            if S.tracers is not None:
+                eng.march_set_tracers(S.tracers[0], S.tracers[1], release=self.tracer_release,
+                                      shift_x=self.xpiv if self.tracer_frame == 'tunnel' else None, cur=S.tcur, record_steps=S.trec)
         # with the dense history every step's row is recorded: the march then keeps a snapshot of the wake per step on
         # the device (shorter calls, the snapshots are [steps, 2, wake size])
         S.dense_march = S.can_march and self.history == 'full'
@@ -670,6 +780,12 @@ class LUDVM:
         if S.probes is not None:
             # one call's probe rows ([steps, 2, P] doubles) stay at or under 256 MB, like the history rows
             j = min(j, i + max(1, int(getattr(self, '_probe_call_bytes', 256e6) // (16 * S.probes.shape[1]))))
+        if S.tracers is not None:
+            # one call's recorded tracer rows ([rows, 2, M] doubles) stay at or under 256 MB as well
+            most = max(1, int(getattr(self, '_tracer_call_bytes', 256e6) // (16 * S.tracers.shape[1])))
+            lo = int(np.searchsorted(S.trec, i))
+            if int(np.searchsorted(S.trec, j)) - lo > most:
+                j = int(S.trec[lo + most])      # (the call ends before its `most + 1`-th recorded step)
         return j, rec_i
 
     def _march_call(self, S, i, j, rec_i, print_dt):
@@ -709,6 +825,9 @@ class LUDVM:
             R = self.engine.march_run(i, cnt, S.prec_code, st, anchors=anchors)
         if S.probes is not None:
             self.probe_u[i:j], self.probe_w[i:j] = self.engine.march_probes(cnt)
+        if S.tracers is not None:
+            for srow, row in zip(*self.engine.march_tracers()):
+                self.tracer_path.store(int(srow), row)
         self._store_march_results(S, i, j, st, R, hist)
 
     def _store_march_results(self, S, i, j, st, R, hist=None):
@@ -929,6 +1048,24 @@ class LUDVM:
             un, wn = eng.induce(np.concatenate([new_g[:ns], dGamma]), np.concatenate([new_x[:ns], xg]), np.concatenate([new_z[:ns], zg]),
                                 px, pz, vc, precision='f64')
             self.probe_u[i], self.probe_w[i] = uo + un, wo + wn
+        if S.tracers is not None:
+            # the same field at the released tracers' start positions, and their Euler step (held ones ride with the seed)
+            seeds = self._tracer_seeds(i)
+            rel, nxt = self.tracer_release, seeds
+            free = rel <= i
+            if free.any():
+                first = (rel == i)[free]
+                px = np.where(first, seeds[0][free], S.tcur[0][free])
+                pz = np.where(first, seeds[1][free], S.tcur[1][free])
+                ns = 2 if shed else 1
+                uo, wo = eng.wake_induce_on_points(0, n_wake, px, pz, vc)
+                un, wn = eng.induce(np.concatenate([new_g[:ns], dGamma]), np.concatenate([new_x[:ns], xg]),
+                                    np.concatenate([new_z[:ns], zg]), px, pz, vc, precision='f64')
+                nxt[0][free], nxt[1][free] = px + dt * (uo + un), pz + dt * (wo + wn)
+            S.tcur = nxt
+            k = int(np.searchsorted(S.trec, i))
+            if k < len(S.trec) and S.trec[k] == i:
+                self.tracer_path.store(i, nxt.copy())
         n_after = n_wake + len(new_x)
         one_trip = (not record) and sb is not None and i < nt - 1 and hasattr(eng, 'wake_step_into')
         if not one_trip:
@@ -1024,6 +1161,11 @@ class LUDVM:
             d[name] = getattr(self, name)
         if S.probes is not None:        # (the definition travels in `ctor`)
             d['probe_u'], d['probe_w'] = self.probe_u[:next_step], self.probe_w[:next_step]
+        if S.tracers is not None:       # (likewise; the current positions and the rows recorded so far)
+            d['tracer_cur'] = self.engine.march_tracer_state() if S.can_march else S.tcur
+            steps_t = self.tracer_path.steps()
+            d['tracer_rows_steps'] = np.array(steps_t, dtype=np.int64)
+            d['tracer_rows'] = np.stack([self.tracer_path[q] for q in steps_t])
         if self.history == 'full':
             for key in ('TEV', 'LEV', 'FREE'):
                 d['path_' + key] = P[key][:next_step]
@@ -1053,6 +1195,8 @@ class LUDVM:
                     raise ValueError("devices=[...] creates the engines and their communicator itself: do not pass engine= / distributed=")
                 if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('probes') is not None:
                     raise ValueError("probes run on one GPU: this checkpoint cannot be resumed on more than one device")
+                if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('tracers') is not None:
+                    raise ValueError("tracers run on one GPU: this checkpoint cannot be resumed on more than one device")
                 return MultiDeviceLUDVM((), {}, devs, builder=lambda r, eng, grp: cls.resume(
                     path, engine=eng, verbose=verbose and r == 0, checkpoint_every=checkpoint_every, checkpoint_path=checkpoint_path,
                     march=march, distributed=grp))
