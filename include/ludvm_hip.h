@@ -425,7 +425,7 @@ int ludvm_march_read_probes(ludvm_ctx* ctx, double* u, double* w, size_t rows);
  *   with the last step's offset) -- for checkpoints and the final state.  LUDVM_E_STATE when no tracers are set.
  * Guarantee: with tracers set, `rows`, `state`, `hist`, the resident wake and any probe rows of ludvm_march_run are
  *   bit-identical to a call without them (the tracer kernels read the wake and write only buffers of their own).
- * Limits: one device (not in ludvm_ensemble_run, not sharded); float64 sums only; tracers do not interact with the foil. */
+ * Limits: one device (not sharded; a sweep has ludvm_ensemble_run_traced); float64 sums only; tracers do not interact with the foil. */
 #define LUDVM_MARCH_MAX_TRACERS 262144
 int ludvm_march_set_tracers(ludvm_ctx* ctx, const double* seed_x, const double* seed_z, const long long* release, size_t count,
                             const double* shift_x, size_t shift_rows, const double* cur_x, const double* cur_z,
@@ -513,6 +513,43 @@ int ludvm_ensemble_run_probed(ludvm_ctx* ctx, size_t members, int npan, int ncoe
                               size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
                               long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
                               const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w);
+
+/* ---- passive tracers in an ensemble: one set of seeds, paths for every member ---------------------------------------
+ *
+ * ludvm_ensemble_run_traced is ludvm_ensemble_run_probed (nprobe may be 0) with the tracers of ludvm_march_set_tracers
+ * advected inside the one launch.  The definition is the same: tracer k of member m is held at (seed_x[k] + shift[i],
+ * seed_z[k]) while i < release[k]; in step i >= release[k] it goes from `start` -- that seed if i == release[k], otherwise its
+ * position after step i - 1 -- to start + dt (u, w)_i(start), (u, w)_i being the probes' field of step i of member m; Vatistas
+ * core, no freestream term, float64, forward Euler.
+ *   seed_x, seed_z, release [ntracer]  common to the batch; ntracer <= LUDVM_ENSEMBLE_MAX_TRACERS (a member's workgroup is
+ *                               meant to stay around a second; a solo march takes LUDVM_MARCH_MAX_TRACERS); release >= 1 (a
+ *                               step a member does not have: never released in it)
+ *   tshift_x                    NULL, or one x offset per kinematics row (tshift_rows must equal kin_rows): shift[i] of member
+ *                               m is tshift_x[kin_off + i]
+ *   trec_steps [ntrec]          strictly increasing steps >= 1, common to the batch, whose positions are kept
+ *   tracer_rows (host)          [members][ntrec + 1][2][ntracer] doubles (tracer_doubles = the number given): x row and z row
+ *                               of all tracers after each recorded step (held ones at the seed of that step) and, record
+ *                               ntrec, after the member's last step.  A record the member has no step for stays 0.
+ * Every other argument, output, limit and guarantee is ludvm_ensemble_run_probed's, and those outputs -- the probe rows
+ * included -- are bit-identical to a call without tracers: the tracer phase reads the member's wake and writes only the
+ * member's tracer buffers.  Each tracer sum is formed in an order that depends on ntracer and on the member's own wake size
+ * only, so a member's paths do not depend on the batch; a member differs from ludvm_march_run(LUDVM_PREC_F64) with the same
+ * tracers by summation order only.  ntracer = 0 is ludvm_ensemble_run_probed itself (the tracer arguments are not looked
+ * at).  Nothing is kept on the context.  Checked on the host before anything touches the device (LUDVM_E_ARG): ntracer over
+ * the limit, null arrays, tshift_rows != kin_rows, a seed or offset that is not finite, release < 1, trec_steps not strictly
+ * increasing or < 1, tracer_doubles too small, and members * (ntrec + 1) * 16 * ntracer bytes of records over 1 GiB (the
+ * message gives the size: split the batch).  A sharded context answers LUDVM_E_STATE.
+ * The entry point is an addition to ABI 7: detect it by its symbol. */
+#define LUDVM_ENSEMBLE_MAX_TRACERS 4096
+int ludvm_ensemble_run_traced(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                              const double* tables, const double* kin, size_t kin_rows, const double* init,
+                              const double* free_xzg, size_t free_count, const long long* desc, const long long* snap_steps,
+                              size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
+                              long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
+                              const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w, const double* seed_x,
+                              const double* seed_z, const long long* release, size_t ntracer, const double* tshift_x,
+                              size_t tshift_rows, const long long* trec_steps, size_t ntrec, double* tracer_rows,
+                              size_t tracer_doubles);
 
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 

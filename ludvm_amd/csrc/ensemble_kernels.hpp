@@ -22,6 +22,12 @@
 //                      points of the sweep, shifted by the member's own offset of the step; row `step` of the member's probe
 //                      rows.  Row 0 -- the field of the free vortices -- is written before the first step.  The phase reads
 //                      the slab and writes nothing but the probe rows: ensemble_march<false> does not contain it.
+// With passive tracers (ensemble_traced<PROBES>; the definition of march_tracer_partial / march_tracer_finish), between 2p and 3:
+//   2t. tracers        the same sources -> the start positions of the M tracers of the sweep that are released (seed + the
+//                      member's offset of the step on the release step, the member's own current position after it), then
+//                      start + dt (u, w) to the member's current positions; a copy of all M positions to the member's tracer
+//                      record on the listed steps and on the last one (held tracers: seed + offset).  The phase reads the
+//                      slab and writes nothing but the member's tracer buffers: ensemble_march<...> does not contain it.
 //
 
 // Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
@@ -159,9 +165,73 @@ __device__ __forceinline__ void ens_probe_row(const EnsembleMember& E, const dou
   __syncthreads();
 }
 
-template <bool PROBES>
-__global__ void __launch_bounds__(kBlock)
-ensemble_march(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap) {
+// The tracers of a member (ensemble_traced only), one record per member in a device array of its own indexed by blockIdx.x:
+// EnsembleMember stays what ensemble_march reads.
+struct EnsembleTracers {
+  const double* seed_x; const double* seed_z;   // the M seeds, common to the batch
+  const long long* release;     // M release steps >= 1, common to the batch
+  const long long* tile_min;    // the earliest release step of each tile of kBlock tracers (host-computed: uniform over a workgroup)
+  long long M;
+  const double* shift;          // nt x offsets of the seeds, one per time level of this member, or null
+  double* cur_x; double* cur_z; // M current positions of this member (defined from a tracer's release step on)
+  double* rec;                  // ntrec + 1 records of x[M] | z[M]: the recorded steps, then the last step
+};
+
+// One Euler step of the released tracers: sources [0, ns) of the member's slab -> (u, w) at every released tracer's start
+// position (seed + shift on its release step, its current position after it), start + dt (u, w) to cur_x / cur_z.  Tiles as
+// ens_probe_row's; a held tracer takes part in no pair, a tile whose earliest release lies after `step` is skipped before
+// its first barrier (tile_min: the same for every lane).  A tracer's current position is read before the tile's first
+// barrier and written after its last by the lane that owns it.  All threads of the workgroup call this; it ends in a barrier.
+__device__ __forceinline__ void ens_tracer_step(const EnsembleTracers& T, const double* __restrict__ xs, const double* __restrict__ zs,
+                                                const double* __restrict__ gs, long long ns, long long step, double shift, double dt,
+                                                double vc4, double* lx, double* lz, double* lg, double (*pu)[kBlock / 2],
+                                                double (*pw)[kBlock / 2]) {
+  const int j = threadIdx.x;
+  const int M = (int)T.M;
+  for (int t0 = 0; t0 < M; t0 += kBlock) {
+    if (T.tile_min[t0 / kBlock] > step) continue;
+    const int cnt = M - t0 < kBlock ? M - t0 : kBlock;
+    if (cnt > kBlock / 2) {
+      const long long rel = j < cnt ? T.release[t0 + j] : step + 1;
+      const bool mine = rel <= step;
+      double xp = 0.0, zp = 0.0;
+      if (mine) {
+        if (rel == step) { xp = T.seed_x[t0 + j] + shift; zp = T.seed_z[t0 + j]; }
+        else { xp = T.cur_x[t0 + j]; zp = T.cur_z[t0 + j]; }
+      }
+      double au, aw;
+      ens_pair_sums<false>(xs, zs, gs, ns, xp, zp, vc4, mine, 0, 1, lx, lz, lg, au, aw);
+      if (mine) { T.cur_x[t0 + j] = xp + dt * (au * kInv2PiD); T.cur_z[t0 + j] = zp + dt * (-aw * kInv2PiD); }
+    } else {
+      int slices = kBlock / cnt;
+      if (slices > kEnsSlicesMax) slices = kEnsSlicesMax;
+      const int slice = j / cnt, q = j - slice * cnt;
+      const long long rel = slice < slices ? T.release[t0 + q] : step + 1;
+      const bool mine = rel <= step;
+      double xp = 0.0, zp = 0.0;
+      if (mine) {
+        if (rel == step) { xp = T.seed_x[t0 + q] + shift; zp = T.seed_z[t0 + q]; }
+        else { xp = T.cur_x[t0 + q]; zp = T.cur_z[t0 + q]; }
+      }
+      double au, aw;
+      ens_pair_sums<true>(xs, zs, gs, ns, xp, zp, vc4, mine, slice, slices, lx, lz, lg, au, aw);
+      double su = au * kInv2PiD, sw = -aw * kInv2PiD;
+      if (mine && slice > 0) { pu[slice - 1][q] = su; pw[slice - 1][q] = sw; }
+      __syncthreads();
+      if (mine && slice == 0) {
+        for (int r = 1; r < slices; ++r) { su += pu[r - 1][q]; sw += pw[r - 1][q]; }
+        T.cur_x[t0 + q] = xp + dt * su; T.cur_z[t0 + q] = zp + dt * sw;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// The time loop of one member.  ensemble_march<PROBES> is <PROBES, false>: what it compiled to before there were tracers.
+template <bool PROBES, bool TRACERS>
+__device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps,
+                                               int nsnap, const EnsembleTracers* __restrict__ tracers,
+                                               const long long* __restrict__ trec_steps, int ntrec) {
   __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lz[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lg[kEnsTile + kEnsGroup];
@@ -196,6 +266,7 @@ ensemble_march(const EnsembleMember* __restrict__ members, const long long* __re
   long long n = E.nfree;
   double lesp_crit = E.init[4], sum_tev = 0.0, sum_lev = 0.0;
   int snap_i = 0;
+  [[maybe_unused]] int trec_i = 0;
   __syncthreads();
   if constexpr (PROBES)        // row 0: the field of the free vortices
     ens_probe_row(E, xc, zc, g, E.nfree, E.shift ? E.shift[0] : 0.0, m.vc4, E.pu_rows, E.pw_rows, lx, lz, lg, pu, pw);
@@ -377,6 +448,24 @@ ensemble_march(const EnsembleMember* __restrict__ members, const long long* __re
       ens_probe_row(E, xc, zc, g, n + npan, E.shift ? E.shift[step] : 0.0, m.vc4, E.pu_rows + (size_t)step * (size_t)E.P,
                     E.pw_rows + (size_t)step * (size_t)E.P, lx, lz, lg, pu, pw);
 
+    // ---- 2t. tracers: the same sources at the released tracers, their Euler step, the records ----------------------------
+    if constexpr (TRACERS) {
+      const EnsembleTracers& T = tracers[blockIdx.x];
+      const double tshift = T.shift ? T.shift[step] : 0.0;
+      ens_tracer_step(T, xc, zc, g, n + npan, step, tshift, m.dt, m.vc4, lx, lz, lg, pu, pw);
+      while (trec_i < ntrec && trec_steps[trec_i] < step) ++trec_i;
+      for (int pass = 0; pass < 2; ++pass) {
+        const int r = pass == 0 ? (trec_i < ntrec && trec_steps[trec_i] == step ? trec_i : -1) : (step == nt - 1 ? ntrec : -1);
+        if (r < 0) continue;
+        double* o = T.rec + (size_t)r * 2 * (size_t)T.M;
+        for (long long i = j; i < T.M; i += kBlock) {
+          const bool free_ = T.release[i] <= step;
+          o[i] = free_ ? T.cur_x[i] : T.seed_x[i] + tshift;
+          o[T.M + i] = free_ ? T.cur_z[i] : T.seed_z[i];
+        }
+      }
+    }
+
     // ---- 3. roll-up (:1095-1127) and 4. placement of the coming step (:672-681, :788-800) -------------------------------
     const double* kin_next = step + 1 < nt ? kin + krow : nullptr;
     for (long long t0 = 0; t0 < n; t0 += kBlock) {
@@ -418,6 +507,20 @@ ensemble_march(const EnsembleMember* __restrict__ members, const long long* __re
       if (j == 0) E.rec_n[r] = n;
     }
   }
+}
+
+template <bool PROBES>
+__global__ void __launch_bounds__(kBlock)
+ensemble_march(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap) {
+  ens_member_run<PROBES, false>(members, snap_steps, nsnap, nullptr, nullptr, 0);
+}
+
+// ensemble_march<PROBES> with phase 2t: the launch of ludvm_ensemble_run_traced
+template <bool PROBES>
+__global__ void __launch_bounds__(kBlock)
+ensemble_traced(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap,
+                const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec) {
+  ens_member_run<PROBES, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec);
 }
 
 }  // namespace ludvm

@@ -7,6 +7,8 @@
 #include "march_kernels.hpp"
 #include "ensemble_kernels.hpp"
 
+#include <limits>
+
 extern "C" {
 
 /* ---- device-resident time march ------------------------------------------------------------- */
@@ -634,13 +636,23 @@ int ludvm_ensemble_limits(ludvm_ctx* c, long long* limits3) {
 
 namespace {
 
-// ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at) and ludvm_ensemble_run_probed
+// The tracer arguments of ludvm_ensemble_run_traced (count = 0: none, nothing else is looked at)
+struct EnsembleTracerArgs {
+  const double* seed_x = nullptr; const double* seed_z = nullptr; const long long* release = nullptr;
+  size_t count = 0;
+  const double* shift_x = nullptr; size_t shift_rows = 0;
+  const long long* rec_steps = nullptr; size_t nrec = 0;
+  double* rows = nullptr; size_t doubles = 0;
+};
+
+// ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at), ludvm_ensemble_run_probed and, with tracers,
+// ludvm_ensemble_run_traced
 int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
                       const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
-                      double* probe_w) {
+                      double* probe_w, const EnsembleTracerArgs& tr = EnsembleTracerArgs()) {
   if (!c) return LUDVM_E_ARG;
   if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
     return fail(c, LUDVM_E_STATE, "ensemble: the context is sharded; members are independent -- split the list per device");
@@ -658,6 +670,29 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
       if (!std::isfinite(probe_x[k]) || !std::isfinite(probe_z[k])) return fail(c, LUDVM_E_ARG, "ensemble: probe positions must be finite");
     for (size_t k = 0; shift_x && k < shift_rows; ++k)
       if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "ensemble: probe offsets must be finite");
+  }
+  const size_t M = tr.count, ntrec = tr.nrec;
+  if (M) {
+    if (M > LUDVM_ENSEMBLE_MAX_TRACERS)
+      return fail(c, LUDVM_E_ARG, "ensemble: at most " + std::to_string(LUDVM_ENSEMBLE_MAX_TRACERS) + " tracers");
+    if (!tr.seed_x || !tr.seed_z || !tr.release || !tr.rows || (ntrec && !tr.rec_steps)) return fail(c, LUDVM_E_ARG, "null array");
+    if (tr.shift_x && tr.shift_rows != kin_rows) return fail(c, LUDVM_E_ARG, "ensemble: tracer offsets must be one per kinematics row");
+    for (size_t k = 0; k < M; ++k) {
+      if (!std::isfinite(tr.seed_x[k]) || !std::isfinite(tr.seed_z[k])) return fail(c, LUDVM_E_ARG, "ensemble: tracer seeds must be finite");
+      if (tr.release[k] < 1) return fail(c, LUDVM_E_ARG, "ensemble: tracer release steps must be >= 1");
+    }
+    for (size_t k = 0; tr.shift_x && k < tr.shift_rows; ++k)
+      if (!std::isfinite(tr.shift_x[k])) return fail(c, LUDVM_E_ARG, "ensemble: tracer offsets must be finite");
+    for (size_t k = 0; k < ntrec; ++k)
+      if (tr.rec_steps[k] < 1 || (k && tr.rec_steps[k] <= tr.rec_steps[k - 1]))
+        return fail(c, LUDVM_E_ARG, "ensemble: tracer record steps must be >= 1 and strictly increasing");
+    // members x (ntrec + 1) records of 2 x 8 x M bytes: at most 1 GiB (each factor is checked before it is multiplied in)
+    const size_t most = (((size_t)1 << 30) / 16) / M;           // records of all members
+    if (ntrec + 1 > most || members > most / (ntrec + 1))
+      return fail(c, LUDVM_E_ARG, "ensemble: " + std::to_string(16.0 * (double)members * (double)(ntrec + 1) * (double)M / (1 << 20)) +
+                                      " MiB of tracer records (2 x 8 x " + std::to_string(members) + " members x " +
+                                      std::to_string(ntrec + 1) + " records x " + std::to_string(M) + " tracers) are over 1 GiB; split the batch");
+    if (tr.doubles < members * (ntrec + 1) * 2 * M) return fail(c, LUDVM_E_ARG, "ensemble: tracer records outside the array");
   }
   if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
     return fail(c, LUDVM_E_ARG, "null array");
@@ -694,7 +729,7 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     const double* sc = scalars + 12 * mi;
     if (sc[8] != 0.0 && !(sc[9] > 0.0 && sc[10] >= 1.0 && sc[11] > 0.0))
       return fail(c, LUDVM_E_ARG, who + "'Ramesh' needs maxerror > 0, maxiter >= 1, epsilon > 0");
-    work_doubles += 5 * (cap + P);
+    work_doubles += 5 * (cap + P) + 2 * M;
   }
 
   HIPCHK(c, hipSetDevice(c->device));
@@ -704,12 +739,20 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   const size_t in_snap = Arena::need(nsnap + 1, 8), in_mem = Arena::need(members, sizeof(EnsembleMember));
   // (probes: points and offsets behind the inputs, rows behind the outputs)
   const size_t in_probe = nprobe ? 2 * Arena::need(nprobe, 8) + (shift_x ? Arena::need(shift_rows, 8) : 0) : 0;
-  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe));
+  // (tracers: seeds, release steps, tile minima, offsets, record steps and the members' tracer records behind those;
+  // current positions in the work memory, records behind the outputs)
+  const size_t ttiles = (M + kBlock - 1) / kBlock;
+  const size_t in_tracer = M ? 3 * Arena::need(M, 8) + Arena::need(ttiles, 8) + (tr.shift_x ? Arena::need(tr.shift_rows, 8) : 0) +
+                                   Arena::need(ntrec + 1, 8) + Arena::need(members, sizeof(EnsembleTracers))
+                             : 0;
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer));
   CHK(ensure(c, c->ens_work, work_doubles * 8));
   const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
   const size_t out_n = Arena::need(members * nrec, 8);
   const size_t out_probe = nprobe ? 2 * Arena::need(kin_rows * nprobe, 8) : 0;
-  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe));
+  const size_t trec_doubles = members * (ntrec + 1) * 2 * M;
+  const size_t out_tracer = M ? Arena::need(trec_doubles, 8) : 0;
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer));
   Arena in(c->ens_in.p), out(c->ens_out.p);
   double* d_tab = in.take<double>(members * tab_doubles);
   double* d_kin = in.take<double>(kin_rows * krow);
@@ -728,8 +771,24 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     d_pu = out.take<double>(kin_rows * nprobe);
     d_pw = out.take<double>(kin_rows * nprobe);
   }
+  double *d_sx = nullptr, *d_sz = nullptr, *d_tshift = nullptr, *d_trows = nullptr;
+  long long *d_rel = nullptr, *d_tmin = nullptr, *d_trec = nullptr;
+  EnsembleTracers* d_tr = nullptr;
+  if (M) {
+    d_sx = in.take<double>(M);
+    d_sz = in.take<double>(M);
+    d_rel = in.take<long long>(M);
+    d_tmin = in.take<long long>(ttiles);
+    if (tr.shift_x) d_tshift = in.take<double>(tr.shift_rows);
+    d_trec = in.take<long long>(ntrec + 1);
+    d_tr = in.take<EnsembleTracers>(members);
+    d_trows = out.take<double>(trec_doubles);
+  }
 
   std::vector<EnsembleMember> hm(members);
+  std::vector<EnsembleTracers> ht(M ? members : 0);
+  std::vector<long long> tmin(ttiles, std::numeric_limits<long long>::max());     // earliest release step of each tile
+  for (size_t k = 0; k < M; ++k) tmin[k / kBlock] = std::min(tmin[k / kBlock], tr.release[k]);
   double* work = static_cast<double*>(c->ens_work.p);
   for (size_t mi = 0; mi < members; ++mi) {
     const long long* d = desc + mi * LUDVM_ENSEMBLE_DESC;
@@ -753,6 +812,14 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     e.free_x = d_free + 3 * (size_t)d[3]; e.free_z = e.free_x + d[2]; e.free_g = e.free_z + d[2];
     e.xa = work; e.za = work + slab; e.xb = work + 2 * slab; e.zb = work + 3 * slab; e.g = work + 4 * slab;
     work += 5 * slab;
+    if (M) {
+      EnsembleTracers& t = ht[mi];
+      t.seed_x = d_sx; t.seed_z = d_sz; t.release = d_rel; t.tile_min = d_tmin; t.M = (long long)M;
+      t.shift = d_tshift ? d_tshift + (size_t)d[1] : nullptr;
+      t.cur_x = work; t.cur_z = work + M;
+      work += 2 * M;
+      t.rec = d_trows + mi * (ntrec + 1) * 2 * M;
+    }
     e.rows = d_rows + (size_t)d[4] * row_doubles;
     e.rec = d_wakes + (size_t)d[5];
     e.rec_n = d_n + mi * nrec;
@@ -775,8 +842,25 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     HIPCHK(c, hipMemsetAsync(d_pu, 0, kin_rows * nprobe * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(d_pw, 0, kin_rows * nprobe * 8, c->stream));
   }
+  if (M) {
+    HIPCHK(c, hipMemcpyAsync(d_sx, tr.seed_x, M * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sz, tr.seed_z, M * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_rel, tr.release, M * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tmin, tmin.data(), ttiles * 8, hipMemcpyHostToDevice, c->stream));
+    if (tr.shift_x) HIPCHK(c, hipMemcpyAsync(d_tshift, tr.shift_x, tr.shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+    if (ntrec) HIPCHK(c, hipMemcpyAsync(d_trec, tr.rec_steps, ntrec * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tr, ht.data(), members * sizeof(EnsembleTracers), hipMemcpyHostToDevice, c->stream));
+    // (a record whose step a member does not have stays 0)
+    HIPCHK(c, hipMemsetAsync(d_trows, 0, trec_doubles * 8, c->stream));
+  }
   // ONE launch: a workgroup per member, all of its time steps inside
-  if (nprobe)
+  if (M && nprobe)
+    hipLaunchKernelGGL(ensemble_traced<true>, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
+                       (const long long*)d_snap, (int)nsnap, (const EnsembleTracers*)d_tr, (const long long*)d_trec, (int)ntrec);
+  else if (M)
+    hipLaunchKernelGGL(ensemble_traced<false>, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
+                       (const long long*)d_snap, (int)nsnap, (const EnsembleTracers*)d_tr, (const long long*)d_trec, (int)ntrec);
+  else if (nprobe)
     hipLaunchKernelGGL(ensemble_march<true>, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
                        (const long long*)d_snap, (int)nsnap);
   else
@@ -790,7 +874,8 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     HIPCHK(c, hipMemcpyAsync(probe_u, d_pu, kin_rows * nprobe * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(probe_w, d_pw, kin_rows * nprobe * 8, hipMemcpyDeviceToHost, c->stream));
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm lives on this frame)
+  if (M) HIPCHK(c, hipMemcpyAsync(tr.rows, d_trows, trec_doubles * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht and tmin live on this frame)
   return LUDVM_OK;
 }
 
@@ -816,6 +901,24 @@ int ludvm_ensemble_run_probed(ludvm_ctx* c, size_t members, int npan, int ncoef,
   return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
                            snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
                            shift_rows, probe_u, probe_w);
+}
+
+int ludvm_ensemble_run_traced(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                              const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                              size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                              size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
+                              const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
+                              double* probe_w, const double* seed_x, const double* seed_z, const long long* release, size_t ntracer,
+                              const double* tshift_x, size_t tshift_rows, const long long* trec_steps, size_t ntrec,
+                              double* tracer_rows, size_t tracer_doubles) {
+  EnsembleTracerArgs tr;
+  tr.seed_x = seed_x; tr.seed_z = seed_z; tr.release = release; tr.count = ntracer;
+  tr.shift_x = tshift_x; tr.shift_rows = tshift_rows;
+  tr.rec_steps = trec_steps; tr.nrec = ntrec;
+  tr.rows = tracer_rows; tr.doubles = tracer_doubles;
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
+                           shift_rows, probe_u, probe_w, tr);
 }
 
 }  // extern "C"

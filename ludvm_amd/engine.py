@@ -492,7 +492,33 @@ class Engine:
         sh = None if shift_x is None else _f64(shift_x)
         return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, (px, pz, sh))
 
-    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes):
+    def ensemble_run_traced(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=(), *, seed_x, seed_z,
+                            release, shift_x=None, record_steps=(), probe_x=None, probe_z=None, probe_shift_x=None):
+        """`ensemble_run` with passive tracers advected inside the launch (ludvm_ensemble_run_traced): seed_x, seed_z [M] and
+        release [M] (steps >= 1) are common to the batch; shift_x: None, or one x offset per row of `kin` -- in step i of a
+        member the seed of tracer k sits at (seed_x[k] + shift_x[kin_off + i], seed_z[k]); record_steps: strictly increasing
+        steps >= 1 whose positions are kept.  probe_x, probe_z (and probe_shift_x): the probes of `ensemble_run_probed`, in the
+        same launch.
+        -> (rows, wakes, wake_n, tracer_rows), plus (probe_u, probe_w) when probes are given; tracer_rows
+        [members, len(record_steps) + 1, 2, M]: the positions after each recorded step and, last, after the member's final
+        step (a recorded step the member does not have: zeros)."""
+        if not hasattr(self._lib, "ludvm_ensemble_run_traced"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_ensemble_run_traced")
+        sx, sz = _f64(seed_x), _f64(seed_z)
+        rel = np.ascontiguousarray(release, dtype=np.int64).reshape(-1)
+        if len(sx) != len(sz) or len(rel) != len(sx):
+            raise ValueError("ensemble_run_traced: seed_x, seed_z and release must have the same length")
+        sh = None if shift_x is None else _f64(shift_x)
+        rec = np.ascontiguousarray(list(record_steps), dtype=np.int64).reshape(-1)
+        probes = None
+        if probe_x is not None or probe_z is not None:
+            px, pz = _f64(probe_x), _f64(probe_z)
+            if len(px) != len(pz):
+                raise ValueError("ensemble_run_traced: probe_x and probe_z must have the same length")
+            probes = (px, pz, None if probe_shift_x is None else _f64(probe_shift_x))
+        return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, (sx, sz, rel, sh, rec))
+
+    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None):
         npan, ncoef = int(npan), int(ncoef)
         desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
         members = desc.shape[0]
@@ -513,6 +539,16 @@ class Engine:
         args = (self._ctx, members, npan, ncoef, _pd(sc), len(sc), _pd(tb), _pd(kin), kin.shape[0], _pd(ini), _pd(fr), len(fr) // 3,
                 desc.ctypes.data_as(pll), snaps.ctypes.data_as(pll), len(snaps), _pd(rows), rows_count, _pd(wakes), wake_doubles,
                 wake_n.ctypes.data_as(pll))
+        if tracers is not None:
+            sx, sz, rel, tsh, rec = tracers
+            px, pz, sh = probes if probes is not None else (np.empty(0), np.empty(0), None)
+            pu, pw = np.empty([kin.shape[0], len(px)]), np.empty([kin.shape[0], len(px)])
+            trows = np.zeros([members, len(rec) + 1, 2, len(sx)])
+            self._check(self._lib.ludvm_ensemble_run_traced(
+                *args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh), _pd(pu), _pd(pw), _pd(sx), _pd(sz),
+                rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),
+                _pd(trows), trows.size))
+            return (rows, wakes, wake_n, trows) if probes is None else (rows, wakes, wake_n, trows, pu, pw)
         if probes is None:
             self._check(self._lib.ludvm_ensemble_run(*args))
             return rows, wakes, wake_n

@@ -1,5 +1,6 @@
 """`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run; with velocity probes
-Engine.ensemble_run_probed / ludvm_ensemble_run_probed).
+Engine.ensemble_run_probed / ludvm_ensemble_run_probed; with passive tracers Engine.ensemble_run_traced /
+ludvm_ensemble_run_traced).
 
 A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
 'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
@@ -17,7 +18,7 @@ are the ones a solo march uploads (LUDVM._march_inputs) and its results are stor
 import numpy as np
 
 from . import _ffi
-from .ludvm import LUDVM
+from .ludvm import LUDVM, SparseHistory
 
 __all__ = ["sweep"]
 
@@ -29,7 +30,11 @@ _REFUSED = {
     "devices": (None, "a sweep runs on one GPU (members are independent: split the list per device)"),
     "march": (True, "the members of a sweep are marched on the device"),
     "run": (True, "the members of a sweep are run"),
-    "tracers": (None, "a sweep has no tracers (a member can be run on its own: LUDVM(..., tracers=...))"),
+    "tracers": (None, "the tracers of a sweep are common to it: sweep(cases, particles=[2, M], particle_release=..., "
+                      "particle_frame=..., particle_steps=...) (or run the member on its own: LUDVM(..., tracers=...))"),
+    "tracer_release": (None, "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_release=...)"),
+    "tracer_steps": (None, "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_steps=...)"),
+    "tracer_frame": ("lab", "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_frame=...)"),
 }
 
 
@@ -48,7 +53,8 @@ class _RecordedWakes:
 def _check_case(idx, kw, first):
     """Everything that can be refused from the keywords alone (no device, no engine call)."""
     who = f"sweep: member {idx}: "
-    for key in ("engine", "device", "snapshot_steps", "verbose", "probes", "probe_frame"):
+    for key in ("engine", "device", "snapshot_steps", "verbose", "probes", "probe_frame", "particles", "particle_release",
+                "particle_frame", "particle_steps"):
         if key in kw:
             raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
     for key, (fine, why) in _REFUSED.items():
@@ -98,7 +104,45 @@ def _check_sweep_probes(probes, probe_frame, merged):
     return xz
 
 
-def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", verbose=False, cls=LUDVM, **common):
+def _time_levels(kw):
+    return len(np.arange(kw.get("t0", 0), kw.get("tf", 12) + kw.get("dt", 1.5e-2), kw.get("dt", 1.5e-2)))
+
+
+def _check_sweep_particles(particles, particle_release, particle_frame, particle_steps, snapshot_steps, merged):
+    """The sweep's tracers -> (seeds [2, M], release steps [M], recorded steps >= 1 or None for the default), or None without
+    `particles`; refused from the keywords alone like a member's."""
+    if particles is None:
+        if particle_frame not in ("lab", "tunnel"):
+            raise ValueError("particle_frame must be 'lab' or 'tunnel'")
+        if particle_release is not None or particle_steps is not None:
+            raise ValueError("particle_release / particle_steps need `particles`")
+        return None
+    try:
+        xz, rel, steps = LUDVM._check_tracers(particles, particle_release, particle_frame, particle_steps)
+    except ValueError as e:
+        raise ValueError("sweep: particles: " + str(e).replace("tracer_", "particle_").replace("tracers", "particles")) from e
+    M = xz.shape[1]
+    if M > _ffi.ENSEMBLE_MAX_TRACERS:
+        raise ValueError(f"sweep: particles: at most {_ffi.ENSEMBLE_MAX_TRACERS} tracers in a sweep (got {M}); a member can be run on "
+                         f"its own with up to {_ffi.MARCH_MAX_TRACERS}: LUDVM(..., tracers=...)")
+    last = max(_time_levels(kw) for kw in merged) - 1
+    if steps is None:
+        rec = None
+        nrec = len({int(s) for s in snapshot_steps if 1 <= int(s) <= last})
+    else:
+        if steps and (steps[0] < 1 or steps[-1] > last):
+            raise ValueError(f"sweep: particle_steps must lie in [1, {last}] (the longest member's last step)")
+        rec, nrec = steps, len(steps)
+    size = len(merged) * (nrec + 1) * 2 * 8 * M
+    if size > _ffi.ENSEMBLE_TRACER_BYTES:
+        raise ValueError(f"sweep: particles: {len(merged)} members x {nrec + 1} records x {M} tracers are {size} bytes "
+                         f"({size / 2**30:.2f} GiB) of tracer records, over the {_ffi.ENSEMBLE_TRACER_BYTES >> 30} GiB one launch "
+                         "returns: split the case list or record fewer steps")
+    return xz, rel, rec
+
+
+def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", particles=None, particle_release=None,
+          particle_frame="lab", particle_steps=None, verbose=False, cls=LUDVM, **common):
     """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
     return the list of LUDVM objects, in order.  Each carries what a solo
     `LUDVM(**kw, precision='f64', history='sparse', snapshot_steps=snapshot_steps)` run carries: Cl, Cd, Cm, Cn, Cs, Ct, Fn, Fs, L,
@@ -112,15 +156,29 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     probe_frame='tunnel' measures x from each member's own pivot (x + xpiv[step]: xpiv depends on the member's Uinf and dt).
     Everything else a member returns is bit-identical to the sweep without probes.
 
+    particles: None, or seeds [2, M] (1 <= M <= 4096) of passive tracers common to the sweep, with particle_release (None: all 1,
+    or one release step >= 1 per tracer), particle_frame ('lab' | 'tunnel') and particle_steps -- the meaning of LUDVM(...,
+    tracers=, tracer_release=, tracer_frame=, tracer_steps=), under sweep-level names because `tracers` itself stays refused in a
+    sweep.  Seeds, release steps and recorded steps are common; particle_frame='tunnel' adds each member's own xpiv[step] to the
+    seeds.  Every member is advected inside the one launch and carries the attributes of a solo run with tracers:
+    `tracer_path` (a SparseHistory step -> [2, M]; row 0, the seeds, always there), `tracer_last`, `tracer_xz`,
+    `tracer_release`, `tracer_frame`, `tracer_released(step)`.  particle_steps=None records snapshot_steps and each member's
+    last step; otherwise every entry lies in [1, the largest nt - 1 of the members], and a member shorter than a listed step
+    has no row for it (`tracer_last` is its last step either way).  `probes` and `particles` compose in one launch; everything else a
+    member returns, its probe rows included, is bit-identical to the sweep without particles.
+
     Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
-    history='full', checkpoint_*, distributed, devices, tracers, march=False, run=False, an engine without ensemble_run; `probes` or
+    history='full', checkpoint_*, distributed, devices, march=False, run=False, an engine without ensemble_run; `probes` or
     `probe_frame` inside a member's dict (they belong to the sweep), more than 1024 probes, points that are not finite, a
     probe_frame other than 'lab' / 'tunnel', an engine without ensemble_run_probed, and probe rows (16 bytes x all members' time
-    levels x P) over 1 GiB: split the case list.
+    levels x P) over 1 GiB: split the case list; `particles` / `particle_*` inside a member's dict, `tracers` / `tracer_*`
+    anywhere (use `particles=`), more than 4096 particles, seeds that are not finite, release steps < 1 or not one integer per
+    tracer, a particle_frame other than 'lab' / 'tunnel', particle_steps outside [1, the largest nt - 1], an engine without
+    ensemble_run_traced, and tracer records (16 bytes x members x (recorded steps + 1) x M) over 1 GiB.
 
-    Out of scope: per-member probe sets, tracers, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe or seed sets, tracers of a sweep on several GPUs, fp32 tracer sums, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     cases = list(cases)
     if not cases:
@@ -133,6 +191,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         first = first or dims
         merged.append(kw)
     probe_xz = _check_sweep_probes(probes, probe_frame, merged)
+    traced = _check_sweep_particles(particles, particle_release, particle_frame, particle_steps, snapshot_steps, merged)
     if engine is None:
         from .engine import Engine
         engine = Engine(device)
@@ -140,6 +199,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         raise ValueError("sweep: this engine has no ensemble_run")
     if probe_xz is not None and not hasattr(engine, "ensemble_run_probed"):
         raise ValueError("sweep: probes: this engine has no ensemble_run_probed")
+    if traced is not None and not hasattr(engine, "ensemble_run_traced"):
+        raise ValueError("sweep: particles: this engine has no ensemble_run_traced")
     snaps = sorted({int(s) for s in snapshot_steps})
     dev_snaps = [s for s in snaps if s >= 1]
     if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
@@ -170,6 +231,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         fr.append(np.concatenate([free0[0], free0[1], np.asarray(sim.circulation_freevort, dtype=float).reshape(-1)]))
         if probe_xz is not None:
             sim.probe_xz, sim.probe_frame = probe_xz.copy(), probe_frame
+        if traced is not None:
+            sim.tracer_xz, sim.tracer_release, sim.tracer_frame = traced[0].copy(), traced[1].copy(), particle_frame
+        if probe_xz is not None or traced is not None:
             shift.append(np.asarray(sim.xpiv, dtype=float))
         nt, nf = sim.nt, S.nf
         desc[idx] = [nt, kin_off, nf, free_off, row_off, wake_off]
@@ -181,7 +245,17 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
 
     # device: one launch
     packed = (npan, ncoef, np.stack(sc), np.stack(tb), np.concatenate(kn), np.stack(ini), np.concatenate(fr), desc, dev_snaps)
-    if probe_xz is None:
+    if traced is not None:
+        # recorded steps: the listed ones, or snapshot_steps (each member's last step is always the final record)
+        trec = [s for s in (dev_snaps if traced[2] is None else traced[2]) if 1 <= s <= max(sim.nt for sim in sims) - 1]
+        targs = dict(seed_x=traced[0][0], seed_z=traced[0][1], release=traced[1], record_steps=trec,
+                  shift_x=np.concatenate(shift) if particle_frame == "tunnel" else None)
+        if probe_xz is not None:
+            targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
+            rows, wakes, wake_n, trows, pu, pw = engine.ensemble_run_traced(*packed, **targs)
+        else:
+            rows, wakes, wake_n, trows = engine.ensemble_run_traced(*packed, **targs)
+    elif probe_xz is None:
         rows, wakes, wake_n = engine.ensemble_run(*packed)
     else:
         rows, wakes, wake_n, pu, pw = engine.ensemble_run_probed(
@@ -192,6 +266,15 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         nt, k0, nf, _, r0, w0 = (int(v) for v in desc[idx])
         if probe_xz is not None:
             sim.probe_u, sim.probe_w = pu[k0:k0 + nt].copy(), pw[k0:k0 + nt].copy()
+        if traced is not None:
+            sim.tracer_path = SparseHistory(nt)
+            sim.tracer_path.store(0, sim._tracer_seeds(0))
+            for r, step in enumerate(trec):
+                if step <= nt - 1:
+                    sim.tracer_path.store(step, trows[idx, r].copy())
+            sim.tracer_last = trows[idx, len(trec)].copy()
+            if traced[2] is None:               # (the solo rule of a sparse history: snapshot_steps and the last step)
+                sim.tracer_path.store(nt - 1, sim.tracer_last.copy())
         cap = nf + 2 * (nt - 1)
         R = rows[r0:r0 + nt - 1]
         hist = _RecordedWakes()

@@ -117,8 +117,9 @@ class LUDVM:
                  and needs no dense history.  Results: `tracer_path`, a SparseHistory step -> [2, M] (row 0, the seeds,
                  always present), `tracer_last` [2, M] (positions after the final step), `tracer_xz`, `tracer_release`,
                  `tracer_frame` as given, `tracer_released(step)` -> bool [M].  Every other result is unchanged, bit for
-                 bit.  Out of scope: tracers in a sweep, on several GPUs, fp32 tracer sums, higher-order time integration
-                 (the reference's wake is forward Euler, and the tracers follow it), tracers that interact with the foil
+                 bit.  A sweep takes them as sweep(..., particles=).  Out of scope: tracers on several GPUs, fp32 tracer
+                 sums, higher-order time integration (the reference's wake is forward Euler, and the tracers follow
+                 it), tracers that interact with the foil
       tracer_release  None (all 1), or one integer release step >= 1 per tracer (a step >= nt: never released)
       tracer_frame  'lab' (default): seeds fixed in the lab frame; 'tunnel': a held tracer rides with the pivot -- its seed
                  at step i is (x + xpiv[i], z) -- and is released into the lab frame from there
