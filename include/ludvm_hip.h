@@ -433,6 +433,40 @@ int ludvm_march_set_tracers(ludvm_ctx* ctx, const double* seed_x, const double* 
 int ludvm_march_read_tracers(ludvm_ctx* ctx, double* x, double* z, size_t rows_cap, long long* steps_out, size_t* nrows_out);
 int ludvm_march_tracer_state(ludvm_ctx* ctx, double* x, double* z);
 
+/* ---- wake survey: running field moments inside the march (an addition to ABI 7: detect it by symbol) -----------
+ *
+ * The time-averaged wake on a survey grid without a time series: for survey point p, (u, w)_i(p) is EXACTLY the probes'
+ * field above -- the reference's  induced_velocity(circulation_wake, xw, zw, p) + induced_velocity(circulation_foil, xa,
+ * za, p)  of LUDVM.py:1095-1106 with xp, zp = p: the wake before the Euler update of step i with the vortices shed in step i
+ * at their placement, plus the bound vortices of step i at airfoil_gamma_points[i]; Vatistas core, no freestream term,
+ * float64 whatever the roll-up's precision.  The sampled steps are W = { i : first <= i < stop, (i - first) % every == 0 }
+ * (stop is clipped to kin_rows).  In step i of W point k sits at (x[k] + shift_x[i], z[k]) (shift 0 without shift_x), and the
+ * device adds to five raw float64 sums per point, sums[0..4][k] = sum u, sum w, sum u^2, sum w^2, sum u w; `samples` counts
+ * the steps of W run so far.  Each point's sums are formed in step order by one lane, the source splits of a step are combined
+ * in split order, no atomics; the splits depend on the point count and on the step's anchor-derived bound of the wake size
+ * only: the sums repeat bit for bit, however a run is cut into ludvm_march_run calls.  Storage does not depend on the number
+ * of steps; a step outside W launches nothing.
+ *
+ * ludvm_march_set_survey: valid after ludvm_march_setup (LUDVM_E_STATE otherwise, and on a sharded context);
+ *   count <= LUDVM_MARCH_MAX_SURVEY; count = 0 removes the survey.  shift_x: NULL, or one x offset per kinematics row
+ *   (shift_rows must equal ludvm_march_setup's kin_rows).  first >= 1, every >= 1.  sums: NULL (start from zero, samples is
+ *   ignored), or [5][count] with samples >= 0 -- what ludvm_march_read_survey returned when a run is continued.  Everything is
+ *   validated (finite values included) before anything is changed: a call refused with LUDVM_E_ARG leaves the survey that was
+ *   set, and its sums, as they were.  A call that passes validation and then fails in the runtime (LUDVM_E_HIP,
+ *   LUDVM_E_NOMEM: the buffers are replaced) leaves the context WITHOUT a survey.  ludvm_march_setup forgets any survey.  A
+ *   ludvm_march_run call that fails leaves the sums undefined: set them again.
+ * ludvm_march_read_survey: sums[5][count] and *samples as they stand, at any time after ludvm_march_set_survey (samples may be
+ *   0).  LUDVM_E_STATE when no survey is set.
+ * Guarantee: with a survey set, `rows`, `state`, `hist`, the resident wake, any probe rows and any tracer positions of
+ *   ludvm_march_run are bit-identical to a call without it (the survey kernels read the wake and write only buffers of their
+ *   own); a call without a survey enqueues exactly what it enqueued before.
+ * Limits: one device (not in ludvm_ensemble_run, not sharded); float64 sums only; no freestream term. */
+#define LUDVM_MARCH_MAX_SURVEY 1048576
+int ludvm_march_set_survey(ludvm_ctx* ctx, const double* x, const double* z, size_t count, const double* shift_x,
+                           size_t shift_rows, long long first, long long stop, long long every, const double* sums,
+                           long long samples);
+int ludvm_march_read_survey(ludvm_ctx* ctx, double* sums, long long* samples);
+
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *
  * A parameter sweep (LESPcrit, k, alpha_max, dt, a gust vortex, 'Faure' / 'Ramesh') is `members` independent simulations,

@@ -33,6 +33,7 @@ ENSEMBLE_MAX_TRACERS = 4096    # LUDVM_ENSEMBLE_MAX_TRACERS
 ENSEMBLE_TRACER_BYTES = 1 << 30  # most bytes of tracer records (members * (recorded steps + 1) * 2 * 8 * tracers) one ludvm_ensemble_run_traced call returns
 MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
 MARCH_MAX_TRACERS = 262144  # LUDVM_MARCH_MAX_TRACERS
+MARCH_MAX_SURVEY = 1048576  # LUDVM_MARCH_MAX_SURVEY
 SYM_SCALE_BYTES = 32
 
 _pd, _pf = POINTER(c_double), POINTER(c_float)
@@ -93,6 +94,8 @@ SIGNATURES = {
                                 c_size_t],
     "ludvm_march_read_tracers": [c_void_p, _pd, _pd, c_size_t, POINTER(c_longlong), POINTER(c_size_t)],
     "ludvm_march_tracer_state": [c_void_p, _pd, _pd],
+    "ludvm_march_set_survey": [c_void_p, _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_longlong],
+    "ludvm_march_read_survey": [c_void_p, _pd, POINTER(c_longlong)],
     "ludvm_ensemble_limits": [c_void_p, POINTER(c_longlong)],
     "ludvm_ensemble_run": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
                            POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
@@ -123,7 +126,7 @@ SIGNATURES = {
 
 # added to ABI 7 without a new version number: a library of ABI 7 built before them is detected by the missing symbol
 ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm_march_read_tracers", "ludvm_march_tracer_state",
-                  "ludvm_ensemble_run_traced")
+                  "ludvm_ensemble_run_traced", "ludvm_march_set_survey", "ludvm_march_read_survey")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -122,6 +122,13 @@ struct ludvm_ctx {
   bool tracer_ran = false;                     // a ludvm_march_run call has succeeded since the tracers were set
   std::vector<long long> tracer_record;        // steps whose rows are recorded, ascending
   std::vector<long long> tracer_rows;          // the recorded steps of the last ludvm_march_run call
+  // wake survey of the march (ludvm_march_set_survey): points x[K] | z[K], the per-step x offsets, the five raw sums
+  // [5][K], the partial slabs of one sampled step -- buffers of the survey's own, like the probes' and the tracers'
+  Buf survey_xz, survey_shift, survey_sums, survey_part;
+  size_t survey_count = 0;                     // K (0: no survey)
+  bool survey_shifted = false;
+  long long survey_first = 1, survey_stop = 0, survey_every = 1;   // sampled steps: first <= i < stop, (i - first) % every == 0
+  long long survey_samples = 0;                // sampled steps the sums hold
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

@@ -23,6 +23,8 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->tracer_ran = false;
   c->tracer_record.clear();
   c->tracer_rows.clear();
+  c->survey_count = 0;      // ... and its survey (ludvm_march_set_survey)
+  c->survey_samples = 0;
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -211,9 +213,112 @@ int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   return LUDVM_OK;
 }
 
+// Launch rule of the survey kernels: tracer_plan's form.  K points in tiles of kSurveyTile (256 lanes x kSurveyPerLane); the
+// sources -- at most ns_ub = n_ub + nfoil, n_ub the step's anchor-derived bound of the wake size after its solve -- in
+// `nsplit` splits of `chunk` sources, a multiple of the 256-source LDS tile, chosen so that tiles x splits comes to about 1024
+// workgroups, with at most 64 splits (the finisher adds them one after the other).  A function of K and n_ub alone: the
+// summation order of a step does not depend on where the calls of a run begin.
+struct SurveyPlan { long long ttiles, k_pad, chunk; int nsplit; };
+constexpr long long kSurveyGroups = 1024, kSurveyMaxSplit = 64;
+long long survey_want(long long ttiles) { return std::min(kSurveyMaxSplit, std::max<long long>(1, kSurveyGroups / ttiles)); }
+SurveyPlan survey_plan(size_t count, long long ns_ub) {
+  SurveyPlan p;
+  p.ttiles = ((long long)count + kSurveyTile - 1) / kSurveyTile;
+  p.k_pad = p.ttiles * kSurveyTile;
+  const long long want = survey_want(p.ttiles);
+  ns_ub = std::max<long long>(ns_ub, 1);
+  p.chunk = std::max<long long>(kSurveySrcTile, ((ns_ub + want - 1) / want + kSurveySrcTile - 1) / kSurveySrcTile * kSurveySrcTile);
+  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
+  return p;
+}
+// the slab of any step: nsplit <= survey_want(ttiles) whatever the wake size (at most 16 MiB)
+size_t survey_slab_bytes(size_t count) {
+  const SurveyPlan p = survey_plan(count, 1);
+  return (size_t)survey_want(p.ttiles) * 2 * (size_t)p.k_pad * 8;
+}
+
+// is time step s one of the survey's sampled steps?
+bool survey_samples_step(const ludvm_ctx* c, long long s) {
+  return c->survey_count != 0 && s >= c->survey_first && s < c->survey_stop && (s - c->survey_first) % c->survey_every == 0;
+}
+
+// The survey's sample of time step s: enqueued where the probes and the tracers are, behind march_solve of step s on the
+// stream that ran it (and behind their kernels when they are set), so before the roll-up's finisher moves anything.  The
+// slab and the sums are the survey's own buffers, touched only by these two kernels in stream order.  Reads the wake, writes
+// nothing of it: rows, state, hist, the resident wake, the probe rows and the tracer paths keep their bits.
+int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s) {
+  const MarchSetup& m = c->msetup;
+  const size_t K = c->survey_count;
+  const SurveyPlan p = survey_plan(K, n_ub + (long long)m.npan);
+  const double* pxz = static_cast<const double*>(c->survey_xz.p);
+  const double* shift = c->survey_shifted ? static_cast<const double*>(c->survey_shift.p) + s : nullptr;
+  double* slab = static_cast<double*>(c->survey_part.p);
+  hipLaunchKernelGGL(march_survey_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
+                     (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                     static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad, p.nsplit,
+                     (long long)K, static_cast<double*>(c->survey_sums.p));
+  HIPCHK(c, hipGetLastError());
+  return LUDVM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_t count, const double* shift_x, size_t shift_rows,
+                           long long first, long long stop, long long every, const double* sums, long long samples) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
+  if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
+    return fail(c, LUDVM_E_STATE, "march: the context is sharded; a survey runs on one device");
+  if (count > LUDVM_MARCH_MAX_SURVEY) return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_SURVEY) + " survey points");
+  if (count && (!x || !z)) return fail(c, LUDVM_E_ARG, "null array");
+  if (count && shift_x && shift_rows != c->march_kin_rows)
+    return fail(c, LUDVM_E_ARG, "march: survey offsets must be one per kinematics row");
+  if (count && (first < 1 || every < 1)) return fail(c, LUDVM_E_ARG, "march: the survey window needs first >= 1 and every >= 1");
+  if (count && sums && samples < 0) return fail(c, LUDVM_E_ARG, "march: survey samples must be >= 0");
+  for (size_t k = 0; k < count; ++k)
+    if (!std::isfinite(x[k]) || !std::isfinite(z[k])) return fail(c, LUDVM_E_ARG, "march: survey points must be finite");
+  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
+    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: survey offsets must be finite");
+  for (size_t k = 0; count && sums && k < kSurveySums * count; ++k)
+    if (!std::isfinite(sums[k])) return fail(c, LUDVM_E_ARG, "march: survey sums must be finite");
+  c->survey_count = 0;
+  c->survey_samples = 0;
+  if (count == 0) return LUDVM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->survey_xz, 2 * count * 8));
+  CHK(ensure(c, c->survey_sums, kSurveySums * count * 8));
+  CHK(ensure(c, c->survey_part, survey_slab_bytes(count)));
+  if (shift_x) CHK(ensure(c, c->survey_shift, shift_rows * 8));
+  double* pxz = static_cast<double*>(c->survey_xz.p);
+  HIPCHK(c, hipMemcpyAsync(pxz, x, count * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(pxz + count, z, count * 8, hipMemcpyHostToDevice, c->stream));
+  if (sums) HIPCHK(c, hipMemcpyAsync(c->survey_sums.p, sums, kSurveySums * count * 8, hipMemcpyHostToDevice, c->stream));
+  else HIPCHK(c, hipMemsetAsync(c->survey_sums.p, 0, kSurveySums * count * 8, c->stream));
+  if (shift_x) HIPCHK(c, hipMemcpyAsync(c->survey_shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->survey_shifted = shift_x != nullptr;
+  c->survey_first = first;
+  c->survey_stop = std::min<long long>(stop, (long long)c->march_kin_rows);
+  c->survey_every = every;
+  c->survey_samples = sums ? samples : 0;
+  c->survey_count = count;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_survey(ludvm_ctx* c, double* sums, long long* samples) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  if (!sums || !samples) return fail(c, LUDVM_E_ARG, "null array");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(sums, c->survey_sums.p, kSurveySums * c->survey_count * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *samples = c->survey_samples;
+  return LUDVM_OK;
+}
 
 int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* seed_z, const long long* release, size_t count,
                             const double* shift_x, size_t shift_rows, const double* cur_x, const double* cur_z,
@@ -391,6 +496,8 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
     if (!trec.empty()) CHK(ensure(c, c->tracer_out, trec.size() * 2 * c->tracer_count * 8));
   }
   size_t trec_at = 0;               // the next recorded step
+  const bool survey = c->survey_count != 0;
+  long long surveyed = 0;           // sampled steps of this call
 
   MarchState hs{};
   hs.n = n0;
@@ -522,6 +629,10 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
         CHK(march_tracer_launch(c, c->stream, n_ub, s, rec ? (long long)trec_at : -1, trec.size()));
         trec_at += rec;
       }
+      if (survey && survey_samples_step(c, s)) {
+        CHK(march_survey_launch(c, c->stream, n_ub, s));
+        ++surveyed;
+      }
       MarchSym ms;
       ms.scale = &S->sc[(s + 1) & 1]; ms.bad = &S->sym_bad; ms.n_lo = n_lo + 1; ms.march = overlap_ok;
       CHK(advect_launch(c, (size_t)n_ub, &S->n, m.dt, nfoil, c->march_vcore, precision, nullptr, nullptr, td, ms));
@@ -556,6 +667,10 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
         const bool rec = trec_at < trec.size() && trec[trec_at] == s;
         rc = march_tracer_launch(c, c->stream_b, n_ub, s, rec ? (long long)trec_at : -1, trec.size());
         trec_at += rec;
+      }
+      if (rc == LUDVM_OK && survey && survey_samples_step(c, s)) {
+        rc = march_survey_launch(c, c->stream_b, n_ub, s);
+        ++surveyed;
       }
       c->stream = main_stream;
       CHK(rc);
@@ -616,6 +731,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   if (c->timing) CHK(drain_timing(c));
   if (probes) c->probe_rows = (size_t)count;
   if (tracers) { c->tracer_rows = trec; c->tracer_ran = true; }
+  c->survey_samples += surveyed;
   return LUDVM_OK;
 }
 

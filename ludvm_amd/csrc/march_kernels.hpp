@@ -703,4 +703,105 @@ march_tracer_finish(const double* slab, long long m_pad, int nsplit, const doubl
   }
 }
 
+// ---- wake survey: running field moments (ludvm_march_set_survey) ------------------------------------------------------------------
+// Survey point k sits at (x[k] + shift[i], z[k]) in step i (shift[i] = 0 in the lab frame).  In every SAMPLED step i -- the
+// host knows the window first <= i < stop, (i - first) % every == 0 and launches nothing outside it -- the probes' field
+// (u, w)_i (above: LUDVM.py:1095-1106, the sources [0, S->n + nfoil) right behind march_solve of step i, Vatistas core, no
+// freestream term, float64) is evaluated there and added to five raw sums per point, sums[0..4][k] = sum u, sum w, sum u^2,
+// sum w^2, sum u w: the time-averaged wake and its Reynolds stresses without a time series ever leaving the device.
+//
+// march_survey_partial  grid = point tiles (kSurveyTile = 256 lanes x kSurveyPerLane points: point t0 + k * 256 + lane in
+//                       register set k of the lane) x source splits; 256-source tiles staged in LDS, every broadcast read of a
+//                       source serves kSurveyPerLane pairs; pair_f64's arithmetic; the source count is read on the device;
+//                       (split, point) partial sums to a slab [split][2][k_pad] of the survey's own
+// march_survey_finish   one lane per point: splits 0, 1, 2, ... in that order give (u, w), then sums[0..4][k] += with plain
+//                       loads and stores (the lane is the only writer of its point; steps follow each other in stream order)
+// The splits are a function of the point count and of the step's anchor-derived bound alone (survey_plan, march.hip), every
+// partial sum is formed by one lane in source order, the splits are combined in split order and the steps in step order: the
+// sums repeat bit for bit however a run is cut into calls.  Both kernels write the survey's buffers only.
+constexpr int kSurveyPerLane = 2;
+constexpr int kSurveyTile = kBlock * kSurveyPerLane;
+constexpr int kSurveySrcTile = 256;
+constexpr int kSurveySums = 5;
+
+__global__ void __launch_bounds__(kBlock)
+march_survey_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, long long count,
+                     long long k_pad, const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
+                     const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
+  __shared__ __attribute__((aligned(16))) double lx[kSurveySrcTile];
+  __shared__ __attribute__((aligned(16))) double lz[kSurveySrcTile];
+  __shared__ __attribute__((aligned(16))) double lg[kSurveySrcTile];
+  __builtin_amdgcn_s_setprio(3);
+  const int tid = threadIdx.x;
+  const long long t0 = (long long)blockIdx.x * kSurveyTile + tid;
+  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
+  const long long s_begin = (long long)blockIdx.y * chunk;
+  long long s_end = s_begin + chunk;
+  if (s_end > ns) s_end = ns;
+  const double sh = shift ? *shift : 0.0;
+  double xp[kSurveyPerLane], zp[kSurveyPerLane], au[kSurveyPerLane], aw[kSurveyPerLane];
+#pragma unroll
+  for (int k = 0; k < kSurveyPerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    const bool on = m < count;
+    xp[k] = on ? px[m] + sh : kPadPosD;
+    zp[k] = on ? pz[m] : kPadPosD;
+    au[k] = 0.0; aw[k] = 0.0;
+  }
+  for (long long base = s_begin; base < s_end; base += kSurveySrcTile) {
+    __syncthreads();
+    {
+      const long long si = base + tid;
+      const bool ok = si < s_end;
+      lx[tid] = ok ? xs[si] : kPadPosD;
+      lz[tid] = ok ? zs[si] : kPadPosD;
+      lg[tid] = ok ? gs[si] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < kSurveySrcTile; ++j) {
+      const double sx = lx[j], sz = lz[j], sg = lg[j];
+#pragma unroll
+      for (int k = 0; k < kSurveyPerLane; ++k) {
+        const double dx = xp[k] - sx;
+        const double dz = zp[k] - sz;
+        const double r2 = __builtin_fma(dz, dz, dx * dx);
+        const double q = __builtin_fma(r2, r2, vc4);
+        const double s = sg * rsqrt_f64(q);
+        au[k] = __builtin_fma(dz, s, au[k]);
+        aw[k] = __builtin_fma(dx, s, aw[k]);
+      }
+    }
+  }
+  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
+  double* row = slab + (long long)blockIdx.y * 2 * k_pad;
+#pragma unroll
+  for (int k = 0; k < kSurveyPerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    if (m < count) {
+      row[m] = au[k] * kInv2PiD;
+      row[k_pad + m] = -aw[k] * kInv2PiD;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_survey_finish(const double* slab, long long k_pad, int nsplit, long long count, double* sums) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (m >= count) return;
+  double u = 0.0, w = 0.0;
+  const double* c0 = slab + m;
+  for (int sidx = 0; sidx < nsplit; ++sidx) {
+    u += c0[(long long)sidx * 2 * k_pad];
+    w += c0[(long long)sidx * 2 * k_pad + k_pad];
+  }
+  double* s = sums + m;
+  s[0] += u;
+  s[count] += w;
+  s[2 * count] = __builtin_fma(u, u, s[2 * count]);
+  s[3 * count] = __builtin_fma(w, w, s[3 * count]);
+  s[4 * count] = __builtin_fma(u, w, s[4 * count]);
+}
+
 }  // namespace ludvm

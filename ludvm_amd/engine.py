@@ -372,6 +372,7 @@ class Engine:
         self._march_dims = (int(npan), int(ncoef))
         self._march_nprobes = 0          # (ludvm_march_setup forgets any probes)
         self._march_ntracers = 0         # (... and any tracers)
+        self._march_nsurvey = 0          # (... and any survey)
 
     def march_run(self, first_step, count, precision, state, hist_nmax=0, anchors=None):
         """Advance the resident wake through time steps [first_step, first_step + count) without a host round
@@ -458,6 +459,38 @@ class Engine:
         xz = np.empty([2, self._march_ntracers])
         self._check(self._lib.ludvm_march_tracer_state(self._ctx, _pd(xz[0]), _pd(xz[1])))
         return xz
+
+    def march_set_survey(self, x, z, shift_x=None, steps=(1, None, 1), sums=None, samples=0):
+        """Wake-survey statistics accumulated by the marched steps (ludvm_march_set_survey); valid after `march_setup`, which
+        forgets them.  In every step i of the window steps = (first, stop, every) -- first <= i < stop, (i - first) % every
+        == 0; stop None: to the end of the kinematics table -- the probes' field at the points (x + shift_x[i], z) is added to
+        five raw float64 sums per point (u, w, u^2, w^2, u w) on the device.  sums [5, K] and samples continue a run (what
+        `march_survey` returned).  Empty points remove the survey."""
+        if not hasattr(self._lib, "ludvm_march_set_survey"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_survey")
+        xs, zs = _f64(x), _f64(z)
+        if len(xs) != len(zs):
+            raise ValueError("march_set_survey: x and z must have the same length")
+        sh = None if shift_x is None else _f64(shift_x)
+        first, stop, every = steps
+        stop = (1 << 62) if stop is None else int(stop)
+        sm = None
+        if sums is not None:
+            sm = np.ascontiguousarray(sums, dtype=np.float64)
+            if sm.shape != (5, len(xs)):
+                raise ValueError("march_set_survey: sums must be [5, K]")
+        self._check(self._lib.ludvm_march_set_survey(self._ctx, _pd(xs), _pd(zs), len(xs), _pd(sh), 0 if sh is None else len(sh),
+                                                     int(first), stop, int(every), _pd(sm), int(samples)))
+        self._march_nsurvey = len(xs)
+
+    def march_survey(self):
+        """(sums float64 [5, K], samples): the survey's raw sums -- u, w, u^2, w^2, u w per point -- and the number of sampled
+        steps they hold (ludvm_march_read_survey)."""
+        if not hasattr(self._lib, "ludvm_march_read_survey"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_read_survey")
+        sums, n = np.empty([5, getattr(self, "_march_nsurvey", 0)]), c_longlong(0)
+        self._check(self._lib.ludvm_march_read_survey(self._ctx, _pd(sums), byref(n)))
+        return sums, int(n.value)
 
     @staticmethod
     def march_anchor_steps(first_step):

@@ -35,6 +35,9 @@ _REFUSED = {
     "tracer_release": (None, "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_release=...)"),
     "tracer_steps": (None, "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_steps=...)"),
     "tracer_frame": ("lab", "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_frame=...)"),
+    "survey": (None, "a sweep has no wake survey (a member can be run on its own: LUDVM(..., survey=...))"),
+    "survey_steps": (None, "a sweep has no wake survey (a member can be run on its own: LUDVM(..., survey=...))"),
+    "survey_frame": ("lab", "a sweep has no wake survey (a member can be run on its own: LUDVM(..., survey=...))"),
 }
 
 

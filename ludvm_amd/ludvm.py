@@ -125,6 +125,22 @@ class LUDVM:
                  at step i is (x + xpiv[i], z) -- and is released into the lab frame from there
       tracer_steps  time steps whose positions `tracer_path` keeps; None (default): every step when the run keeps a dense
                  history, snapshot_steps and the last step otherwise
+      survey     None (default), or the points of a wake survey: a [2, K] array (x row, z row), or a dict(xmin, xmax, zmin, zmax,
+                 dr) meaning the mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr), x-major as `flowfield` builds it
+                 (1 <= K <= 1048576).  In every sampled step the field of `probes` is evaluated at the points and added to
+                 five raw float64 sums per point (u, w, u^2, w^2, u w) -- inside the device-resident march, beside the resident
+                 wake, with storage that does not depend on the number of steps (or from two engine calls per sampled step on
+                 the per-step path).  Results, mesh-shaped [nx, nz] for a dict and [K] otherwise: `survey_x`, `survey_z`,
+                 `survey_count` (sampled steps), `survey_sums` [5, ...], `survey_mean_u`, `survey_mean_w`, and the central
+                 second moments `survey_uu`, `survey_ww`, `survey_uw` = sum(ab)/n - (sum(a)/n)(sum(b)/n) (the Reynolds
+                 stresses of the time-averaged wake); `survey_frame`, `survey_steps` as used.  No freestream term.  Every
+                 other result is unchanged, bit for bit; the sums repeat bit for bit however the run is cut (chunks,
+                 snapshot_steps, history, checkpoint / resume).  Out of scope: a survey in a sweep or on several GPUs, fp32
+                 sums, field snapshots (`flowfield` on snapshot_steps), thrust integration
+      survey_frame  'lab' (default): the points are fixed in the lab frame; 'tunnel': x is measured from the pivot's
+                 x-coordinate -- in step i point k sits at (x[k] + xpiv[i], z[k])
+      survey_steps  (first, stop, every): the sampled steps are first <= i < stop with (i - first) % every == 0; first >= 1,
+                 every >= 1, stop is clipped to nt; default (1, nt, 1).  An empty window is refused
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -151,6 +167,9 @@ class LUDVM:
                 if kwargs.get('tracers') is not None:
                     cls._check_tracers(kwargs['tracers'], kwargs.get('tracer_release'), kwargs.get('tracer_frame', 'lab'))
                     raise ValueError("tracers run on one GPU: not with more than one device in `devices`")
+                if kwargs.get('survey') is not None:
+                    cls._check_survey(kwargs['survey'], kwargs.get('survey_frame', 'lab'), kwargs.get('survey_steps'))
+                    raise ValueError("a survey runs on one GPU: not with more than one device in `devices`")
                 return MultiDeviceLUDVM(args, kwargs, devs)
         return super().__new__(cls)
 
@@ -170,6 +189,63 @@ class LUDVM:
         if not np.isfinite(xz).all():
             raise ValueError("probes must be finite")
         return np.ascontiguousarray(xz)
+
+    @staticmethod
+    def _check_survey(survey, survey_frame, survey_steps=None, nt=None):
+        """-> (float64 [2, K], the results' shape (nx, nz) or (K,), (first, stop, every) with stop clipped to nt), or ValueError
+        (nothing else has been created yet)."""
+        if survey_frame not in ('lab', 'tunnel'):
+            raise ValueError("survey_frame must be 'lab' or 'tunnel'")
+        most = 1048576
+        if isinstance(survey, dict):
+            if set(survey) != {'xmin', 'xmax', 'zmin', 'zmax', 'dr'}:
+                raise ValueError("survey: a dict has exactly the keys xmin, xmax, zmin, zmax, dr")
+            try:
+                xmin, xmax, zmin, zmax, dr = (float(survey[k]) for k in ('xmin', 'xmax', 'zmin', 'zmax', 'dr'))
+            except (TypeError, ValueError) as e:
+                raise ValueError("survey: xmin, xmax, zmin, zmax, dr must be numbers") from e
+            if not np.isfinite([xmin, xmax, zmin, zmax, dr]).all():
+                raise ValueError("survey must be finite")
+            if not dr > 0.0:
+                raise ValueError(f"survey: dr must be > 0 (got {dr})")
+            if not (xmax > xmin and zmax > zmin):
+                raise ValueError("survey: the mesh is empty (xmax > xmin and zmax > zmin)")
+            if np.ceil((xmax - xmin) / dr) * np.ceil((zmax - zmin) / dr) > most:      # (before any mesh is built)
+                raise ValueError(f"survey: at most {most} points")
+            x1, z1 = np.arange(xmin, xmax, dr), np.arange(zmin, zmax, dr)
+            x, z = np.meshgrid(x1, z1, indexing='ij')
+            xz, shape = np.stack([x.ravel(), z.ravel()]), (len(x1), len(z1))
+        else:
+            try:
+                xz = np.array(survey, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError("survey must be an array-like [2, K] of numbers, or a dict(xmin, xmax, zmin, zmax, dr)") from e
+            if xz.ndim != 2 or xz.shape[0] != 2:
+                raise ValueError(f"survey must be [2, K] (x row, z row); got shape {xz.shape}")
+            shape = (xz.shape[1],)
+        K = xz.shape[1]
+        if K < 1:
+            raise ValueError("survey: at least one point")
+        if K > most:
+            raise ValueError(f"survey: at most {most} points (got {K})")
+        if not np.isfinite(xz).all():
+            raise ValueError("survey must be finite")
+        if survey_steps is None:
+            survey_steps = (1, nt if nt is not None else 1 << 62, 1)
+        try:
+            raw = list(survey_steps)
+            first, stop, every = (int(v) for v in raw)
+        except (TypeError, ValueError) as e:
+            raise ValueError("survey_steps must be three integers (first, stop, every)") from e
+        if any(int(v) != v for v in raw):
+            raise ValueError("survey_steps must be three integers (first, stop, every)")
+        if first < 1 or every < 1:
+            raise ValueError("survey_steps: first >= 1 and every >= 1")
+        if nt is not None:
+            stop = min(stop, nt)
+        if stop <= first:
+            raise ValueError(f"survey_steps: the window [{first}, {stop}) holds no time step")
+        return np.ascontiguousarray(xz), shape, (first, stop, every)
 
     @staticmethod
     def _check_tracers(tracers, tracer_release, tracer_frame, tracer_steps=None, nt=None):
@@ -220,7 +296,8 @@ class LUDVM:
                  circulation_freevort=None, xy_freevort=None, *,
                  engine=None, device=0, precision='auto', history='auto', snapshot_steps=(), run=True,
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
-                 probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None):
+                 probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
+                 survey=None, survey_frame='lab', survey_steps=None):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -238,6 +315,16 @@ class LUDVM:
             raise ValueError("tracer_frame must be 'lab' or 'tunnel'")
         elif tracer_release is not None or tracer_steps is not None:
             raise ValueError("tracer_release / tracer_steps need `tracers`")
+        if survey is not None:
+            # refused before any engine, thread or communicator exists
+            survey_xz, survey_shape, survey_win = self._check_survey(survey, survey_frame, survey_steps,
+                                                                     nt=len(np.arange(t0, tf + dt, dt)))
+            if distributed is not None and distributed is not False:
+                raise ValueError("a survey runs on one GPU: not with `distributed`")
+        elif survey_frame not in ('lab', 'tunnel'):
+            raise ValueError("survey_frame must be 'lab' or 'tunnel'")
+        elif survey_steps is not None:
+            raise ValueError("survey_steps needs `survey`")
         # the smallest section the method runs: two panels; the loads read A0 .. A3 (LUDVM.py:1035-1090)
         if Npoints < 3:
             raise ValueError(f"Npoints={Npoints}: a section has at least 3 points (2 panels)")
@@ -258,6 +345,12 @@ class LUDVM:
                               tracer_steps=tracer_rec)
             self.tracer_xz, self.tracer_release, self.tracer_frame = tracer_xz, tracer_rel, tracer_frame
             self._tracer_steps = tracer_rec
+        if survey is not None:              # (likewise; a mesh travels as its five numbers)
+            self._ctor.update(survey={k: float(v) for k, v in survey.items()} if isinstance(survey, dict) else survey_xz.tolist(),
+                              survey_frame=survey_frame, survey_steps=list(survey_win))
+            self._survey_xz, self._survey_shape = survey_xz, survey_shape
+            self.survey_x, self.survey_z = survey_xz[0].reshape(survey_shape), survey_xz[1].reshape(survey_shape)
+            self.survey_frame, self.survey_steps = survey_frame, survey_win
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -533,6 +626,8 @@ class LUDVM:
                 i += 1
             if S.tracers is not None:
                 self.tracer_last = eng.march_tracer_state() if S.can_march else S.tcur
+            if S.survey is not None:
+                self._survey_results(*(eng.march_survey() if S.can_march else (S.ssums, S.scount)))
         finally:
             if self._shard is not None:
                 self._shard.detach(eng)
@@ -546,7 +641,7 @@ class LUDVM:
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
             'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
-            'tracers', 'trec', 'tcur',
+            'tracers', 'trec', 'tcur', 'survey', 'ssums', 'scount',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
@@ -653,7 +748,33 @@ class LUDVM:
             self.tracer_path = SparseHistory(nt)
             S.tcur = self._tracer_seeds(0)
             self.tracer_path.store(0, S.tcur.copy())
+        S.survey = getattr(self, '_survey_xz', None)
+        S.ssums, S.scount = None, 0
+        if S.survey is not None:
+            # the five raw sums the per-step path accumulates (the march keeps its own on the device), or a checkpoint's
+            S.ssums = np.zeros([5, S.survey.shape[1]])
         return S
+
+    def _survey_sampled(self, step):
+        """Is time step `step` one of the survey's sampled steps?"""
+        first, stop, every = self.survey_steps
+        return first <= step < stop and (step - first) % every == 0
+
+    def _survey_points(self, step):
+        """Lab coordinates (x [K], z [K]) of the survey points at time step `step` ('tunnel' frame: x + xpiv[step])."""
+        x, z = self._survey_xz
+        return (x + self.xpiv[int(step)] if self.survey_frame == 'tunnel' else x), z
+
+    def _survey_results(self, sums, n):
+        """The survey's attributes from the raw sums [5, K] over n sampled steps."""
+        shape = self._survey_shape
+        self.survey_count = int(n)
+        self.survey_sums = np.array(sums, dtype=np.float64).reshape((5,) + shape)
+        su, sw, suu, sww, suw = self.survey_sums
+        with np.errstate(divide='ignore', invalid='ignore'):       # (n = 0: a run that stopped before its window)
+            mu, mw = su / n, sw / n
+            self.survey_mean_u, self.survey_mean_w = mu, mw
+            self.survey_uu, self.survey_ww, self.survey_uw = suu / n - mu * mu, sww / n - mw * mw, suw / n - mu * mw
 
     def _tracer_seeds(self, step):
         """Lab coordinates [2, M] of the seeds at time step `step` ('tunnel' frame: x + xpiv[step])."""
@@ -691,6 +812,8 @@ class LUDVM:
             S.tcur = R['tracer_cur'].copy()
             for srow, row in zip(R['tracer_rows_steps'], R['tracer_rows']):
                 self.tracer_path.store(int(srow), row.copy())
+        if S.survey is not None:
+            S.ssums, S.scount = R['survey_sums'].copy(), int(R['survey_samples'])
         for key in ('TEV', 'LEV', 'FREE'):
             if self.history == 'full':
                 P[key][:S.first_step] = R['path_' + key]
@@ -708,6 +831,8 @@ class LUDVM:
         npan = self.Npoints - 1
         if S.tracers is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracers'):
             raise RuntimeError("tracers: this engine marches but has no march_set_tracers (pass march=False for the per-step path)")
+        if S.survey is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey'):
+            raise RuntimeError("survey: this engine marches but has no march_set_survey (pass march=False for the per-step path)")
         # preallocated host buffers for the two device calls of a step (engines that offer them)
         S.sb = eng.step_buffers(npan) if hasattr(eng, 'step_buffers') else None
         S.prec_code = {'f32': 0, 'f32x2': 1, 'f64': 2}[self.precision]
@@ -724,6 +849,9 @@ class LUDVM:
             if S.tracers is not None:
                 eng.march_set_tracers(S.tracers[0], S.tracers[1], release=self.tracer_release,
                                       shift_x=self.xpiv if self.tracer_frame == 'tunnel' else None, cur=S.tcur, record_steps=S.trec)
+            if S.survey is not None:
+                eng.march_set_survey(S.survey[0], S.survey[1], shift_x=self.xpiv if self.survey_frame == 'tunnel' else None,
+                                     steps=self.survey_steps, sums=S.ssums if S.scount else None, samples=S.scount)
         # with the dense history every step's row is recorded: the march then keeps a snapshot of the wake per step on
         # the device (shorter calls, the snapshots are [steps, 2, wake size])
         S.dense_march = S.can_march and self.history == 'full'
@@ -1067,6 +1195,17 @@ class LUDVM:
             k = int(np.searchsorted(S.trec, i))
             if k < len(S.trec) and S.trec[k] == i:
                 self.tracer_path.store(i, nxt.copy())
+        if S.survey is not None and self._survey_sampled(i):
+            # the same field at the survey points, added to the five raw sums in step order
+            px, pz = self._survey_points(i)
+            ns = 2 if shed else 1
+            uo, wo = eng.wake_induce_on_points(0, n_wake, px, pz, vc)
+            un, wn = eng.induce(np.concatenate([new_g[:ns], dGamma]), np.concatenate([new_x[:ns], xg]), np.concatenate([new_z[:ns], zg]),
+                                px, pz, vc, precision='f64')
+            u, w = uo + un, wo + wn
+            for acc, term in zip(S.ssums, (u, w, u * u, w * w, u * w)):
+                acc += term
+            S.scount += 1
         n_after = n_wake + len(new_x)
         one_trip = (not record) and sb is not None and i < nt - 1 and hasattr(eng, 'wake_step_into')
         if not one_trip:
@@ -1167,6 +1306,8 @@ class LUDVM:
             steps_t = self.tracer_path.steps()
             d['tracer_rows_steps'] = np.array(steps_t, dtype=np.int64)
             d['tracer_rows'] = np.stack([self.tracer_path[q] for q in steps_t])
+        if S.survey is not None:        # (likewise; the sums and the count of sampled steps so far)
+            d['survey_sums'], d['survey_samples'] = self.engine.march_survey() if S.can_march else (S.ssums, S.scount)
         if self.history == 'full':
             for key in ('TEV', 'LEV', 'FREE'):
                 d['path_' + key] = P[key][:next_step]
@@ -1198,6 +1339,8 @@ class LUDVM:
                     raise ValueError("probes run on one GPU: this checkpoint cannot be resumed on more than one device")
                 if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('tracers') is not None:
                     raise ValueError("tracers run on one GPU: this checkpoint cannot be resumed on more than one device")
+                if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('survey') is not None:
+                    raise ValueError("a survey runs on one GPU: this checkpoint cannot be resumed on more than one device")
                 return MultiDeviceLUDVM((), {}, devs, builder=lambda r, eng, grp: cls.resume(
                     path, engine=eng, verbose=verbose and r == 0, checkpoint_every=checkpoint_every, checkpoint_path=checkpoint_path,
                     march=march, distributed=grp))
