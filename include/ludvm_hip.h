@@ -460,7 +460,7 @@ int ludvm_march_tracer_state(ludvm_ctx* ctx, double* x, double* z);
  * Guarantee: with a survey set, `rows`, `state`, `hist`, the resident wake, any probe rows and any tracer positions of
  *   ludvm_march_run are bit-identical to a call without it (the survey kernels read the wake and write only buffers of their
  *   own); a call without a survey enqueues exactly what it enqueued before.
- * Limits: one device (not in ludvm_ensemble_run, not sharded); float64 sums only; no freestream term. */
+ * Limits: one device (not sharded; a sweep has ludvm_ensemble_run_surveyed); float64 sums only; no freestream term. */
 #define LUDVM_MARCH_MAX_SURVEY 1048576
 int ludvm_march_set_survey(ludvm_ctx* ctx, const double* x, const double* z, size_t count, const double* shift_x,
                            size_t shift_rows, long long first, long long stop, long long every, const double* sums,
@@ -584,6 +584,45 @@ int ludvm_ensemble_run_traced(ludvm_ctx* ctx, size_t members, int npan, int ncoe
                               const double* seed_z, const long long* release, size_t ntracer, const double* tshift_x,
                               size_t tshift_rows, const long long* trec_steps, size_t ntrec, double* tracer_rows,
                               size_t tracer_doubles);
+
+/* ---- wake survey in an ensemble: one set of points, time-averaged field for every member ---------------------------
+ *
+ * ludvm_ensemble_run_surveyed is ludvm_ensemble_run_traced (nprobe and ntracer may be 0) with the survey of
+ * ludvm_march_set_survey accumulated inside the one launch.  The definition is the same: in a sampled step i of member m --
+ * first <= i < min(stop, nt of m), (i - first) % every == 0 -- (u, w) is the probes' field of step i of member m at
+ * (survey_x[k] + shift[i], survey_z[k]), and the member's five raw sums at point k grow by u, w, u^2, w^2, u w, in step
+ * order; Vatistas core, no freestream term, float64.
+ *   survey_x, survey_z [nsurvey]  common to the batch; nsurvey <= LUDVM_ENSEMBLE_MAX_SURVEY (a sampled step costs what a
+ *                               tracer step of as many tracers costs; a solo march takes LUDVM_MARCH_MAX_SURVEY)
+ *   sshift_x                    one x offset per kinematics row (sshift_rows = kin_rows): shift[i] of member m is
+ *                               sshift_x[kin_off + i]; sshift_rows = 0: no offsets (sshift_x is not looked at)
+ *   first, stop, every          the window, common to the batch; first >= 1, every >= 1 (a member the window misses keeps
+ *                               sums of 0: the number of sampled steps is the caller's to count)
+ *   survey_sums (host)          [members][5][nsurvey] doubles (survey_doubles = exactly that number): sum u, sum w, sum u^2,
+ *                               sum w^2, sum u w of each member
+ * Every other argument, output, limit and guarantee is ludvm_ensemble_run_traced's, and those outputs -- probe rows and tracer
+ * records included -- are bit-identical to a call without a survey: the survey phase reads the member's wake and writes only
+ * the member's sums.  (u, w) of a point are formed in the order a probe row of the same points is, which depends on nsurvey
+ * and on the member's own wake size only, and each point's sums are added by one lane in step order: a member's sums do not
+ * depend on the batch and repeat bit for bit; a member differs from ludvm_march_run(LUDVM_PREC_F64) with the same survey by
+ * summation order only.  nsurvey = 0 is ludvm_ensemble_run_traced itself (the survey arguments are not looked at).  Nothing is
+ * kept on the context.  Checked on the host before anything touches the device (LUDVM_E_ARG): nsurvey over the limit, null
+ * arrays, sshift_rows neither 0 nor kin_rows, a point or offset that is not finite, first < 1, every < 1, survey_doubles !=
+ * members * 5 * nsurvey, and members * 40 * nsurvey bytes of sums over 1 GiB (the message gives the size: split the batch).
+ * A sharded context answers LUDVM_E_STATE.
+ * The entry point is an addition to ABI 7: detect it by its symbol. */
+#define LUDVM_ENSEMBLE_MAX_SURVEY 4096
+int ludvm_ensemble_run_surveyed(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                                const double* tables, const double* kin, size_t kin_rows, const double* init,
+                                const double* free_xzg, size_t free_count, const long long* desc, const long long* snap_steps,
+                                size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
+                                long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
+                                const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w, const double* seed_x,
+                                const double* seed_z, const long long* release, size_t ntracer, const double* tshift_x,
+                                size_t tshift_rows, const long long* trec_steps, size_t ntrec, double* tracer_rows,
+                                size_t tracer_doubles, const double* survey_x, const double* survey_z, size_t nsurvey,
+                                const double* sshift_x, size_t sshift_rows, long long first, long long stop, long long every,
+                                double* survey_sums, size_t survey_doubles);
 
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 

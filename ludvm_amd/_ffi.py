@@ -31,6 +31,8 @@ ENSEMBLE_MAX_PROBES = 1024     # LUDVM_ENSEMBLE_MAX_PROBES
 ENSEMBLE_PROBE_BYTES = 1 << 30  # most bytes of probe rows (2 * 8 * kinematics rows * probes) one ludvm_ensemble_run_probed call returns
 ENSEMBLE_MAX_TRACERS = 4096    # LUDVM_ENSEMBLE_MAX_TRACERS
 ENSEMBLE_TRACER_BYTES = 1 << 30  # most bytes of tracer records (members * (recorded steps + 1) * 2 * 8 * tracers) one ludvm_ensemble_run_traced call returns
+ENSEMBLE_MAX_SURVEY = 4096     # LUDVM_ENSEMBLE_MAX_SURVEY
+ENSEMBLE_SURVEY_BYTES = 1 << 30  # most bytes of survey sums (members * 5 * 8 * points) one ludvm_ensemble_run_surveyed call returns
 MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
 MARCH_MAX_TRACERS = 262144  # LUDVM_MARCH_MAX_TRACERS
 MARCH_MAX_SURVEY = 1048576  # LUDVM_MARCH_MAX_SURVEY
@@ -107,6 +109,11 @@ SIGNATURES = {
                                   POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
                                   POINTER(c_longlong), _pd, _pd, c_size_t, _pd, c_size_t, _pd, _pd,
                                   _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, POINTER(c_longlong), c_size_t, _pd, c_size_t],
+    "ludvm_ensemble_run_surveyed": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
+                                    POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
+                                    POINTER(c_longlong), _pd, _pd, c_size_t, _pd, c_size_t, _pd, _pd,
+                                    _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, POINTER(c_longlong), c_size_t, _pd, c_size_t,
+                                    _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_size_t],
     "ludvm_flowfield_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
                             c_double, _pf, _pf],
     "ludvm_flowfield_vorticity_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
@@ -126,7 +133,7 @@ SIGNATURES = {
 
 # added to ABI 7 without a new version number: a library of ABI 7 built before them is detected by the missing symbol
 ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm_march_read_tracers", "ludvm_march_tracer_state",
-                  "ludvm_ensemble_run_traced", "ludvm_march_set_survey", "ludvm_march_read_survey")
+                  "ludvm_ensemble_run_traced", "ludvm_march_set_survey", "ludvm_march_read_survey", "ludvm_ensemble_run_surveyed")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -28,6 +28,12 @@
 //                      start + dt (u, w) to the member's current positions; a copy of all M positions to the member's tracer
 //                      record on the listed steps and on the last one (held tracers: seed + offset).  The phase reads the
 //                      slab and writes nothing but the member's tracer buffers: ensemble_march<...> does not contain it.
+// With a wake survey (ensemble_surveyed<PROBES, TRACERS>; the definition of march_survey_partial / march_survey_finish), between
+// 2t and 3:
+//   2s. survey         on the sampled steps (first <= step < stop, (step - first) % every == 0) the same sources -> (u, w) at
+//                      the K survey points of the sweep, shifted by the member's own offset of the step, then the member's five
+//                      raw sums [5][K] += u, w, u^2, w^2, u w by the lane that owns the point.  The phase reads the slab and
+//                      writes nothing but the member's sums: ensemble_march / ensemble_traced do not contain it.
 //
 
 // Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
@@ -227,11 +233,72 @@ __device__ __forceinline__ void ens_tracer_step(const EnsembleTracers& T, const 
   __syncthreads();
 }
 
-// The time loop of one member.  ensemble_march<PROBES> is <PROBES, false>: what it compiled to before there were tracers.
-template <bool PROBES, bool TRACERS>
+// The wake survey of a member (ensemble_surveyed only), one record per member in a device array of its own indexed by
+// blockIdx.x: EnsembleMember and EnsembleTracers stay what ensemble_march and ensemble_traced read.
+struct EnsembleSurvey {
+  const double* x; const double* z;     // the K survey points, common to the batch
+  long long K;
+  const double* shift;          // nt x offsets of the points, one per time level of this member, or null
+  long long first, stop, every; // sampled steps: first <= step < stop, (step - first) % every == 0 (common to the batch)
+  double* sums;                 // [5][K] raw sums of this member: u, w, u^2, w^2, u w (zero before the launch)
+};
+
+// One sampled step of the survey: sources [0, ns) of the member's slab -> (u, w) at the K points, each shifted by `shift` in
+// x, then sums[c][k] += for c = 0 .. 4, the terms formed as march_survey_finish forms them.  Tiles as ens_probe_row's, and
+// its order of summation: (u, w) are the bits of a probe row at the same points.  The lane that owns a point (the slice-0
+// lane of the sliced path) is the only writer of its five sums: plain loads and stores.  All threads of the workgroup call
+// this; it ends in a barrier.
+__device__ __forceinline__ void ens_survey_step(const EnsembleSurvey& V, const double* __restrict__ xs, const double* __restrict__ zs,
+                                                const double* __restrict__ gs, long long ns, double shift, double vc4, double* lx,
+                                                double* lz, double* lg, double (*pu)[kBlock / 2], double (*pw)[kBlock / 2]) {
+  const int j = threadIdx.x;
+  const int K = (int)V.K;
+  for (int t0 = 0; t0 < K; t0 += kBlock) {
+    const int cnt = K - t0 < kBlock ? K - t0 : kBlock;
+    double u = 0.0, w = 0.0;
+    int k = -1;                 // the point this lane adds to the sums, if any
+    if (cnt > kBlock / 2) {
+      const bool mine = j < cnt;
+      const double xp = mine ? V.x[t0 + j] + shift : 0.0, zp = mine ? V.z[t0 + j] : 0.0;
+      double au, aw;
+      ens_pair_sums<false>(xs, zs, gs, ns, xp, zp, vc4, mine, 0, 1, lx, lz, lg, au, aw);
+      u = au * kInv2PiD; w = -aw * kInv2PiD;
+      if (mine) k = t0 + j;
+    } else {
+      int slices = kBlock / cnt;
+      if (slices > kEnsSlicesMax) slices = kEnsSlicesMax;
+      const int slice = j / cnt, q = j - slice * cnt;
+      const bool mine = slice < slices;
+      const double xp = mine ? V.x[t0 + q] + shift : 0.0, zp = mine ? V.z[t0 + q] : 0.0;
+      double au, aw;
+      ens_pair_sums<true>(xs, zs, gs, ns, xp, zp, vc4, mine, slice, slices, lx, lz, lg, au, aw);
+      u = au * kInv2PiD; w = -aw * kInv2PiD;
+      if (mine && slice > 0) { pu[slice - 1][q] = u; pw[slice - 1][q] = w; }
+      __syncthreads();
+      if (slice == 0) {
+        for (int r = 1; r < slices; ++r) { u += pu[r - 1][q]; w += pw[r - 1][q]; }
+        k = t0 + q;
+      }
+    }
+    if (k >= 0) {
+      double* s = V.sums + k;
+      s[0] += u;
+      s[K] += w;
+      s[2 * (size_t)K] = __builtin_fma(u, u, s[2 * (size_t)K]);
+      s[3 * (size_t)K] = __builtin_fma(w, w, s[3 * (size_t)K]);
+      s[4 * (size_t)K] = __builtin_fma(u, w, s[4 * (size_t)K]);
+    }
+  }
+  __syncthreads();
+}
+
+// The time loop of one member.  ensemble_march<PROBES> is <PROBES, false, false>: what it compiled to before there were tracers;
+// ensemble_traced<PROBES> is <PROBES, true, false>: what it compiled to before there was a survey.
+template <bool PROBES, bool TRACERS, bool SURVEY>
 __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps,
                                                int nsnap, const EnsembleTracers* __restrict__ tracers,
-                                               const long long* __restrict__ trec_steps, int ntrec) {
+                                               const long long* __restrict__ trec_steps, int ntrec,
+                                               const EnsembleSurvey* __restrict__ surveys) {
   __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lz[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lg[kEnsTile + kEnsGroup];
@@ -466,6 +533,14 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
       }
     }
 
+    // ---- 2s. survey: on a sampled step the same sources at the survey points, added to the member's five raw sums --------
+    if constexpr (SURVEY) {
+      const EnsembleSurvey& V = surveys[blockIdx.x];
+      // (the same for every lane of the workgroup: an unsampled step skips the phase before its first barrier)
+      if (step >= V.first && step < V.stop && (step - V.first) % V.every == 0)
+        ens_survey_step(V, xc, zc, g, n + npan, V.shift ? V.shift[step] : 0.0, m.vc4, lx, lz, lg, pu, pw);
+    }
+
     // ---- 3. roll-up (:1095-1127) and 4. placement of the coming step (:672-681, :788-800) -------------------------------
     const double* kin_next = step + 1 < nt ? kin + krow : nullptr;
     for (long long t0 = 0; t0 < n; t0 += kBlock) {
@@ -512,7 +587,7 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
 template <bool PROBES>
 __global__ void __launch_bounds__(kBlock)
 ensemble_march(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap) {
-  ens_member_run<PROBES, false>(members, snap_steps, nsnap, nullptr, nullptr, 0);
+  ens_member_run<PROBES, false, false>(members, snap_steps, nsnap, nullptr, nullptr, 0, nullptr);
 }
 
 // ensemble_march<PROBES> with phase 2t: the launch of ludvm_ensemble_run_traced
@@ -520,7 +595,16 @@ template <bool PROBES>
 __global__ void __launch_bounds__(kBlock)
 ensemble_traced(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap,
                 const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec) {
-  ens_member_run<PROBES, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec);
+  ens_member_run<PROBES, true, false>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, nullptr);
+}
+
+// ensemble_march<PROBES> / ensemble_traced<PROBES> with phase 2s: the launches of ludvm_ensemble_run_surveyed
+template <bool PROBES, bool TRACERS>
+__global__ void __launch_bounds__(kBlock)
+ensemble_surveyed(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap,
+                  const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec,
+                  const EnsembleSurvey* __restrict__ surveys) {
+  ens_member_run<PROBES, TRACERS, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, surveys);
 }
 
 }  // namespace ludvm

@@ -761,14 +761,23 @@ struct EnsembleTracerArgs {
   double* rows = nullptr; size_t doubles = 0;
 };
 
-// ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at), ludvm_ensemble_run_probed and, with tracers,
-// ludvm_ensemble_run_traced
+// The survey arguments of ludvm_ensemble_run_surveyed (count = 0: none, nothing else is looked at)
+struct EnsembleSurveyArgs {
+  const double* x = nullptr; const double* z = nullptr; size_t count = 0;
+  const double* shift_x = nullptr; size_t shift_rows = 0;
+  long long first = 1, stop = 0, every = 1;
+  double* sums = nullptr; size_t doubles = 0;
+};
+
+// ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at), ludvm_ensemble_run_probed, with tracers
+// ludvm_ensemble_run_traced and, with a survey, ludvm_ensemble_run_surveyed
 int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
                       const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
-                      double* probe_w, const EnsembleTracerArgs& tr = EnsembleTracerArgs()) {
+                      double* probe_w, const EnsembleTracerArgs& tr = EnsembleTracerArgs(),
+                      const EnsembleSurveyArgs& sv = EnsembleSurveyArgs()) {
   if (!c) return LUDVM_E_ARG;
   if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
     return fail(c, LUDVM_E_STATE, "ensemble: the context is sharded; members are independent -- split the list per device");
@@ -809,6 +818,26 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
                                       " MiB of tracer records (2 x 8 x " + std::to_string(members) + " members x " +
                                       std::to_string(ntrec + 1) + " records x " + std::to_string(M) + " tracers) are over 1 GiB; split the batch");
     if (tr.doubles < members * (ntrec + 1) * 2 * M) return fail(c, LUDVM_E_ARG, "ensemble: tracer records outside the array");
+  }
+  const size_t K = sv.count;
+  if (K) {
+    if (K > LUDVM_ENSEMBLE_MAX_SURVEY)
+      return fail(c, LUDVM_E_ARG, "ensemble: at most " + std::to_string(LUDVM_ENSEMBLE_MAX_SURVEY) + " survey points");
+    if (!sv.x || !sv.z || !sv.sums) return fail(c, LUDVM_E_ARG, "null array");
+    if (sv.shift_rows != 0 && sv.shift_rows != kin_rows)
+      return fail(c, LUDVM_E_ARG, "ensemble: survey offsets must be one per kinematics row");
+    if (sv.shift_rows && !sv.shift_x) return fail(c, LUDVM_E_ARG, "null array");
+    if (sv.first < 1 || sv.every < 1) return fail(c, LUDVM_E_ARG, "ensemble: survey steps: first >= 1 and every >= 1");
+    for (size_t k = 0; k < K; ++k)
+      if (!std::isfinite(sv.x[k]) || !std::isfinite(sv.z[k])) return fail(c, LUDVM_E_ARG, "ensemble: survey points must be finite");
+    for (size_t k = 0; k < sv.shift_rows; ++k)
+      if (!std::isfinite(sv.shift_x[k])) return fail(c, LUDVM_E_ARG, "ensemble: survey offsets must be finite");
+    // members x 5 x 8 x K bytes of sums: at most 1 GiB
+    if (members > (((size_t)1 << 30) / 40) / K)
+      return fail(c, LUDVM_E_ARG, "ensemble: " + std::to_string(40.0 * (double)members * (double)K / (1 << 20)) +
+                                      " MiB of survey sums (5 x 8 x " + std::to_string(members) + " members x " + std::to_string(K) +
+                                      " points) are over 1 GiB; split the batch");
+    if (sv.doubles != members * 5 * K) return fail(c, LUDVM_E_ARG, "ensemble: survey sums must hold members x 5 x points doubles");
   }
   if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
     return fail(c, LUDVM_E_ARG, "null array");
@@ -861,14 +890,20 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   const size_t in_tracer = M ? 3 * Arena::need(M, 8) + Arena::need(ttiles, 8) + (tr.shift_x ? Arena::need(tr.shift_rows, 8) : 0) +
                                    Arena::need(ntrec + 1, 8) + Arena::need(members, sizeof(EnsembleTracers))
                              : 0;
-  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer));
+  // (survey: points, offsets and the members' survey records behind those; the sums behind the outputs)
+  const bool sshift = K && sv.shift_rows;
+  const size_t in_survey = K ? 2 * Arena::need(K, 8) + (sshift ? Arena::need(sv.shift_rows, 8) : 0) +
+                                   Arena::need(members, sizeof(EnsembleSurvey))
+                             : 0;
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey));
   CHK(ensure(c, c->ens_work, work_doubles * 8));
   const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
   const size_t out_n = Arena::need(members * nrec, 8);
   const size_t out_probe = nprobe ? 2 * Arena::need(kin_rows * nprobe, 8) : 0;
   const size_t trec_doubles = members * (ntrec + 1) * 2 * M;
   const size_t out_tracer = M ? Arena::need(trec_doubles, 8) : 0;
-  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer));
+  const size_t out_survey = K ? Arena::need(members * 5 * K, 8) : 0;
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey));
   Arena in(c->ens_in.p), out(c->ens_out.p);
   double* d_tab = in.take<double>(members * tab_doubles);
   double* d_kin = in.take<double>(kin_rows * krow);
@@ -900,8 +935,18 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     d_tr = in.take<EnsembleTracers>(members);
     d_trows = out.take<double>(trec_doubles);
   }
+  double *d_vx = nullptr, *d_vz = nullptr, *d_vshift = nullptr, *d_vsums = nullptr;
+  EnsembleSurvey* d_sv = nullptr;
+  if (K) {
+    d_vx = in.take<double>(K);
+    d_vz = in.take<double>(K);
+    if (sshift) d_vshift = in.take<double>(sv.shift_rows);
+    d_sv = in.take<EnsembleSurvey>(members);
+    d_vsums = out.take<double>(members * 5 * K);
+  }
 
   std::vector<EnsembleMember> hm(members);
+  std::vector<EnsembleSurvey> hv(K ? members : 0);
   std::vector<EnsembleTracers> ht(M ? members : 0);
   std::vector<long long> tmin(ttiles, std::numeric_limits<long long>::max());     // earliest release step of each tile
   for (size_t k = 0; k < M; ++k) tmin[k / kBlock] = std::min(tmin[k / kBlock], tr.release[k]);
@@ -936,6 +981,13 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
       work += 2 * M;
       t.rec = d_trows + mi * (ntrec + 1) * 2 * M;
     }
+    if (K) {
+      EnsembleSurvey& v = hv[mi];
+      v.x = d_vx; v.z = d_vz; v.K = (long long)K;
+      v.shift = d_vshift ? d_vshift + (size_t)d[1] : nullptr;
+      v.first = sv.first; v.stop = sv.stop; v.every = sv.every;
+      v.sums = d_vsums + mi * 5 * K;
+    }
     e.rows = d_rows + (size_t)d[4] * row_doubles;
     e.rec = d_wakes + (size_t)d[5];
     e.rec_n = d_n + mi * nrec;
@@ -969,8 +1021,24 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     // (a record whose step a member does not have stays 0)
     HIPCHK(c, hipMemsetAsync(d_trows, 0, trec_doubles * 8, c->stream));
   }
+  if (K) {
+    HIPCHK(c, hipMemcpyAsync(d_vx, sv.x, K * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_vz, sv.z, K * 8, hipMemcpyHostToDevice, c->stream));
+    if (sshift) HIPCHK(c, hipMemcpyAsync(d_vshift, sv.shift_x, sv.shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sv, hv.data(), members * sizeof(EnsembleSurvey), hipMemcpyHostToDevice, c->stream));
+    // (the kernel adds to the sums)
+    HIPCHK(c, hipMemsetAsync(d_vsums, 0, members * 5 * K * 8, c->stream));
+  }
   // ONE launch: a workgroup per member, all of its time steps inside
-  if (M && nprobe)
+  if (K) {
+    const dim3 grid((unsigned)members), block(kBlock);
+    const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
+    const long long* ar = d_trec; const EnsembleSurvey* av = d_sv;
+    if (M && nprobe) hipLaunchKernelGGL((ensemble_surveyed<true, true>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av);
+    else if (M) hipLaunchKernelGGL((ensemble_surveyed<false, true>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av);
+    else if (nprobe) hipLaunchKernelGGL((ensemble_surveyed<true, false>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av);
+    else hipLaunchKernelGGL((ensemble_surveyed<false, false>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av);
+  } else if (M && nprobe)
     hipLaunchKernelGGL(ensemble_traced<true>, dim3((unsigned)members), dim3(kBlock), 0, c->stream, (const EnsembleMember*)d_mem,
                        (const long long*)d_snap, (int)nsnap, (const EnsembleTracers*)d_tr, (const long long*)d_trec, (int)ntrec);
   else if (M)
@@ -991,7 +1059,8 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     HIPCHK(c, hipMemcpyAsync(probe_w, d_pw, kin_rows * nprobe * 8, hipMemcpyDeviceToHost, c->stream));
   }
   if (M) HIPCHK(c, hipMemcpyAsync(tr.rows, d_trows, trec_doubles * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht and tmin live on this frame)
+  if (K) HIPCHK(c, hipMemcpyAsync(sv.sums, d_vsums, members * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv and tmin live on this frame)
   return LUDVM_OK;
 }
 
@@ -1035,6 +1104,31 @@ int ludvm_ensemble_run_traced(ludvm_ctx* c, size_t members, int npan, int ncoef,
   return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
                            snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
                            shift_rows, probe_u, probe_w, tr);
+}
+
+int ludvm_ensemble_run_surveyed(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                                const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
+                                size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
+                                size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
+                                const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
+                                double* probe_w, const double* seed_x, const double* seed_z, const long long* release, size_t ntracer,
+                                const double* tshift_x, size_t tshift_rows, const long long* trec_steps, size_t ntrec,
+                                double* tracer_rows, size_t tracer_doubles, const double* survey_x, const double* survey_z,
+                                size_t nsurvey, const double* sshift_x, size_t sshift_rows, long long first, long long stop,
+                                long long every, double* survey_sums, size_t survey_doubles) {
+  EnsembleTracerArgs tr;
+  tr.seed_x = seed_x; tr.seed_z = seed_z; tr.release = release; tr.count = ntracer;
+  tr.shift_x = tshift_x; tr.shift_rows = tshift_rows;
+  tr.rec_steps = trec_steps; tr.nrec = ntrec;
+  tr.rows = tracer_rows; tr.doubles = tracer_doubles;
+  EnsembleSurveyArgs sv;
+  sv.x = survey_x; sv.z = survey_z; sv.count = nsurvey;
+  sv.shift_x = sshift_x; sv.shift_rows = sshift_rows;
+  sv.first = first; sv.stop = stop; sv.every = every;
+  sv.sums = survey_sums; sv.doubles = survey_doubles;
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
+                           shift_rows, probe_u, probe_w, tr, sv);
 }
 
 }  // extern "C"

@@ -551,7 +551,38 @@ class Engine:
             probes = (px, pz, None if probe_shift_x is None else _f64(probe_shift_x))
         return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, (sx, sz, rel, sh, rec))
 
-    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None):
+    def ensemble_run_surveyed(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=(), *, survey_x, survey_z,
+                              survey_steps, survey_shift_x=None, seed_x=(), seed_z=(), release=(), shift_x=None, record_steps=(),
+                              probe_x=None, probe_z=None, probe_shift_x=None):
+        """`ensemble_run_traced` (tracers and probes optional) with a wake survey accumulated inside the launch
+        (ludvm_ensemble_run_surveyed): survey_x, survey_z [K] and survey_steps = (first, stop, every) are common to the batch;
+        survey_shift_x: None, or one x offset per row of `kin` -- in a sampled step i of a member (first <= i < min(stop, nt),
+        (i - first) % every == 0) point k sits at (survey_x[k] + survey_shift_x[kin_off + i], survey_z[k]).
+        -> `ensemble_run_traced`'s tuple with survey_sums [members, 5, K] appended: sum u, sum w, sum u^2, sum w^2, sum u w of
+        each member over its sampled steps (counting them is the caller's)."""
+        if not hasattr(self._lib, "ludvm_ensemble_run_surveyed"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_ensemble_run_surveyed")
+        vx, vz = _f64(survey_x), _f64(survey_z)
+        if len(vx) != len(vz):
+            raise ValueError("ensemble_run_surveyed: survey_x and survey_z must have the same length")
+        first, stop, every = (int(v) for v in survey_steps)
+        vsh = None if survey_shift_x is None else _f64(survey_shift_x)
+        sx, sz = _f64(seed_x), _f64(seed_z)
+        rel = np.ascontiguousarray(release, dtype=np.int64).reshape(-1)
+        if len(sx) != len(sz) or len(rel) != len(sx):
+            raise ValueError("ensemble_run_surveyed: seed_x, seed_z and release must have the same length")
+        sh = None if shift_x is None else _f64(shift_x)
+        rec = np.ascontiguousarray(list(record_steps), dtype=np.int64).reshape(-1)
+        probes = None
+        if probe_x is not None or probe_z is not None:
+            px, pz = _f64(probe_x), _f64(probe_z)
+            if len(px) != len(pz):
+                raise ValueError("ensemble_run_surveyed: probe_x and probe_z must have the same length")
+            probes = (px, pz, None if probe_shift_x is None else _f64(probe_shift_x))
+        return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, (sx, sz, rel, sh, rec),
+                              (vx, vz, vsh, first, stop, every))
+
+    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None, survey=None):
         npan, ncoef = int(npan), int(ncoef)
         desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
         members = desc.shape[0]
@@ -577,6 +608,15 @@ class Engine:
             px, pz, sh = probes if probes is not None else (np.empty(0), np.empty(0), None)
             pu, pw = np.empty([kin.shape[0], len(px)]), np.empty([kin.shape[0], len(px)])
             trows = np.zeros([members, len(rec) + 1, 2, len(sx)])
+            if survey is not None:
+                vx, vz, vsh, first, stop, every = survey
+                sums = np.zeros([members, 5, len(vx)])
+                self._check(self._lib.ludvm_ensemble_run_surveyed(
+                    *args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh), _pd(pu), _pd(pw), _pd(sx), _pd(sz),
+                    rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),
+                    _pd(trows), trows.size, _pd(vx), _pd(vz), len(vx), _pd(vsh), 0 if vsh is None else len(vsh), first, stop, every,
+                    _pd(sums), sums.size))
+                return (rows, wakes, wake_n, trows, sums) if probes is None else (rows, wakes, wake_n, trows, pu, pw, sums)
             self._check(self._lib.ludvm_ensemble_run_traced(
                 *args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh), _pd(pu), _pd(pw), _pd(sx), _pd(sz),
                 rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),

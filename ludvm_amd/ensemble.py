@@ -1,6 +1,6 @@
 """`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run; with velocity probes
 Engine.ensemble_run_probed / ludvm_ensemble_run_probed; with passive tracers Engine.ensemble_run_traced /
-ludvm_ensemble_run_traced).
+ludvm_ensemble_run_traced; with a wake survey Engine.ensemble_run_surveyed / ludvm_ensemble_run_surveyed).
 
 A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
 'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
@@ -35,9 +35,9 @@ _REFUSED = {
     "tracer_release": (None, "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_release=...)"),
     "tracer_steps": (None, "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_steps=...)"),
     "tracer_frame": ("lab", "the tracers of a sweep are common to it: sweep(cases, particles=..., particle_frame=...)"),
-    "survey": (None, "a sweep has no wake survey (a member can be run on its own: LUDVM(..., survey=...))"),
-    "survey_steps": (None, "a sweep has no wake survey (a member can be run on its own: LUDVM(..., survey=...))"),
-    "survey_frame": ("lab", "a sweep has no wake survey (a member can be run on its own: LUDVM(..., survey=...))"),
+    "survey": (None, "the survey of a sweep is common to it: sweep(cases, survey=...)"),
+    "survey_steps": (None, "the survey of a sweep is common to it: sweep(cases, survey=...)"),
+    "survey_frame": ("lab", "the survey of a sweep is common to it: sweep(cases, survey=...)"),
 }
 
 
@@ -144,8 +144,38 @@ def _check_sweep_particles(particles, particle_release, particle_frame, particle
     return xz, rel, rec
 
 
+def _check_sweep_survey(survey, survey_frame, survey_steps, merged):
+    """The sweep's survey -> (points [2, K], the results' shape, (first, stop, every)), or None without `survey`; refused from
+    the keywords alone like a member's."""
+    if survey is None:
+        if survey_frame not in ("lab", "tunnel"):
+            raise ValueError("survey_frame must be 'lab' or 'tunnel'")
+        if survey_steps is not None:
+            raise ValueError("survey_steps needs `survey`")
+        return None
+    try:
+        xz, shape, win = LUDVM._check_survey(survey, survey_frame, survey_steps)
+    except ValueError as e:
+        raise ValueError("sweep: " + str(e)) from e
+    K = xz.shape[1]
+    if K > _ffi.ENSEMBLE_MAX_SURVEY:
+        raise ValueError(f"sweep: survey: at most {_ffi.ENSEMBLE_MAX_SURVEY} points in a sweep (got {K}); a member can be run on its "
+                         f"own with up to {_ffi.MARCH_MAX_SURVEY}: LUDVM(..., survey=...)")
+    size = len(merged) * 5 * 8 * K
+    if size > _ffi.ENSEMBLE_SURVEY_BYTES:
+        raise ValueError(f"sweep: survey: {len(merged)} members x {K} points are {size} bytes ({size / 2**30:.2f} GiB) of survey "
+                         f"sums, over the {_ffi.ENSEMBLE_SURVEY_BYTES >> 30} GiB one launch returns: split the case list")
+    for idx, kw in enumerate(merged):
+        nt = _time_levels(kw)
+        if min(win[1], nt) <= win[0]:
+            raise ValueError(f"sweep: member {idx}: survey_steps: the window [{win[0]}, {min(win[1], nt)}) holds no time step of "
+                             f"its {nt - 1}")
+    return xz, shape, win
+
+
 def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", particles=None, particle_release=None,
-          particle_frame="lab", particle_steps=None, verbose=False, cls=LUDVM, **common):
+          particle_frame="lab", particle_steps=None, survey=None, survey_frame="lab", survey_steps=None, verbose=False, cls=LUDVM,
+          **common):
     """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
     return the list of LUDVM objects, in order.  Each carries what a solo
     `LUDVM(**kw, precision='f64', history='sparse', snapshot_steps=snapshot_steps)` run carries: Cl, Cd, Cm, Cn, Cs, Ct, Fn, Fs, L,
@@ -170,6 +200,16 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     has no row for it (`tracer_last` is its last step either way).  `probes` and `particles` compose in one launch; everything else a
     member returns, its probe rows included, is bit-identical to the sweep without particles.
 
+    survey: None, or the points of a wake survey common to the sweep -- a [2, K] array or a dict(xmin, xmax, zmin, zmax, dr) mesh,
+    1 <= K <= 4096 -- with survey_frame ('lab' | 'tunnel') and survey_steps (first, stop, every), the meaning of LUDVM(..., survey=,
+    survey_frame=, survey_steps=).  Points and window are common; survey_frame='tunnel' adds each member's own xpiv[step] to the
+    points, and a member samples first <= i < min(stop, its nt), (i - first) % every == 0.  The five raw sums are accumulated
+    inside the one launch and every member carries the attributes of a solo run with a survey: `survey_x`, `survey_z`
+    (mesh-shaped for a dict), `survey_count`, `survey_sums`, `survey_mean_u`, `survey_mean_w`, `survey_uu`, `survey_ww`,
+    `survey_uw`, `survey_frame`, and `survey_steps` with stop clipped to the member's nt.  `survey` composes with `probes` and
+    `particles` in one launch; everything else a member returns, probe rows and tracer paths included, is bit-identical to the
+    sweep without a survey.
+
     Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
@@ -179,9 +219,13 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     levels x P) over 1 GiB: split the case list; `particles` / `particle_*` inside a member's dict, `tracers` / `tracer_*`
     anywhere (use `particles=`), more than 4096 particles, seeds that are not finite, release steps < 1 or not one integer per
     tracer, a particle_frame other than 'lab' / 'tunnel', particle_steps outside [1, the largest nt - 1], an engine without
-    ensemble_run_traced, and tracer records (16 bytes x members x (recorded steps + 1) x M) over 1 GiB.
+    ensemble_run_traced, and tracer records (16 bytes x members x (recorded steps + 1) x M) over 1 GiB; `survey` / `survey_steps` /
+    survey_frame='tunnel' inside a member's dict (they belong to the sweep), more than 4096 survey points, points that are not
+    finite, a survey_frame other than 'lab' / 'tunnel', survey_steps that are not three integers with first >= 1 and every >= 1
+    or that hold no step of some member (named), survey_steps without `survey`, an engine without ensemble_run_surveyed, and
+    survey sums (40 bytes x members x K) over 1 GiB: split the case list.
 
-    Out of scope: per-member probe or seed sets, tracers of a sweep on several GPUs, fp32 tracer sums, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe, seed or survey point sets and windows, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums, fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     cases = list(cases)
     if not cases:
@@ -195,6 +239,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         merged.append(kw)
     probe_xz = _check_sweep_probes(probes, probe_frame, merged)
     traced = _check_sweep_particles(particles, particle_release, particle_frame, particle_steps, snapshot_steps, merged)
+    surveyed = _check_sweep_survey(survey, survey_frame, survey_steps, merged)
     if engine is None:
         from .engine import Engine
         engine = Engine(device)
@@ -204,6 +249,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         raise ValueError("sweep: probes: this engine has no ensemble_run_probed")
     if traced is not None and not hasattr(engine, "ensemble_run_traced"):
         raise ValueError("sweep: particles: this engine has no ensemble_run_traced")
+    if surveyed is not None and not hasattr(engine, "ensemble_run_surveyed"):
+        raise ValueError("sweep: survey: this engine has no ensemble_run_surveyed")
     snaps = sorted({int(s) for s in snapshot_steps})
     dev_snaps = [s for s in snaps if s >= 1]
     if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
@@ -236,7 +283,11 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
             sim.probe_xz, sim.probe_frame = probe_xz.copy(), probe_frame
         if traced is not None:
             sim.tracer_xz, sim.tracer_release, sim.tracer_frame = traced[0].copy(), traced[1].copy(), particle_frame
-        if probe_xz is not None or traced is not None:
+        if surveyed is not None:
+            sim._survey_xz, sim._survey_shape = surveyed[0].copy(), surveyed[1]
+            sim.survey_x, sim.survey_z = sim._survey_xz[0].reshape(surveyed[1]), sim._survey_xz[1].reshape(surveyed[1])
+            sim.survey_frame, sim.survey_steps = survey_frame, (surveyed[2][0], min(surveyed[2][1], sim.nt), surveyed[2][2])
+        if probe_xz is not None or traced is not None or surveyed is not None:
             shift.append(np.asarray(sim.xpiv, dtype=float))
         nt, nf = sim.nt, S.nf
         desc[idx] = [nt, kin_off, nf, free_off, row_off, wake_off]
@@ -248,11 +299,22 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
 
     # device: one launch
     packed = (npan, ncoef, np.stack(sc), np.stack(tb), np.concatenate(kn), np.stack(ini), np.concatenate(fr), desc, dev_snaps)
+    targs = {}
     if traced is not None:
         # recorded steps: the listed ones, or snapshot_steps (each member's last step is always the final record)
         trec = [s for s in (dev_snaps if traced[2] is None else traced[2]) if 1 <= s <= max(sim.nt for sim in sims) - 1]
         targs = dict(seed_x=traced[0][0], seed_z=traced[0][1], release=traced[1], record_steps=trec,
-                  shift_x=np.concatenate(shift) if particle_frame == "tunnel" else None)
+                     shift_x=np.concatenate(shift) if particle_frame == "tunnel" else None)
+    if surveyed is not None:
+        # (the window as given: the device clips it to each member's nt)
+        targs.update(survey_x=surveyed[0][0], survey_z=surveyed[0][1], survey_steps=surveyed[2],
+                     survey_shift_x=np.concatenate(shift) if survey_frame == "tunnel" else None)
+        if probe_xz is not None:
+            targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
+            rows, wakes, wake_n, trows, pu, pw, ssums = engine.ensemble_run_surveyed(*packed, **targs)
+        else:
+            rows, wakes, wake_n, trows, ssums = engine.ensemble_run_surveyed(*packed, **targs)
+    elif traced is not None:
         if probe_xz is not None:
             targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
             rows, wakes, wake_n, trows, pu, pw = engine.ensemble_run_traced(*packed, **targs)
@@ -278,6 +340,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
             sim.tracer_last = trows[idx, len(trec)].copy()
             if traced[2] is None:               # (the solo rule of a sparse history: snapshot_steps and the last step)
                 sim.tracer_path.store(nt - 1, sim.tracer_last.copy())
+        if surveyed is not None:
+            first, stop, every = sim.survey_steps
+            sim._survey_results(ssums[idx], len(range(first, stop, every)))
         cap = nf + 2 * (nt - 1)
         R = rows[r0:r0 + nt - 1]
         hist = _RecordedWakes()

@@ -135,7 +135,7 @@ class LUDVM:
                  second moments `survey_uu`, `survey_ww`, `survey_uw` = sum(ab)/n - (sum(a)/n)(sum(b)/n) (the Reynolds
                  stresses of the time-averaged wake); `survey_frame`, `survey_steps` as used.  No freestream term.  Every
                  other result is unchanged, bit for bit; the sums repeat bit for bit however the run is cut (chunks,
-                 snapshot_steps, history, checkpoint / resume).  Out of scope: a survey in a sweep or on several GPUs, fp32
+                 snapshot_steps, history, checkpoint / resume).  A sweep takes it as sweep(..., survey=).  Out of scope: a survey on several GPUs, fp32
                  sums, field snapshots (`flowfield` on snapshot_steps), thrust integration
       survey_frame  'lab' (default): the points are fixed in the lab frame; 'tunnel': x is measured from the pivot's
                  x-coordinate -- in step i point k sits at (x[k] + xpiv[i], z[k])

@@ -19,7 +19,12 @@ instantiations (and the parent's kernel) apart.
     python tools/ensemble_throughput.py --particles-leg [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_tracers_cost.txt
 What passive tracers in a sweep cost: the same device call of 256 copies of config 1 without tracers on this
 build and on the parent build, alternated; then with M = 256 and M = 4096 tracers (a rake in the tunnel frame, all released
-at step 1, the last step recorded)."""
+at step 1, the last step recorded).
+
+    python tools/ensemble_throughput.py --survey-leg [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_survey_cost.txt
+What a wake survey in a sweep costs: the same device call of 256 copies of config 1 without a survey on this
+build and on the parent build, alternated; then with K = 256 and K = 4096 survey points (a rake in the tunnel frame, every
+step sampled), and the probe phase on the K = 256 rake beside them."""
 import argparse
 import os
 import sys
@@ -37,7 +42,8 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--window", type=float, default=1.0, help="seconds a timed window should last")
 ap.add_argument("--probes-leg", action="store_true", help="the cost of probes in a sweep instead of the size ladder")
 ap.add_argument("--particles-leg", action="store_true", help="the cost of passive tracers in a sweep instead of the size ladder")
-ap.add_argument("--parent-lib", default="", help="probes / particles leg: a build of the parent commit, timed beside this one")
+ap.add_argument("--survey-leg", action="store_true", help="the cost of a wake survey in a sweep instead of the size ladder")
+ap.add_argument("--parent-lib", default="", help="probes / particles / survey leg: a build of the parent commit, timed beside this one")
 a = ap.parse_args()
 
 from ludvm_amd import LUDVM, Engine, sweep  # noqa: E402
@@ -284,6 +290,92 @@ def particles_leg():
         print("untraced device call against the parent build: NOT MEASURED (no --parent-lib given)")
 
 
+def survey_leg():
+    """Device call only, like the probes leg: B = 256 copies of config 1 packed once, the call repeated."""
+    B = 256
+    kept = {}
+    plain_call = inner
+
+    def keep(*args, **kw):
+        kept[len(args[7])] = args
+        return plain_call(*args, **kw)
+    eng.ensemble_run = keep
+    sims = sweep([dict(CONFIG1)] * B, engine=eng)
+    del eng.ensemble_run
+    engines = {"this build": eng}
+    if a.parent_lib:
+        engines["parent build"] = Engine(0, lib_path=os.path.abspath(a.parent_lib))
+    packed, s1 = kept[B], sims[0]
+    shift = np.concatenate([s.xpiv for s in sims])
+
+    def variant(which, K):
+        e = engines[which]
+        if K == 0:
+            return lambda: e.ensemble_run(*packed)
+        # a rake behind the foil in the frame of the pivot, K points over z in [-2, 2], every step sampled
+        vx, vz = np.full(K, 2.0), np.linspace(-2.0, 2.0, K)
+        return lambda: e.ensemble_run_surveyed(*packed, survey_x=vx, survey_z=vz, survey_steps=(1, 1 << 62, 1), survey_shift_x=shift)
+    order = ([("parent build", 0)] if a.parent_lib else []) + [("this build", 0), ("this build", 256), ("this build", 4096)]
+    calls = {v: variant(*v) for v in order}
+    # beside them, in the same windows: the probe phase on the same rake (P = 256: 420 MB of probe rows)
+    px, pz = np.full(256, 2.0), np.linspace(-2.0, 2.0, 256)
+    order.append(("probes", 256))
+    calls[("probes", 256)] = lambda: eng.ensemble_run_probed(*packed, probe_x=px, probe_z=pz, shift_x=shift)
+    reps_in = {}
+    for v, f in calls.items():                        # warm-up of every shape (buffers grow here)
+        f()
+        t0 = time.perf_counter()
+        f()
+        reps_in[v] = max(1, int(a.window / (time.perf_counter() - t0)))
+    T = {v: [] for v in order}
+    for _ in range(a.reps):                           # the variants alternated
+        for v, f in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps_in[v]):
+                f()
+            T[v].append((time.perf_counter() - t0) / reps_in[v] * 1e3)
+    print("# survey leg: device call (host clock around the synchronous entry point: uploads, ONE kernel, downloads) of 256 copies\n"
+          "# of config 1 packed once; ms per call, min / median / max over the windows and the build's own spread (max - min) / min")
+    base = {}
+    # sources a point sees in step s: the wake after the solve + the bound vortices
+    nsrc = s1.n_freevort + np.arange(1, s1.nt) + np.cumsum((s1.LEV_shed[1:] != -1).astype(np.int64)) + s1.Npoints - 1
+    for v in order:
+        which, K = v
+        t = np.array(T[v])
+        if which == "probes":
+            pairs = B * K * int(nsrc.sum() + s1.n_freevort)
+            added = np.median(t) - np.median(base["this build"])
+            print(f"{'this build':<13} B {B:4d}  P {K:5d}  windows of {reps_in[v]:3d}  device call {t.min():9.3f} / {np.median(t):9.3f} / "
+                  f"{t.max():9.3f}  spread {(t.max() - t.min()) / t.min() * 100:5.2f} %\n{'':13} the probe phase on the same rake: added "
+                  f"{added:9.3f} ms per call = {added / (s1.nt - 1) * 1e3:8.3f} us per step; {pairs:.3e} probe pairs, "
+                  f"{pairs / (added * 1e-3):.3e} pairs/s of the added time, which holds the clearing and the return copy of "
+                  f"{2 * B * s1.nt * K * 8 / 2**20:.1f} MiB of probe rows (the survey returns {B * 5 * K * 8 / 2**20:.1f} MiB)", flush=True)
+            continue
+        line = (f"{which:<13} B {B:4d}  K {K:5d}  windows of {reps_in[v]:3d}  device call {t.min():9.3f} / {np.median(t):9.3f} / "
+                f"{t.max():9.3f}  spread {(t.max() - t.min()) / t.min() * 100:5.2f} %")
+        if K == 0:
+            base[which] = t
+        else:
+            pairs = B * K * int(nsrc.sum())
+            added = np.median(t) - np.median(base[which])
+            line += (f"\n{'':13} added {added:9.3f} ms per call = {added / (s1.nt - 1) * 1e3:8.3f} us per sampled step (of every member, "
+                     f"side by side); {pairs:.3e} survey pairs, {pairs / (added * 1e-3):.3e} pairs/s of the added time (the probe phase: "
+                     f"1.65-1.7e11); sums returned {B * 5 * K * 8 / 2**20:.1f} MiB; roll-up pairs of the call {B * pairs_of(s1):.3e}: "
+                     f"K / mean wake size = {K / (nsrc.mean() - s1.Npoints + 1):.2f}")
+        print(line, flush=True)
+    if a.parent_lib:
+        p, n = base["parent build"], base["this build"]
+        print(f"unsurveyed device call, this build against the parent build: median {np.median(n) / np.median(p):.4f} x; the parent's own "
+              f"windows span {p.min():.3f} .. {p.max():.3f} ms, this build's {n.min():.3f} .. {n.max():.3f} ms: "
+              f"{'inside' if p.min() <= np.median(n) <= p.max() else 'OUTSIDE'} the parent's run-to-run spread")
+    else:
+        print("unsurveyed device call against the parent build: NOT MEASURED (no --parent-lib given)")
+
+
+if a.survey_leg:
+    eng.ensemble_run = inner
+    survey_leg()
+    sys.exit(0)
 if a.particles_leg:
     eng.ensemble_run = inner
     particles_leg()
