@@ -5,6 +5,10 @@ streamwise velocity across one station is the picture of the reverse Karman stre
 the foil produces thrust.  (The field is the induced one: no freestream term.)
 
     python examples/wake_survey.py [--periods 3] [--steps-per-period 400] [--k 1.5] [--h 0.25] [--station 2.0] [--plot wake.png]
+                                   [--f32]
+
+--f32: the survey's pair sums in fp32 on local origins (survey_precision='f32': means within 1e-5 of max|u| of the float64
+survey, every other result of the run unchanged) -- the choice for a fine grid over a long run.
 """
 import argparse
 import os
@@ -24,6 +28,7 @@ ap.add_argument("--h", type=float, default=0.25, help="plunge amplitude in chord
 ap.add_argument("--station", type=float, default=2.0, help="x - xpiv of the printed profile")
 ap.add_argument("--dr", type=float, default=0.05)
 ap.add_argument("--plot", default=None, help="write the picture here (needs matplotlib)")
+ap.add_argument("--f32", action="store_true", help="evaluate the survey's field in fp32 (survey_precision='f32')")
 args = ap.parse_args()
 
 period = 2 * np.pi / args.k                                      # chord = Uinf = 1
@@ -37,9 +42,9 @@ grid = dict(xmin=1.0, xmax=4.0, zmin=-1.5, zmax=1.5, dr=args.dr)
 t0 = time.perf_counter()
 sim = LUDVM(t0=0, tf=(steps - 0.5) * dt, dt=dt, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012",
             alpha_max=0, h_max=args.h, k=args.k, verbose=False, history="sparse", survey=grid, survey_frame="tunnel",
-            survey_steps=window)
+            survey_steps=window, survey_precision="f32" if args.f32 else "f64")
 nx, nz = sim.survey_x.shape
-print(f"{sim.nt - 1} steps of dt = {dt:.4g} ({args.steps_per_period} per period), {nx} x {nz} survey points, "
+print(f"{sim.nt - 1} steps of dt = {dt:.4g} ({args.steps_per_period} per period), {nx} x {nz} survey points in {sim.survey_precision}, "
       f"{sim.survey_count} sampled steps = {sim.survey_count / args.steps_per_period:g} periods, {time.perf_counter() - t0:.2f} s")
 
 ix = int(np.argmin(np.abs(sim.survey_x[:, 0] - args.station)))

@@ -460,12 +460,30 @@ int ludvm_march_tracer_state(ludvm_ctx* ctx, double* x, double* z);
  * Guarantee: with a survey set, `rows`, `state`, `hist`, the resident wake, any probe rows and any tracer positions of
  *   ludvm_march_run are bit-identical to a call without it (the survey kernels read the wake and write only buffers of their
  *   own); a call without a survey enqueues exactly what it enqueued before.
- * Limits: one device (not sharded; a sweep has ludvm_ensemble_run_surveyed); float64 sums only; no freestream term. */
+ * Limits: one device (not sharded; a sweep has ludvm_ensemble_run_surveyed); float64 pair sums unless ludvm_march_set_survey_precision
+ *   says otherwise; no freestream term. */
 #define LUDVM_MARCH_MAX_SURVEY 1048576
 int ludvm_march_set_survey(ludvm_ctx* ctx, const double* x, const double* z, size_t count, const double* shift_x,
                            size_t shift_rows, long long first, long long stop, long long every, const double* sums,
                            long long samples);
 int ludvm_march_read_survey(ludvm_ctx* ctx, double* sums, long long* samples);
+
+/* ---- the survey's pair sums in fp32 (an addition to ABI 7: detect it by symbol) --------------------------------
+ *
+ * ludvm_march_set_survey_precision: how the sampled steps evaluate (u, w)_i at the survey points.  0 (the default, and what
+ *   ludvm_march_set_survey and ludvm_march_setup reset it to): float64 pairs, everything above.  1: the pair arithmetic in fp32
+ *   on local origins -- the sources in tiles of 256 slots counted from slot 0, two origin classes of 128 per tile by index
+ *   parity, each referred to the float64 position of its middle member; offsets, point differences (formed in float64, then
+ *   rounded) and a class's 128 pairs in fp32; the class sums, the source splits, the five sums and everything else in
+ *   float64.  A class whose extent (largest |offset| of a member) exceeds 300 v_core is evaluated in float64 instead.  Within
+ *   1e-5 of max|u| of the float64 field for a wake of the march; a quarter of the cost where the classes are compact (a
+ *   long run's rolled-up wake mostly is not: DESIGN.md section 4.11 has the figures).  The sums repeat bit for bit
+ *   however a run is cut into calls, as the float64 ones do, but are not the float64 bits.
+ *   Valid only while a survey is set (LUDVM_E_STATE otherwise); a value other than 0 and 1 is LUDVM_E_ARG and changes nothing.
+ *   It may be called between ludvm_march_run calls: the steps that follow use it.
+ * Guarantee: as ludvm_march_set_survey's -- every other result of ludvm_march_run keeps its bits -- and a context whose
+ *   precision is 0 enqueues exactly what it enqueued before this entry existed. */
+int ludvm_march_set_survey_precision(ludvm_ctx* ctx, int precision);
 
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *

@@ -129,6 +129,7 @@ struct ludvm_ctx {
   bool survey_shifted = false;
   long long survey_first = 1, survey_stop = 0, survey_every = 1;   // sampled steps: first <= i < stop, (i - first) % every == 0
   long long survey_samples = 0;                // sampled steps the sums hold
+  int survey_precision = 0;                    // 0: float64 pair sums; 1: fp32 on local origins (ludvm_march_set_survey_precision)
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

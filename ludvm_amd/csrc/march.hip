@@ -25,6 +25,7 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->tracer_rows.clear();
   c->survey_count = 0;      // ... and its survey (ludvm_march_set_survey)
   c->survey_samples = 0;
+  c->survey_precision = 0;
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -237,6 +238,25 @@ size_t survey_slab_bytes(size_t count) {
   return (size_t)survey_want(p.ttiles) * 2 * (size_t)p.k_pad * 8;
 }
 
+// Launch rule of the fp32 survey kernel (march_f32_survey_partial): survey_plan's form and constants with its own point tile
+// (256 lanes x kSurveyF32PerLane).  `chunk` is a multiple of the 256-source tile, so every split starts on a tile -- and
+// origin-class -- boundary counted from slot 0.  A function of K and n_ub alone.
+SurveyPlan survey_plan_f32(size_t count, long long ns_ub) {
+  SurveyPlan p;
+  p.ttiles = ((long long)count + kSurveyF32Tile - 1) / kSurveyF32Tile;
+  p.k_pad = p.ttiles * kSurveyF32Tile;
+  const long long want = survey_want(p.ttiles);
+  ns_ub = std::max<long long>(ns_ub, 1);
+  p.chunk = std::max<long long>(kLocalTile, ((ns_ub + want - 1) / want + kLocalTile - 1) / kLocalTile * kLocalTile);
+  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
+  return p;
+}
+// the fp32 kernel's slab of any step (at most 16 MiB: want x k_pad <= 1024 tiles of 1024 points)
+size_t survey_slab_bytes_f32(size_t count) {
+  const SurveyPlan p = survey_plan_f32(count, 1);
+  return (size_t)survey_want(p.ttiles) * 2 * (size_t)p.k_pad * 8;
+}
+
 // is time step s one of the survey's sampled steps?
 bool survey_samples_step(const ludvm_ctx* c, long long s) {
   return c->survey_count != 0 && s >= c->survey_first && s < c->survey_stop && (s - c->survey_first) % c->survey_every == 0;
@@ -249,13 +269,19 @@ bool survey_samples_step(const ludvm_ctx* c, long long s) {
 int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s) {
   const MarchSetup& m = c->msetup;
   const size_t K = c->survey_count;
-  const SurveyPlan p = survey_plan(K, n_ub + (long long)m.npan);
+  const bool f32 = c->survey_precision == 1;
+  const SurveyPlan p = f32 ? survey_plan_f32(K, n_ub + (long long)m.npan) : survey_plan(K, n_ub + (long long)m.npan);
   const double* pxz = static_cast<const double*>(c->survey_xz.p);
   const double* shift = c->survey_shifted ? static_cast<const double*>(c->survey_shift.p) + s : nullptr;
   double* slab = static_cast<double*>(c->survey_part.p);
-  hipLaunchKernelGGL(march_survey_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
-                     (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
-                     static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  if (f32)
+    hipLaunchKernelGGL(march_f32_survey_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
+                       (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, c->march_vcore, slab);
+  else
+    hipLaunchKernelGGL(march_survey_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
+                       (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad, p.nsplit,
                      (long long)K, static_cast<double*>(c->survey_sums.p));
@@ -287,11 +313,12 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
     if (!std::isfinite(sums[k])) return fail(c, LUDVM_E_ARG, "march: survey sums must be finite");
   c->survey_count = 0;
   c->survey_samples = 0;
+  c->survey_precision = 0;         // float64 until ludvm_march_set_survey_precision says otherwise
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_xz, 2 * count * 8));
   CHK(ensure(c, c->survey_sums, kSurveySums * count * 8));
-  CHK(ensure(c, c->survey_part, survey_slab_bytes(count)));
+  CHK(ensure(c, c->survey_part, std::max(survey_slab_bytes(count), survey_slab_bytes_f32(count))));   // either precision's
   if (shift_x) CHK(ensure(c, c->survey_shift, shift_rows * 8));
   double* pxz = static_cast<double*>(c->survey_xz.p);
   HIPCHK(c, hipMemcpyAsync(pxz, x, count * 8, hipMemcpyHostToDevice, c->stream));
@@ -306,6 +333,14 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
   c->survey_every = every;
   c->survey_samples = sums ? samples : 0;
   c->survey_count = count;
+  return LUDVM_OK;
+}
+
+int ludvm_march_set_survey_precision(ludvm_ctx* c, int precision) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  if (precision != 0 && precision != 1) return fail(c, LUDVM_E_ARG, "march: survey precision is 0 (float64) or 1 (fp32)");
+  c->survey_precision = precision;
   return LUDVM_OK;
 }
 

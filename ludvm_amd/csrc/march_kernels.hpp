@@ -785,6 +785,170 @@ march_survey_partial(const double* __restrict__ px, const double* __restrict__ p
   }
 }
 
+// ---- the survey's field in fp32 on local origins (ludvm_march_set_survey_precision) ------------------------------------------------
+// The same quantity as march_survey_partial into the same slab, with the pair arithmetic in fp32 (pair2_f32: pair_f32's, packed
+// over sources) and everything around it in float64.  It reads the float64 master arrays and makes its own offsets, so it
+// depends neither on the resident wake's fp32 mirrors nor on the finishers' origin tables:
+//   tiles    256 consecutive source slots at 256-aligned indices counted from slot 0 (`chunk` is a multiple of 256); a tile holds
+//            two origin CLASSES of 128 by index parity (TEV and LEV each sit on one parity)
+//   origin   of a class: the float64 position of its middle valid member (member cnt / 2 of cnt; a class without a member
+//            borrows the tile's slot 0).  LDS holds (float)(xs - ox), (float)(zs - oz), (float)G; slots past the end are
+//            pair_f32's padding (kPadPosF, G = 0: exactly 0)
+//   points   each lane forms (float)(xp - ox), (float)(zp - oz) once per class and point, the subtraction in float64: the low
+//            half of the packed operand is referred to the even class's origin, the high half to the odd one's
+//   sums     two levels: a class's 128 pairs in fp32 registers (the halves of the packed accumulators ARE the two class sums),
+//            then class 0 and class 1, in that order, added to the lane's float64 (u, w)
+//   guard    while staging, the workgroup reduces each class's extent, max over its members of max(|x offset|, |z offset|); a
+//            class whose extent exceeds kSurveyF32MaxExtent x v_core is struck from the fp32 tile (padding) and evaluated by
+//            march_survey_partial's float64 loop on the float64 values instead -- a sparse set has no neighbours within a few
+//            cores whose differences need the precision, but an fp32 offset of that size no longer resolves the core
+//            (DESIGN section 3's calibration).  The branch is uniform over the workgroup
+// One lane forms every partial sum in tile order, the class sums in class order: with survey_plan_f32 (march.hip) a function of
+// K and the step's bound alone, the sums repeat bit for bit however a run is cut into calls.
+// local_field_f32 is the body: PPL points of the lane (xd, zd: float64; a lane without a point passes -kPadPosF, away
+// from the sources' padding) against the
+// sources [s_begin, s_end), s_begin a multiple of 256 -> au += sum G dz / sqrt(r^4 + vc^4), aw += sum G dx / sqrt(..) (no
+// 1 / 2 pi, no sign).  Every lane of the workgroup calls it (barriers inside).
+constexpr int kSurveyF32PerLane = 4;
+constexpr int kSurveyF32Tile = kBlock * kSurveyF32PerLane;
+constexpr int kLocalTile = 256;                    // = kOriginBlock: two classes of 128
+constexpr double kSurveyF32MaxExtent = 300.0;      // in units of v_core
+
+template <int PPL>
+__device__ __forceinline__ void local_field_f32(const double (&xd)[PPL], const double (&zd)[PPL], const double* __restrict__ xs,
+                                                const double* __restrict__ zs, const double* __restrict__ gs, long long s_begin,
+                                                long long s_end, double vc4, float max_extent, double (&au)[PPL],
+                                                double (&aw)[PPL]) {
+  static_assert(kLocalTile == kBlock, "one source slot per lane");
+  __shared__ __attribute__((aligned(16))) double mx[kLocalTile];     // the tile's float64 values: origins, and the guard's loop
+  __shared__ __attribute__((aligned(16))) double mz[kLocalTile];
+  __shared__ __attribute__((aligned(16))) double mg[kLocalTile];
+  __shared__ __attribute__((aligned(16))) float lx[kLocalTile];      // offsets from the class origins
+  __shared__ __attribute__((aligned(16))) float lz[kLocalTile];
+  __shared__ __attribute__((aligned(16))) float lg[kLocalTile];
+  __shared__ float lext[kBlock / 64][2];
+  const int tid = threadIdx.x, par = tid & 1;
+  const float vc4s = (float)vc4;
+  const f32x2 vc4p = {vc4s, vc4s};
+  for (long long base = s_begin; base < s_end; base += kLocalTile) {
+    __syncthreads();                                // previous tile fully consumed
+    const long long si = base + tid;
+    const bool ok = si < s_end;
+    const double x = ok ? xs[si] : kPadPosD, z = ok ? zs[si] : kPadPosD, g = ok ? gs[si] : 0.0;
+    mx[tid] = x; mz[tid] = z; mg[tid] = g;
+    __syncthreads();
+    // the classes' middle valid members (uniform)
+    const int nv = (int)(s_end - base < kLocalTile ? s_end - base : kLocalTile);       // >= 1
+    const int cnt0 = (nv + 1) >> 1, cnt1 = nv >> 1;
+    const int oi0 = 2 * (cnt0 >> 1), oi1 = cnt1 ? 1 + 2 * (cnt1 >> 1) : 0;
+    const double ox0 = mx[oi0], oz0 = mz[oi0], ox1 = mx[oi1], oz1 = mz[oi1];
+    {
+      const float fx = ok ? (float)(x - (par ? ox1 : ox0)) : kPadPosF;
+      const float fz = ok ? (float)(z - (par ? oz1 : oz0)) : kPadPosF;
+      lx[tid] = fx; lz[tid] = fz; lg[tid] = (float)g;
+      // strides 2 .. 32 keep the lane parity: lanes 0 / 1 of each wavefront end up with the even / odd class's extent
+      float e = ok ? fmaxf(fabsf(fx), fabsf(fz)) : 0.0f;
+      for (int s = 2; s < 64; s <<= 1) e = fmaxf(e, __shfl_xor(e, s));
+      if ((tid & 63) < 2) lext[tid >> 6][tid & 63] = e;
+    }
+    __syncthreads();
+    float e0 = 0.0f, e1 = 0.0f;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) { e0 = fmaxf(e0, lext[w][0]); e1 = fmaxf(e1, lext[w][1]); }
+    // bit p: class p takes the float64 loop (the same value in every lane: say so, the branches below hold barriers)
+    const int guard = __builtin_amdgcn_readfirstlane((e0 > max_extent ? 1 : 0) | (e1 > max_extent ? 2 : 0));
+    if (guard != 0) {
+      if ((guard >> par) & 1) { lx[tid] = kPadPosF; lz[tid] = kPadPosF; lg[tid] = 0.0f; }
+      __syncthreads();
+    }
+    f32x2 tu[PPL], tw[PPL];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) { tu[k] = (f32x2){0.0f, 0.0f}; tw[k] = (f32x2){0.0f, 0.0f}; }
+    if (guard != 3) {
+      f32x2 xp[PPL], zp[PPL];
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) {
+        xp[k] = (f32x2){(float)(xd[k] - ox0), (float)(xd[k] - ox1)};
+        zp[k] = (f32x2){(float)(zd[k] - oz0), (float)(zd[k] - oz1)};
+      }
+#pragma unroll 2
+      for (int j = 0; j < kLocalTile; j += 4) {
+        const f32x4 X = *reinterpret_cast<const f32x4*>(&lx[j]);
+        const f32x4 Z = *reinterpret_cast<const f32x4*>(&lz[j]);
+        const f32x4 G = *reinterpret_cast<const f32x4*>(&lg[j]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const f32x2 xs2 = h ? (f32x2){X.z, X.w} : (f32x2){X.x, X.y};
+          const f32x2 zs2 = h ? (f32x2){Z.z, Z.w} : (f32x2){Z.x, Z.y};
+          const f32x2 gs2 = h ? (f32x2){G.z, G.w} : (f32x2){G.x, G.y};
+#pragma unroll
+          for (int k = 0; k < PPL; ++k) pair2_f32(xp[k] - xs2, zp[k] - zs2, gs2, vc4p, tu[k], tw[k]);
+        }
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if ((guard >> p) & 1) {
+        double cu[PPL], cw[PPL];
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) { cu[k] = 0.0; cw[k] = 0.0; }
+        for (int j = p; j < kLocalTile; j += 2) {
+          const double sx = mx[j], sz = mz[j], sg = mg[j];
+#pragma unroll
+          for (int k = 0; k < PPL; ++k) {
+            const double dx = xd[k] - sx;
+            const double dz = zd[k] - sz;
+            const double r2 = __builtin_fma(dz, dz, dx * dx);
+            const double q = __builtin_fma(r2, r2, vc4);
+            const double s = sg * rsqrt_f64(q);
+            cu[k] = __builtin_fma(dz, s, cu[k]);
+            cw[k] = __builtin_fma(dx, s, cw[k]);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) { au[k] += cu[k]; aw[k] += cw[k]; }
+      } else {
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) { au[k] += (double)(p ? tu[k].y : tu[k].x); aw[k] += (double)(p ? tw[k].y : tw[k].x); }
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_f32_survey_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, long long count,
+                         long long k_pad, const double* __restrict__ xs, const double* __restrict__ zs,
+                         const double* __restrict__ gs, const MarchState* S, int nfoil, long long chunk, double vc4, double v_core,
+                         double* slab) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long t0 = (long long)blockIdx.x * kSurveyF32Tile + threadIdx.x;
+  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
+  const long long s_begin = (long long)blockIdx.y * chunk;
+  long long s_end = s_begin + chunk;
+  if (s_end > ns) s_end = ns;
+  const double sh = shift ? *shift : 0.0;
+  double xp[kSurveyF32PerLane], zp[kSurveyF32PerLane], au[kSurveyF32PerLane], aw[kSurveyF32PerLane];
+#pragma unroll
+  for (int k = 0; k < kSurveyF32PerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    const bool on = m < count;
+    xp[k] = on ? px[m] + sh : -(double)kPadPosF;
+    zp[k] = on ? pz[m] : -(double)kPadPosF;
+    au[k] = 0.0; aw[k] = 0.0;
+  }
+  local_field_f32<kSurveyF32PerLane>(xp, zp, xs, zs, gs, s_begin, s_end, vc4, (float)(kSurveyF32MaxExtent * v_core), au, aw);
+  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
+  double* row = slab + (long long)blockIdx.y * 2 * k_pad;
+#pragma unroll
+  for (int k = 0; k < kSurveyF32PerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    if (m < count) {
+      row[m] = au[k] * kInv2PiD;
+      row[k_pad + m] = -aw[k] * kInv2PiD;
+    }
+  }
+}
+
 __global__ void __launch_bounds__(kBlock)
 march_survey_finish(const double* slab, long long k_pad, int nsplit, long long count, double* sums) {
   __builtin_amdgcn_s_setprio(3);

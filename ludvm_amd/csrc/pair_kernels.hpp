@@ -108,6 +108,19 @@ __device__ __forceinline__ void grid_point(const PairArgs& a, long long p, doubl
   z = a.zmin + (double)j * a.dr;
 }
 
+// Two fp32 pairs of one target in one packed instruction stream: the halves of dx / dz are the target's differences to two
+// sources (j and j + 1), gs2 their circulations, vc4 = v_core^4 in both halves; tu += dz G / sqrt(r^4 + vc^4), tw += dx G /
+// sqrt(r^4 + vc^4) per half.  6 v_pk_*_f32 + 2 v_rsq_f32 (8 packed with the two differences the caller forms).
+__device__ __forceinline__ void pair2_f32(f32x2 dx, f32x2 dz, f32x2 gs2, f32x2 vc4, f32x2& tu, f32x2& tw) {
+  f32x2 r2 = dx * dx;
+  r2 = __builtin_elementwise_fma(dz, dz, r2);
+  const f32x2 q = __builtin_elementwise_fma(r2, r2, vc4);
+  f32x2 s = {__builtin_amdgcn_rsqf(q.x), __builtin_amdgcn_rsqf(q.y)};
+  s = s * gs2;
+  tu = __builtin_elementwise_fma(dz, s, tu);
+  tw = __builtin_elementwise_fma(dx, s, tw);
+}
+
 // ---------------------------------------------------------------------------------------------
 // fp32, packed over sources.  TPL = targets per lane, TILE = sources per LDS tile.
 // HILO = false: plain fp32 positions.
@@ -326,13 +339,7 @@ pair_f32(PairArgs a) {
             dx = dx + (xpl[t] - xl2);
             dz = dz + (zpl[t] - zl2);
           }
-          f32x2 r2 = dx * dx;
-          r2 = __builtin_elementwise_fma(dz, dz, r2);
-          const f32x2 q = __builtin_elementwise_fma(r2, r2, vc4);
-          f32x2 s = {__builtin_amdgcn_rsqf(q.x), __builtin_amdgcn_rsqf(q.y)};
-          s = s * gs2;
-          tu[t] = __builtin_elementwise_fma(dz, s, tu[t]);
-          tw[t] = __builtin_elementwise_fma(dx, s, tw[t]);
+          pair2_f32(dx, dz, gs2, vc4, tu[t], tw[t]);
         }
       }
     }

@@ -483,6 +483,17 @@ class Engine:
                                                      int(first), stop, int(every), _pd(sm), int(samples)))
         self._march_nsurvey = len(xs)
 
+    def march_set_survey_precision(self, precision):
+        """How the marched steps evaluate the survey's field (ludvm_march_set_survey_precision): 'f64' (what `march_set_survey`
+        leaves) or 'f32' -- fp32 pair arithmetic on local origins, float64 class sums, splits and moments -- or the library's
+        own code (0 / 1; anything else is the library's LUDVM_E_ARG).  Valid while a survey is set."""
+        if not hasattr(self._lib, "ludvm_march_set_survey_precision"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_survey_precision")
+        code = _ffi.SURVEY_PRECISIONS.get(precision, precision) if isinstance(precision, str) else precision
+        if isinstance(code, bool) or not isinstance(code, int):
+            raise ValueError("march_set_survey_precision: 'f64' or 'f32' (or the library's code)")
+        self._check(self._lib.ludvm_march_set_survey_precision(self._ctx, code))
+
     def march_survey(self):
         """(sums float64 [5, K], samples): the survey's raw sums -- u, w, u^2, w^2, u w per point -- and the number of sampled
         steps they hold (ludvm_march_read_survey)."""

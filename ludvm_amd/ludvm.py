@@ -135,12 +135,22 @@ class LUDVM:
                  second moments `survey_uu`, `survey_ww`, `survey_uw` = sum(ab)/n - (sum(a)/n)(sum(b)/n) (the Reynolds
                  stresses of the time-averaged wake); `survey_frame`, `survey_steps` as used.  No freestream term.  Every
                  other result is unchanged, bit for bit; the sums repeat bit for bit however the run is cut (chunks,
-                 snapshot_steps, history, checkpoint / resume).  A sweep takes it as sweep(..., survey=).  Out of scope: a survey on several GPUs, fp32
-                 sums, field snapshots (`flowfield` on snapshot_steps), thrust integration
+                 snapshot_steps, history, checkpoint / resume).  A sweep takes it as sweep(..., survey=).  Out of scope: a survey on
+                 several GPUs, fp32 sums in a sweep, field snapshots (`flowfield` on snapshot_steps), thrust integration
       survey_frame  'lab' (default): the points are fixed in the lab frame; 'tunnel': x is measured from the pivot's
                  x-coordinate -- in step i point k sits at (x[k] + xpiv[i], z[k])
       survey_steps  (first, stop, every): the sampled steps are first <= i < stop with (i - first) % every == 0; first >= 1,
                  every >= 1, stop is clipped to nt; default (1, nt, 1).  An empty window is refused
+      survey_precision  'f64' (default): the survey's pair sums in float64.  'f32': the pair arithmetic in fp32 on local origins,
+                 inside the device-resident march only -- the sources in tiles of 256, two origin classes of 128 per tile by index
+                 parity, each referred to the float64 position of its middle member; a class's 128 pairs summed in fp32, the
+                 class sums, the source splits and the five moments in float64; a class wider than 300 v_core is evaluated in
+                 float64.  Means within 1e-5 of max|u| of the 'f64' survey, raw second moments within 3e-5 of max|u|^2, at a
+                 quarter of the cost per sampled step where the classes are compact and 0.8 of it on a long run's rolled-up
+                 wake; every other result keeps its bits, and the sums repeat bit for bit
+                 however the run is cut, checkpoints included (they carry the value).  Refused: without `survey`, with
+                 march=False, in a sweep; a run that cannot take the march raises instead of falling back to float64.  The
+                 object carries `survey_precision` as used
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -248,6 +258,16 @@ class LUDVM:
         return np.ascontiguousarray(xz), shape, (first, stop, every)
 
     @staticmethod
+    def _check_survey_precision(survey_precision, surveyed, march=True):
+        """ValueError from the keywords alone (nothing else has been created yet)."""
+        if not isinstance(survey_precision, str) or survey_precision not in ('f64', 'f32'):
+            raise ValueError(f"survey_precision must be 'f64' or 'f32' (got {survey_precision!r})")
+        if survey_precision != 'f64' and not surveyed:
+            raise ValueError("survey_precision needs `survey`")
+        if survey_precision == 'f32' and not march:
+            raise ValueError("survey_precision='f32' is evaluated inside the device-resident march: not with march=False")
+
+    @staticmethod
     def _check_tracers(tracers, tracer_release, tracer_frame, tracer_steps=None, nt=None):
         """-> (float64 [2, M], int64 [M], sorted steps or None), or ValueError (nothing else has been created yet)."""
         if tracer_frame not in ('lab', 'tunnel'):
@@ -297,7 +317,7 @@ class LUDVM:
                  engine=None, device=0, precision='auto', history='auto', snapshot_steps=(), run=True,
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
                  probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
-                 survey=None, survey_frame='lab', survey_steps=None):
+                 survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64'):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -325,6 +345,7 @@ class LUDVM:
             raise ValueError("survey_frame must be 'lab' or 'tunnel'")
         elif survey_steps is not None:
             raise ValueError("survey_steps needs `survey`")
+        self._check_survey_precision(survey_precision, survey is not None, march)
         # the smallest section the method runs: two panels; the loads read A0 .. A3 (LUDVM.py:1035-1090)
         if Npoints < 3:
             raise ValueError(f"Npoints={Npoints}: a section has at least 3 points (2 panels)")
@@ -351,6 +372,9 @@ class LUDVM:
             self._survey_xz, self._survey_shape = survey_xz, survey_shape
             self.survey_x, self.survey_z = survey_xz[0].reshape(survey_shape), survey_xz[1].reshape(survey_shape)
             self.survey_frame, self.survey_steps = survey_frame, survey_win
+            self.survey_precision = survey_precision
+            if self.survey_precision != 'f64':      # (a float64 survey keeps the checkpoints it had)
+                self._ctor.update(survey_precision=self.survey_precision)
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -833,6 +857,9 @@ class LUDVM:
             raise RuntimeError("tracers: this engine marches but has no march_set_tracers (pass march=False for the per-step path)")
         if S.survey is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey'):
             raise RuntimeError("survey: this engine marches but has no march_set_survey (pass march=False for the per-step path)")
+        f32_survey = S.survey is not None and self.survey_precision == 'f32'
+        if f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_precision'):
+            raise RuntimeError("survey_precision='f32': this engine marches but has no march_set_survey_precision")
         # preallocated host buffers for the two device calls of a step (engines that offer them)
         S.sb = eng.step_buffers(npan) if hasattr(eng, 'step_buffers') else None
         S.prec_code = {'f32': 0, 'f32x2': 1, 'f64': 2}[self.precision]
@@ -852,6 +879,12 @@ class LUDVM:
             if S.survey is not None:
                 eng.march_set_survey(S.survey[0], S.survey[1], shift_x=self.xpiv if self.survey_frame == 'tunnel' else None,
                                      steps=self.survey_steps, sums=S.ssums if S.scount else None, samples=S.scount)
+                if f32_survey:
+                    eng.march_set_survey_precision('f32')
+        if f32_survey and not S.can_march:
+            # (no float64 in its place: the per-step path has no fp32 survey sums)
+            raise RuntimeError("survey_precision='f32' is evaluated inside the device-resident march, which this run cannot take "
+                               "(an engine without march_run, method, Npoints or Ncoeffs outside its limits)")
         # with the dense history every step's row is recorded: the march then keeps a snapshot of the wake per step on
         # the device (shorter calls, the snapshots are [steps, 2, wake size])
         S.dense_march = S.can_march and self.history == 'full'

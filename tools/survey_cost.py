@@ -1,18 +1,26 @@
 #!/usr/bin/env python3
 """What a wake survey costs (profiles/survey_cost.txt): a marched run with `survey=None` against the parent build, the added
-time per sampled step with K points, and -- from rocprofv3 kernel statistics -- march_survey_partial's pairs/s beside pair_f64's
-on the same shape.
+time per sampled step with K points in both precisions of the survey (survey_precision 'f64' | 'f32', runs alternated in one
+process), and -- from rocprofv3 kernel statistics -- the pairs/s of march_survey_partial and march_f32_survey_partial beside
+pair_f64's and pair_f32's on the same points and wake.
 
     python tools/survey_cost.py ab     --parent-lib LIB [--repeats R]        survey=None: this build and the parent's library
                                                                               loaded in ONE process, runs alternated
-    python tools/survey_cost.py time   --survey K [--repeats R] [--every E]   wall time, added time per sampled step, pair count
-    python tools/survey_cost.py once   --survey K [--induce] [--every E]      one warm-up + one run (under rocprofv3); --induce:
-                                                                              also 5 Engine.induce f64 calls, K points x final wake
+    python tools/survey_cost.py time   --survey K [--repeats R] [--every E] [--first F]
+                                                                              wall time, added time per sampled step and pair
+                                                                              count: a float64 and an fp32 column, and their ratio
+    python tools/survey_cost.py once   --survey K [--induce] [--every E] [--first F]
+                                                                              one run per precision (under rocprofv3); --induce:
+                                                                              also 5 Engine.induce calls in f64 and 5 in f32, K
+                                                                              points x final wake
     python tools/survey_cost.py stats  kernel_stats.csv [--pairs N] [--induce-pairs N]
-                                                                              the survey and pair_f64 kernels' time and pairs/s
+                                                                              the survey and pair kernels' time and pairs/s
+                                                                              (--pairs: of ONE run; each precision runs once)
 
 The run: 5000 steps of config 1's foil at dt = 1e-3, history='sparse', precision='f32' (DESIGN 4.7's 'long' case).  The
-survey: K points of a box behind the trailing edge in the tunnel frame, sampled in every `--every`-th step from step 1."""
+survey: K points of a box behind the trailing edge in the tunnel frame, sampled in every `--every`-th step from step `--first`
+(--steps 17000 --first 16000: every sample sees at least 16 000 sources).  --lespcrit 10 sheds no leading-edge vortex: the wake is
+one trailing-edge sheet, whose origin classes are compact (the fp32 kernel evaluates none of them in float64)."""
 import argparse
 import csv
 import os
@@ -26,6 +34,8 @@ ap.add_argument("mode", choices=["ab", "time", "once", "stats"])
 ap.add_argument("files", nargs="*")
 ap.add_argument("--survey", type=int, default=0)
 ap.add_argument("--every", type=int, default=1)
+ap.add_argument("--first", type=int, default=1)
+ap.add_argument("--lespcrit", type=float, default=0.2, help="10: no leading-edge vortex is shed, the wake is one sheet")
 ap.add_argument("--induce", action="store_true")
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--steps", type=int, default=5000)
@@ -38,7 +48,8 @@ if args.mode == "stats":
     with open(args.files[0]) as f:
         rows = {r["Name"]: (int(r["Calls"]), int(r["TotalDurationNs"])) for r in csv.DictReader(f)}
     for k, (calls, ns) in rows.items():
-        pairs = {"march_survey_partial": args.pairs, "pair_f64<": args.induce_pairs}
+        pairs = {"march_survey_partial": args.pairs, "march_f32_survey_partial": args.pairs, "pair_f64<": args.induce_pairs,
+                 "pair_f32<": args.induce_pairs}
         hit = [p for name, p in pairs.items() if name in k]
         if "march_survey" in k or (hit and "pair_f64_few" not in k):
             rate = f", {hit[0] / (ns * 1e-9):.3g} pairs/s" if hit and hit[0] else ""
@@ -48,7 +59,7 @@ if args.mode == "stats":
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ludvm_amd import LUDVM, Engine  # noqa: E402
 
-kw = dict(t0=0, tf=args.steps * 1e-3, dt=1e-3, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012",
+kw = dict(t0=0, tf=args.steps * 1e-3, dt=1e-3, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=args.lespcrit, Naca="0012",
           history="sparse", precision="f32")
 
 
@@ -57,8 +68,9 @@ def box(K):
     return np.stack([rng.uniform(0.75, 4.75, K), rng.uniform(-2.0, 2.0, K)])
 
 
-def extras(K):
-    return dict(survey=box(K), survey_frame="tunnel", survey_steps=(1, 10 ** 9, args.every)) if K else {}
+def extras(K, precision="f64"):
+    return dict(survey=box(K), survey_frame="tunnel", survey_steps=(args.first, 10 ** 9, args.every),
+                survey_precision=precision) if K else {}
 
 
 def run(eng, **extra):
@@ -71,6 +83,22 @@ def sources_per_step(sim):
     """Sources of step i's field: the wake after the step's solve plus the bound vortices."""
     shed = np.cumsum(sim.LEV_shed != -1)
     return sim.n_freevort + np.arange(sim.nt) + shed + sim.Npoints - 1
+
+
+def guarded_classes(eng, v_core, limit=300.0):
+    """(classes of the resident wake wider than limit x v_core, classes, median width / v_core): the fp32 kernel's origin classes
+    -- tiles of 256 slots, even and odd slots, width = largest |offset| from the middle member -- as NumPy restates them."""
+    n = eng.wake_size()
+    x, z = eng.wake_read(0, n)[:2]
+    ext = []
+    for base in range(0, n, 256):
+        for par in (0, 1):
+            idx = np.arange(base + par, min(base + 256, n), 2)
+            if len(idx):
+                mid = idx[len(idx) // 2]
+                ext.append(max(np.abs(x[idx] - x[mid]).max(), np.abs(z[idx] - z[mid]).max()) / v_core)
+    ext = np.array(ext)
+    return int((ext > limit).sum()), len(ext), float(np.median(ext))
 
 
 def spread(ts):
@@ -94,35 +122,45 @@ if args.mode == "ab":
     sys.exit(0)
 
 eng = Engine(0)
-extra = extras(args.survey)
 if args.mode == "once":
-    run(eng, **extra)
-    t, sim = run(eng, **extra)
-    ns = sources_per_step(sim)
-    sampled = np.arange(1, sim.nt, args.every)
-    pairs = float(args.survey) * float(ns[sampled].sum())
-    print(f"K={args.survey} every={args.every}: {t:.4f} s, {sim.nt - 1} steps, {len(sampled)} sampled, final wake {eng.wake_size()}; "
-          f"{pairs:.6g} survey pairs per run, {2 * pairs:.6g} for the two runs of this process")
+    run(eng)
+    for prec in ("f64", "f32"):
+        t, sim = run(eng, **extras(args.survey, prec))
+        ns = sources_per_step(sim)
+        sampled = np.arange(args.first, sim.nt, args.every)
+        pairs = float(args.survey) * float(ns[sampled].sum())
+        print(f"K={args.survey} every={args.every} first={args.first} {prec}: {t:.4f} s, {sim.nt - 1} steps, {len(sampled)} sampled, "
+              f"sources {ns[sampled].min()} .. {ns[sampled].max()}, final wake {eng.wake_size()}; {pairs:.6g} survey pairs in this run")
     if args.induce:
         n = eng.wake_size()
         x, z, g = eng.wake_read(0, n, gamma=True)
         px, pz = box(args.survey)
-        for _ in range(5):
-            eng.induce(g, x, z, px + sim.xpiv[-1], pz, sim.v_core, precision="f64")
-        print(f"Engine.induce f64: 5 calls of {args.survey} points x {n} sources = {5.0 * args.survey * n:.6g} pairs")
+        for prec in ("f64", "f32"):
+            for _ in range(5):
+                eng.induce(g, x, z, px + sim.xpiv[-1], pz, sim.v_core, precision=prec)
+        print(f"Engine.induce: 5 calls in f64 and 5 in f32 of {args.survey} points x {n} sources = {5.0 * args.survey * n:.6g} pairs each")
 else:
     run(eng)
-    run(eng, **extra)
-    t0s, t1s = [], []
+    for prec in ("f64", "f32"):
+        run(eng, **extras(args.survey, prec))
+    ts = {"plain": [], "f64": [], "f32": []}
     for _ in range(args.repeats):
-        t0s.append(run(eng)[0])
-        t, sim = run(eng, **extra)
-        t1s.append(t)
+        ts["plain"].append(run(eng)[0])
+        for prec in ("f64", "f32"):
+            t, sim = run(eng, **extras(args.survey, prec))
+            ts[prec].append(t)
     ns = sources_per_step(sim)
-    sampled = np.arange(1, sim.nt, args.every)
-    m0, m1 = sorted(t0s)[len(t0s) // 2], sorted(t1s)[len(t1s) // 2]
+    sampled = np.arange(args.first, sim.nt, args.every)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
     pairs = float(args.survey) * float(ns[sampled].sum())
-    print(f"plain:            {spread(t0s)}")
-    print(f"K={args.survey} every={args.every}: {spread(t1s)}")
-    print(f"added: {m1 - m0:.4f} s = {(m1 - m0) / len(sampled) * 1e6:.2f} us per sampled step ({len(sampled)} of {sim.nt - 1} steps); "
-          f"{pairs:.6g} survey pairs, {pairs / max(m1 - m0, 1e-9):.3g} pairs/s of the added time")
+    print(f"{sim.nt - 1} steps, K={args.survey}, {len(sampled)} sampled steps (first {args.first}, every {args.every}), sources "
+          f"{ns[sampled].min()} .. {ns[sampled].max()}, {pairs:.6g} survey pairs")
+    print(f"plain:       {spread(ts['plain'])}")
+    for prec in ("f64", "f32"):
+        add = med[prec] - med["plain"]
+        print(f"survey {prec}:  {spread(ts[prec])}; added {add:.4f} s = {add / len(sampled) * 1e6:.2f} us per sampled step, "
+              f"{pairs / max(add, 1e-9):.3g} pairs/s of the added time")
+    wide, classes, median = guarded_classes(eng, sim.v_core)
+    print(f"origin classes of the final wake wider than 300 v_core (evaluated in float64 by the fp32 kernel): {wide} of {classes}; "
+          f"median width {median:.0f} v_core")
+    print(f"added time per sampled step, f32 / f64: {(med['f32'] - med['plain']) / max(med['f64'] - med['plain'], 1e-9):.3f}")
