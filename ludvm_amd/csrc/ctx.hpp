@@ -295,7 +295,7 @@ inline bool too_sparse(double mean_extent, bool reordered, double vcore) {
 
 // ---- wake.hip -----------------------------------------------------------------------------------------------------------
 int wake_grow(ludvm_ctx* c, size_t capacity);
-int wake_refresh(ludvm_ctx* c, size_t first, size_t count);
+int wake_refresh(ludvm_ctx* c, size_t first, size_t count, bool staged = false);
 inline unsigned fin_blocks(long long n) { return (unsigned)((n + kFinBlock - 1) / kFinBlock); }
 // (march) where a symmetric launch sized from an upper bound finds its scale and how small the wake may be
 struct MarchSym { const SymScale* scale = nullptr; long long* bad = nullptr; long long n_lo = 0; bool march = false; };

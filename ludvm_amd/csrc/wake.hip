@@ -50,13 +50,15 @@ int wake_grow(ludvm_ctx* c, size_t capacity) {
 }
 
 // Rebuild the fp32 mirrors of [first, first + count) -- and of the rest of the origin blocks they touch -- from the
-// float64 masters.
-int wake_refresh(ludvm_ctx* c, size_t first, size_t count) {
+// float64 masters.  `staged`: the range holds one roll-up's bound vortices behind the wake, which lend no origin to a block
+// of the wake (refresh_mirrors).
+int wake_refresh(ludvm_ctx* c, size_t first, size_t count, bool staged) {
   if (!count) return LUDVM_OK;
+  const size_t stored = std::max(c->wake_n, first + count);
   const long long lo = (long long)(first / kOriginBlock * kOriginBlock);
   const long long hi = std::min<long long>((long long)c->wake_cap, (long long)((first + count + kOriginBlock - 1) / kOriginBlock * kOriginBlock));
   hipLaunchKernelGGL(refresh_mirrors, dim3(blocks_for(hi - lo)), dim3(kBlock), 0, c->stream, (long long)first, (long long)count,
-                     (long long)std::max(c->wake_n, first + count), (long long)c->wake_cap, c->x64, c->z64, c->g64, c->mir(), c->g32);
+                     (long long)stored, (long long)(staged ? c->wake_n : stored), (long long)c->wake_cap, c->x64, c->z64, c->g64, c->mir(), c->g32);
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
 }
@@ -313,7 +315,7 @@ int ludvm_wake_advect(ludvm_ctx* c, double dt, const double* foil_x, const doubl
     CHK(h2d(c, c->x64 + n, foil_x, nfoil * 8));
     CHK(h2d(c, c->z64 + n, foil_z, nfoil * 8));
     CHK(h2d(c, c->g64 + n, foil_dgamma, nfoil * 8));
-    CHK(wake_refresh(c, n, nfoil));
+    CHK(wake_refresh(c, n, nfoil, true));
   }
   double *du = nullptr, *dw = nullptr;
   if (u_out) {

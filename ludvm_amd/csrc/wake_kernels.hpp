@@ -7,13 +7,35 @@
 
 namespace ludvm {
 
+// Which wake vortex lends class (b, p) its origin while bound vortices are staged behind the n vortices of the wake
+// (n > 256 b).  The bound vortices lie up to a chord from the wake's newest vortices: were the newest or the middle ENTRY
+// of the block one of them, the wake's offsets there would be of the order of the chord, not of the vortex spacing, so
+// the choice is origin_index over the wake alone -- what the Euler finisher republishes.  A vortex of zero strength is a
+// target only and may lie anywhere (the time loop convects one from the origin of the plane on a step that sheds no
+// leading-edge vortex, as the wake's last entry): an older member of its class, else of the block's other class, lends the
+// origin instead, and where the block holds no wake vortex with a strength the choice falls on the `stored` entries as a whole.
+__device__ __forceinline__ long long staged_lender(long long b, int p, long long n, long long stored, const double* g64) {
+  const long long first = b << kOriginShift;
+  long long pick = -1;
+#pragma unroll
+  for (int t = 0; t < 2 && pick < 0; ++t) {
+    long long oi = origin_index(b, p ^ t, n);
+    while (g64[oi] == 0.0 && oi - 2 >= first) oi -= 2;
+    if (g64[oi] != 0.0) pick = oi;
+  }
+  return pick >= 0 ? pick : origin_index(b, p, stored);
+}
+
 // Rebuild the fp32 mirrors of every origin block that intersects [first, first + count) from the float64
 // masters (after a host write): the block's two origins are re-taken (origin_index over the `stored` entries), so the
 // whole block is refreshed.  Entries of a touched block that lie beyond the stored range are computed from whatever
 // the master arrays hold there and are never read.  `limit` = allocated capacity.
+// `owners` < stored: the entries behind the first `owners` -- the wake -- are one roll-up's bound vortices, and only
+// the wake lends an origin to a block it reaches into (staged_lender); a block past the wake takes its origins from
+// what is staged in it.
 __global__ void __launch_bounds__(kBlock)
-refresh_mirrors(long long first, long long count, long long stored, long long limit, const double* x64, const double* z64,
-                const double* g64, Mirrors m, float* g32) {
+refresh_mirrors(long long first, long long count, long long stored, long long owners, long long limit, const double* x64,
+                const double* z64, const double* g64, Mirrors m, float* g32) {
   const long long lo = (first >> kOriginShift) << kOriginShift;
   const long long i = lo + (long long)blockIdx.x * kBlock + threadIdx.x;
   long long hi = ((first + count + kOriginBlock - 1) >> kOriginShift) << kOriginShift;
@@ -21,7 +43,7 @@ refresh_mirrors(long long first, long long count, long long stored, long long li
   if (i >= hi) return;
   const long long b = i >> kOriginShift;
   const int p = (int)(i & 1);
-  const long long oi = origin_index(b, p, stored);
+  const long long oi = (owners < stored && (b << kOriginShift) < owners) ? staged_lender(b, p, owners, stored, g64) : origin_index(b, p, stored);
   const float ox = (float)x64[oi], oz = (float)z64[oi];
   if ((i & (kOriginBlock - 1)) < 2) { m.cx[2 * b + p] = ox; m.cz[2 * b + p] = oz; }      // the first thread of each class
   store_mirrors(m, i, x64[i], z64[i], ox, oz);
