@@ -3,7 +3,10 @@
 a held tracer translates with the pivot; staggered tracer_release: one particle per rake point every k steps).  At the end
 of the run the particles of one rake point, in release order, are that point's streakline.
 
-    python examples/streaklines.py [--tf 10] [--dt 1e-2] [--every 5] [--rake 7] [--plot streaklines.png]
+    python examples/streaklines.py [--tf 10] [--dt 1e-2] [--every 5] [--rake 7] [--plot streaklines.png] [--f32x2]
+
+--f32x2: the tracers' pair sums in fp32 on hi+lo positions (tracer_precision='f32x2': velocities within 2e-6 of max|u| of the
+float64 ones, every other result of the run unchanged) -- the choice for many particles over a long run.
 """
 import argparse
 import os
@@ -21,6 +24,7 @@ ap.add_argument("--dt", type=float, default=1e-2)
 ap.add_argument("--every", type=int, default=5, help="release a particle from every rake point each so many steps")
 ap.add_argument("--rake", type=int, default=7, help="points of the rake")
 ap.add_argument("--plot", default=None, help="write the picture here (needs matplotlib)")
+ap.add_argument("--f32x2", action="store_true", help="advect the tracers with hi+lo fp32 pair sums (tracer_precision='f32x2')")
 args = ap.parse_args()
 
 nt = len(np.arange(0, args.tf + args.dt, args.dt))
@@ -33,9 +37,10 @@ release = np.tile(releases, args.rake)                           # tracer p * le
 
 t0 = time.perf_counter()
 sim = LUDVM(t0=0, tf=args.tf, dt=args.dt, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012",
-            verbose=False, history="sparse", tracers=seeds, tracer_release=release, tracer_frame="tunnel")
+            verbose=False, history="sparse", tracers=seeds, tracer_release=release, tracer_frame="tunnel",
+            tracer_precision="f32x2" if args.f32x2 else "f64")
 last = sim.nt - 1
-print(f"{last} steps, {seeds.shape[1]} tracers ({args.rake} rake points x {len(releases)} releases), "
+print(f"{last} steps, {seeds.shape[1]} tracers ({args.rake} rake points x {len(releases)} releases) in {sim.tracer_precision}, "
       f"{time.perf_counter() - t0:.2f} s; tracer rows kept: {sim.tracer_path.steps()}")
 
 end = sim.tracer_path[last].reshape(2, args.rake, len(releases))   # [x | z, rake point, release]

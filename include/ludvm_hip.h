@@ -425,13 +425,31 @@ int ludvm_march_read_probes(ludvm_ctx* ctx, double* u, double* w, size_t rows);
  *   with the last step's offset) -- for checkpoints and the final state.  LUDVM_E_STATE when no tracers are set.
  * Guarantee: with tracers set, `rows`, `state`, `hist`, the resident wake and any probe rows of ludvm_march_run are
  *   bit-identical to a call without them (the tracer kernels read the wake and write only buffers of their own).
- * Limits: one device (not sharded; a sweep has ludvm_ensemble_run_traced); float64 sums only; tracers do not interact with the foil. */
+ * Limits: one device (not sharded; a sweep has ludvm_ensemble_run_traced); float64 pair sums unless ludvm_march_set_tracer_precision
+ *   says otherwise; tracers do not interact with the foil. */
 #define LUDVM_MARCH_MAX_TRACERS 262144
 int ludvm_march_set_tracers(ludvm_ctx* ctx, const double* seed_x, const double* seed_z, const long long* release, size_t count,
                             const double* shift_x, size_t shift_rows, const double* cur_x, const double* cur_z,
                             const long long* record_steps, size_t nrecord);
 int ludvm_march_read_tracers(ludvm_ctx* ctx, double* x, double* z, size_t rows_cap, long long* steps_out, size_t* nrows_out);
 int ludvm_march_tracer_state(ludvm_ctx* ctx, double* x, double* z);
+
+/* ---- the tracers' pair sums in hi+lo fp32 (an addition to ABI 7: detect it by symbol) ---------------------------
+ *
+ * ludvm_march_set_tracer_precision: how the marched steps evaluate (u, w)_i at the released tracers.  0 (the default, and what
+ *   ludvm_march_set_tracers and ludvm_march_setup reset it to): float64 pairs, everything above.  2: the pair arithmetic in
+ *   fp32 on hi+lo positions -- every float64 source and tracer position v is split into hi = (float)v, lo = (float)(v - hi);
+ *   dx = (xh_p - xh_s) + (xl_p - xl_s), dz likewise, and the pair in fp32 from there; the sources in tiles of 256 from each
+ *   split's first one, a tile's pairs summed in fp32 (even and odd sources apart), the tile sums, the source splits, the
+ *   Euler update and the positions in float64.  No origins, no classes, no fall-back: the error does not depend on where the
+ *   wake is or on how far it has rolled up.  Within 2e-6 of max|u| of the float64 field (DESIGN.md section 4.9 has the
+ *   figures).  A trajectory repeats bit for bit however a run is cut into calls, as the float64 ones do, but is not the
+ *   float64 trajectory.  1 is left free (the survey's numbering: fp32 on local origins, which the tracers do not have).
+ *   Valid only while tracers are set (LUDVM_E_STATE otherwise); a value other than 0 and 2 is LUDVM_E_ARG and changes nothing.
+ *   It may be called between ludvm_march_run calls: the steps that follow use it.
+ * Guarantee: as ludvm_march_set_tracers's -- every other result of ludvm_march_run keeps its bits -- and a context whose
+ *   precision is 0 enqueues exactly what it enqueued before this entry existed. */
+int ludvm_march_set_tracer_precision(ludvm_ctx* ctx, int precision);
 
 /* ---- wake survey: running field moments inside the march (an addition to ABI 7: detect it by symbol) -----------
  *

@@ -122,6 +122,7 @@ struct ludvm_ctx {
   bool tracer_ran = false;                     // a ludvm_march_run call has succeeded since the tracers were set
   std::vector<long long> tracer_record;        // steps whose rows are recorded, ascending
   std::vector<long long> tracer_rows;          // the recorded steps of the last ludvm_march_run call
+  int tracer_precision = 0;                    // 0: float64 pair sums; 2: hi+lo fp32 (ludvm_march_set_tracer_precision)
   // wake survey of the march (ludvm_march_set_survey): points x[K] | z[K], the per-step x offsets, the five raw sums
   // [5][K], the partial slabs of one sampled step -- buffers of the survey's own, like the probes' and the tracers'
   Buf survey_xz, survey_shift, survey_sums, survey_part;

@@ -23,6 +23,7 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->tracer_ran = false;
   c->tracer_record.clear();
   c->tracer_rows.clear();
+  c->tracer_precision = 0;
   c->survey_count = 0;      // ... and its survey (ludvm_march_set_survey)
   c->survey_samples = 0;
   c->survey_precision = 0;
@@ -186,6 +187,25 @@ size_t tracer_slab_bytes(size_t count) {
   return (size_t)tracer_want(p.ttiles) * 2 * (size_t)p.m_pad * 8;
 }
 
+// Launch rule of the hi+lo fp32 tracer kernel (march_f32x2_tracer_partial): tracer_plan's form and constants with its own
+// tracer tile (256 lanes x kTracerF32PerLane).  `chunk` is a multiple of the 256-source tile the kernel stages.  A function of M
+// and n_ub alone.
+TracerPlan tracer_plan_f32x2(size_t count, long long ns_ub) {
+  TracerPlan p;
+  p.ttiles = ((long long)count + kTracerF32Tile - 1) / kTracerF32Tile;
+  p.m_pad = p.ttiles * kTracerF32Tile;
+  const long long want = tracer_want(p.ttiles);
+  ns_ub = std::max<long long>(ns_ub, 1);
+  p.chunk = std::max<long long>(kHiloTile, ((ns_ub + want - 1) / want + kHiloTile - 1) / kHiloTile * kHiloTile);
+  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
+  return p;
+}
+// the fp32 kernel's slab of any step (at most 16 MiB: want x m_pad <= 1024 tiles of 1024 tracers)
+size_t tracer_slab_bytes_f32x2(size_t count) {
+  const TracerPlan p = tracer_plan_f32x2(count, 1);
+  return (size_t)tracer_want(p.ttiles) * 2 * (size_t)p.m_pad * 8;
+}
+
 // The tracers' Euler step of time step s (rec_row >= 0: also row rec_row of the call's record): enqueued where the probes
 // are, behind march_solve of step s on the stream that ran it and behind the probe kernels when both are set, so before the
 // roll-up's finisher moves anything.  The slab, the positions and the record are the tracers' own buffers, touched only by
@@ -194,17 +214,24 @@ size_t tracer_slab_bytes(size_t count) {
 int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s, long long rec_row, size_t rec_rows) {
   const MarchSetup& m = c->msetup;
   const size_t M = c->tracer_count;
-  const TracerPlan p = tracer_plan(M, n_ub + (long long)m.npan);
+  const bool f32x2 = c->tracer_precision == 2;
+  const TracerPlan p = f32x2 ? tracer_plan_f32x2(M, n_ub + (long long)m.npan) : tracer_plan(M, n_ub + (long long)m.npan);
   const double* seed = static_cast<const double*>(c->tracer_seed.p);
   const long long* release = static_cast<const long long*>(c->tracer_release.p);
   const double* shift = c->tracer_shifted ? static_cast<const double*>(c->tracer_shift.p) + s : nullptr;
   double* cur = static_cast<double*>(c->tracer_cur.p);
   double* slab = static_cast<double*>(c->tracer_part.p);
   double* out = static_cast<double*>(c->tracer_out.p);
-  hipLaunchKernelGGL(march_tracer_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M, release,
-                     release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.m_pad,
-                     (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
-                     static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  if (f32x2)
+    hipLaunchKernelGGL(march_f32x2_tracer_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M,
+                       release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.m_pad,
+                       (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  else
+    hipLaunchKernelGGL(march_tracer_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M, release,
+                       release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.m_pad,
+                       (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
   double* rec_x = rec_row >= 0 ? out + (size_t)rec_row * M : nullptr;
   double* rec_z = rec_row >= 0 ? out + (rec_rows + (size_t)rec_row) * M : nullptr;
@@ -380,6 +407,7 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
   c->tracer_ran = false;
   c->tracer_record.clear();
   c->tracer_rows.clear();
+  c->tracer_precision = 0;         // float64 until ludvm_march_set_tracer_precision says otherwise
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const TracerPlan p = tracer_plan(count, 1);
@@ -398,7 +426,7 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
   CHK(ensure(c, c->tracer_seed, 2 * count * 8));
   CHK(ensure(c, c->tracer_release, rel.size() * 8));
   CHK(ensure(c, c->tracer_cur, 2 * count * 8));
-  CHK(ensure(c, c->tracer_part, tracer_slab_bytes(count)));
+  CHK(ensure(c, c->tracer_part, std::max(tracer_slab_bytes(count), tracer_slab_bytes_f32x2(count))));   // either precision's
   if (shift_x) CHK(ensure(c, c->tracer_shift, shift_rows * 8));
   double* seed = static_cast<double*>(c->tracer_seed.p);
   HIPCHK(c, hipMemcpyAsync(seed, seed_x, count * 8, hipMemcpyHostToDevice, c->stream));
@@ -410,6 +438,14 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
   c->tracer_shifted = shift_x != nullptr;
   c->tracer_record.assign(record_steps, record_steps + nrecord);
   c->tracer_count = count;
+  return LUDVM_OK;
+}
+
+int ludvm_march_set_tracer_precision(ludvm_ctx* c, int precision) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (precision != 0 && precision != 2) return fail(c, LUDVM_E_ARG, "march: tracer precision is 0 (float64) or 2 (hi+lo fp32)");
+  c->tracer_precision = precision;
   return LUDVM_OK;
 }
 

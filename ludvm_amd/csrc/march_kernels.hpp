@@ -968,4 +968,146 @@ march_survey_finish(const double* slab, long long k_pad, int nsplit, long long c
   s[4 * count] = __builtin_fma(u, w, s[4 * count]);
 }
 
+// ---- the tracers' field in hi+lo fp32 (ludvm_march_set_tracer_precision) ---------------------------------------------------------
+// The same quantity as march_tracer_partial into the same slab, with the pair arithmetic in fp32 on hi+lo positions (pair_f32<...,
+// HILO = true>'s inner loop) and everything around it in float64.  It reads the float64 master arrays and splits them itself
+// (split_hilo), so it depends neither on the resident wake's fp32 mirrors nor on any origin table: no classes, no guard, and
+// an error that does not grow with the distance from the coordinate origin or with how far the roll-up has stretched the wake:
+//   tiles    256 consecutive sources from the split's first one (`chunk` is a multiple of 256); each lane splits one source's
+//            x and z into (hi, lo) and stages xh, xl, zh, zl, (float)G: five float planes, 5 KiB.  Slots past the end are
+//            pair_f32's padding (hi = kPadPosF, lo = 0, G = 0: exactly 0)
+//   points   each lane splits its PPL points once, before the source loop
+//   pairs    dx = (xh_p - xh_s) + (xl_p - xl_s), dz likewise, then pair2_f32: two sources per packed instruction, 12 v_pk_*_f32
+//            + 2 v_rsq_f32 per two pairs and point; the sources come by broadcast ds_read_b128
+//   sums     two levels: a tile's contributions in fp32 packed registers (even sources in the low halves, odd ones in the high
+//            halves), then low half and high half, in that order, added to the lane's float64 (u, w)
+// One lane forms every partial sum in source order and the tiles in tile order: with tracer_plan_f32x2 (march.hip) a function of
+// M and the step's bound alone, a trajectory repeats bit for bit however a run is cut into calls.
+// hilo_field_f32 is the body: PPL points of the lane (xd, zd: float64; a lane without a point passes -kPadPosF, away from the
+// sources' padding) against the sources [s_begin, s_end) -> au += sum G dz / sqrt(r^4 + vc^4), aw += sum G dx / sqrt(..) (no
+// 1 / 2 pi, no sign).  Every lane of the workgroup calls it (barriers inside).
+constexpr int kTracerF32PerLane = 4;
+constexpr int kTracerF32Tile = kBlock * kTracerF32PerLane;
+constexpr int kHiloTile = 256;
+
+template <int PPL>
+__device__ __forceinline__ void hilo_field_f32(const double (&xd)[PPL], const double (&zd)[PPL], const double* __restrict__ xs,
+                                               const double* __restrict__ zs, const double* __restrict__ gs, long long s_begin,
+                                               long long s_end, double vc4, double (&au)[PPL], double (&aw)[PPL]) {
+  static_assert(kHiloTile == kBlock, "one source slot per lane");
+  __shared__ __attribute__((aligned(16))) float lxh[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lxl[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lzh[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lzl[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lg[kHiloTile];
+  const int tid = threadIdx.x;
+  const float vc4s = (float)vc4;
+  const f32x2 vc4p = {vc4s, vc4s};
+  f32x2 xph[PPL], xpl[PPL], zph[PPL], zpl[PPL];
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    float h, l;
+    split_hilo(xd[k], h, l);
+    xph[k] = (f32x2){h, h}; xpl[k] = (f32x2){l, l};
+    split_hilo(zd[k], h, l);
+    zph[k] = (f32x2){h, h}; zpl[k] = (f32x2){l, l};
+  }
+  for (long long base = s_begin; base < s_end; base += kHiloTile) {
+    __syncthreads();                                // previous tile fully consumed
+    {
+      const long long si = base + tid;
+      float xh = kPadPosF, xl = 0.0f, zh = kPadPosF, zl = 0.0f, g = 0.0f;
+      if (si < s_end) {
+        split_hilo(xs[si], xh, xl);
+        split_hilo(zs[si], zh, zl);
+        g = (float)gs[si];
+      }
+      lxh[tid] = xh; lxl[tid] = xl; lzh[tid] = zh; lzl[tid] = zl; lg[tid] = g;
+    }
+    __syncthreads();
+    f32x2 tu[PPL], tw[PPL];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) { tu[k] = (f32x2){0.0f, 0.0f}; tw[k] = (f32x2){0.0f, 0.0f}; }
+#pragma unroll 2
+    for (int j = 0; j < kHiloTile; j += 4) {
+      const f32x4 X = *reinterpret_cast<const f32x4*>(&lxh[j]);
+      const f32x4 XL = *reinterpret_cast<const f32x4*>(&lxl[j]);
+      const f32x4 Z = *reinterpret_cast<const f32x4*>(&lzh[j]);
+      const f32x4 ZL = *reinterpret_cast<const f32x4*>(&lzl[j]);
+      const f32x4 G = *reinterpret_cast<const f32x4*>(&lg[j]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x2 xs2 = h ? (f32x2){X.z, X.w} : (f32x2){X.x, X.y};
+        const f32x2 xl2 = h ? (f32x2){XL.z, XL.w} : (f32x2){XL.x, XL.y};
+        const f32x2 zs2 = h ? (f32x2){Z.z, Z.w} : (f32x2){Z.x, Z.y};
+        const f32x2 zl2 = h ? (f32x2){ZL.z, ZL.w} : (f32x2){ZL.x, ZL.y};
+        const f32x2 gs2 = h ? (f32x2){G.z, G.w} : (f32x2){G.x, G.y};
+#pragma unroll
+        for (int k = 0; k < PPL; ++k)
+          pair2_f32((xph[k] - xs2) + (xpl[k] - xl2), (zph[k] - zs2) + (zpl[k] - zl2), gs2, vc4p, tu[k], tw[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      au[k] += (double)tu[k].x; au[k] += (double)tu[k].y;
+      aw[k] += (double)tw[k].x; aw[k] += (double)tw[k].y;
+    }
+  }
+}
+
+// march_tracer_partial's contract (the same arguments, the same slab [split][2][m_pad], march_tracer_finish behind it) with
+// hilo_field_f32 as the body.  A workgroup owns kTracerF32Tile tracers: tracer t0 + k * 256 + lane in register set k of the lane.
+// `tile_min` holds one entry per kTracerTile tracers, so a workgroup takes the earliest of its kTracerF32Tile / kTracerTile entries.
+__global__ void __launch_bounds__(kBlock)
+march_f32x2_tracer_partial(const double* __restrict__ seed_x, const double* __restrict__ seed_z, const long long* __restrict__ release,
+                           const long long* __restrict__ tile_min, const double* cur_x, const double* cur_z, const double* shift,
+                           long long step, long long count, long long m_pad, const double* __restrict__ xs,
+                           const double* __restrict__ zs, const double* __restrict__ gs, const MarchState* S, int nfoil,
+                           long long chunk, double vc4, double* slab) {
+  static_assert(kTracerF32Tile % kTracerTile == 0, "whole tile_min entries per workgroup");
+  constexpr int kSub = kTracerF32Tile / kTracerTile;
+  {
+    // every tracer of the tile is still held: leave (uniform: before any barrier)
+    const long long nsub = (count + kTracerTile - 1) / kTracerTile;
+    bool held = true;
+#pragma unroll
+    for (int q = 0; q < kSub; ++q) {
+      const long long e = (long long)blockIdx.x * kSub + q;
+      if (e < nsub && tile_min[e] <= step) held = false;
+    }
+    if (held) return;
+  }
+  __builtin_amdgcn_s_setprio(3);
+  const long long t0 = (long long)blockIdx.x * kTracerF32Tile + threadIdx.x;
+  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
+  const long long s_begin = (long long)blockIdx.y * chunk;
+  long long s_end = s_begin + chunk;
+  if (s_end > ns) s_end = ns;
+  const double sh = shift ? *shift : 0.0;
+  double xp[kTracerF32PerLane], zp[kTracerF32PerLane], au[kTracerF32PerLane], aw[kTracerF32PerLane];
+  bool free_[kTracerF32PerLane];
+#pragma unroll
+  for (int k = 0; k < kTracerF32PerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    xp[k] = -(double)kPadPosF; zp[k] = -(double)kPadPosF; au[k] = 0.0; aw[k] = 0.0;
+    free_[k] = false;
+    if (m < count) {
+      const long long rel = release[m];
+      free_[k] = rel <= step;
+      if (free_[k]) tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, xp[k], zp[k]);
+    }
+  }
+  hilo_field_f32<kTracerF32PerLane>(xp, zp, xs, zs, gs, s_begin, s_end, vc4, au, aw);
+  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
+  double* row = slab + (long long)blockIdx.y * 2 * m_pad;
+#pragma unroll
+  for (int k = 0; k < kTracerF32PerLane; ++k) {
+    const long long m = t0 + (long long)k * kBlock;
+    if (free_[k]) {
+      row[m] = au[k] * kInv2PiD;
+      row[m_pad + m] = -aw[k] * kInv2PiD;
+    }
+  }
+}
+
 }  // namespace ludvm

@@ -483,6 +483,18 @@ class Engine:
                                                      int(first), stop, int(every), _pd(sm), int(samples)))
         self._march_nsurvey = len(xs)
 
+    def march_set_tracer_precision(self, precision):
+        """How the marched steps evaluate the field at the released tracers (ludvm_march_set_tracer_precision): 'f64' (what
+        `march_set_tracers` leaves) or 'f32x2' -- fp32 pair arithmetic on hi+lo positions, float64 tile sums, splits, Euler update
+        and positions -- or the library's own code (0 / 2; anything else is the library's LUDVM_E_ARG).  Valid while tracers
+        are set."""
+        if not hasattr(self._lib, "ludvm_march_set_tracer_precision"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_tracer_precision")
+        code = _ffi.TRACER_PRECISIONS.get(precision, precision) if isinstance(precision, str) else precision
+        if isinstance(code, bool) or not isinstance(code, int):
+            raise ValueError("march_set_tracer_precision: 'f64' or 'f32x2' (or the library's code)")
+        self._check(self._lib.ludvm_march_set_tracer_precision(self._ctx, code))
+
     def march_set_survey_precision(self, precision):
         """How the marched steps evaluate the survey's field (ludvm_march_set_survey_precision): 'f64' (what `march_set_survey`
         leaves) or 'f32' -- fp32 pair arithmetic on local origins, float64 class sums, splits and moments -- or the library's

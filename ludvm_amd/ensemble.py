@@ -63,6 +63,9 @@ def _check_case(idx, kw, first):
     if "survey_precision" in kw:
         raise ValueError(who + f"survey_precision={kw['survey_precision']!r}: the survey of a sweep is evaluated in float64 (fp32 "
                          "survey sums: run the member on its own, LUDVM(..., survey=..., survey_precision='f32'))")
+    if "tracer_precision" in kw:
+        raise ValueError(who + f"tracer_precision={kw['tracer_precision']!r}: the tracers of a sweep are advected in float64 (fp32 "
+                         "tracer sums: run the member on its own, LUDVM(..., tracers=..., tracer_precision='f32x2'))")
     for key, (fine, why) in _REFUSED.items():
         if key in kw and not (kw[key] is fine or (fine is not None and kw[key] == fine)):
             raise ValueError(who + f"{key}={kw[key]!r}: {why}")
@@ -225,15 +228,18 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     ensemble_run_traced, and tracer records (16 bytes x members x (recorded steps + 1) x M) over 1 GiB; `survey` / `survey_steps` /
     survey_frame='tunnel' inside a member's dict (they belong to the sweep), more than 4096 survey points, points that are not
     finite, a survey_frame other than 'lab' / 'tunnel', survey_steps that are not three integers with first >= 1 and every >= 1
-    or that hold no step of some member (named), survey_steps without `survey`, `survey_precision` anywhere (the sweep's or a member's), an engine without
+    or that hold no step of some member (named), survey_steps without `survey`, `survey_precision` or `tracer_precision` anywhere (the sweep's or a member's), an engine without
     ensemble_run_surveyed, and
     survey sums (40 bytes x members x K) over 1 GiB: split the case list.
 
-    Out of scope: per-member probe, seed or survey point sets and windows, tracers or a survey of a sweep on several GPUs, fp32 tracer sums, fp32 survey sums in a sweep (a solo run has survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe, seed or survey point sets and windows, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     if "survey_precision" in common:
         raise ValueError(f"sweep: survey_precision={common['survey_precision']!r}: the survey of a sweep is evaluated in float64 "
                          "(fp32 survey sums: run a member on its own, LUDVM(..., survey=..., survey_precision='f32'))")
+    if "tracer_precision" in common:
+        raise ValueError(f"sweep: tracer_precision={common['tracer_precision']!r}: the tracers of a sweep are advected in float64 "
+                         "(fp32 tracer sums: run a member on its own, LUDVM(..., tracers=..., tracer_precision='f32x2'))")
     cases = list(cases)
     if not cases:
         return []

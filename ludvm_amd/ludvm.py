@@ -118,13 +118,22 @@ class LUDVM:
                  always present), `tracer_last` [2, M] (positions after the final step), `tracer_xz`, `tracer_release`,
                  `tracer_frame` as given, `tracer_released(step)` -> bool [M].  Every other result is unchanged, bit for
                  bit.  A sweep takes them as sweep(..., particles=).  Out of scope: tracers on several GPUs, fp32 tracer
-                 sums, higher-order time integration (the reference's wake is forward Euler, and the tracers follow
-                 it), tracers that interact with the foil
+                 sums in a sweep, higher-order time integration (the reference's wake is forward Euler, and the tracers
+                 follow it), tracers that interact with the foil
       tracer_release  None (all 1), or one integer release step >= 1 per tracer (a step >= nt: never released)
       tracer_frame  'lab' (default): seeds fixed in the lab frame; 'tunnel': a held tracer rides with the pivot -- its seed
                  at step i is (x + xpiv[i], z) -- and is released into the lab frame from there
       tracer_steps  time steps whose positions `tracer_path` keeps; None (default): every step when the run keeps a dense
                  history, snapshot_steps and the last step otherwise
+      tracer_precision  'f64' (default): the tracers' pair sums in float64.  'f32x2': the pair arithmetic in fp32 on hi+lo
+                 positions, inside the device-resident march only -- every float64 source and tracer position split into
+                 (float)v and the float remainder, dx = (xh_p - xh_s) + (xl_p - xl_s), the sources in tiles of 256, a tile's
+                 pairs summed in fp32, the tile sums, the source splits, the Euler update and the positions in float64.  No
+                 origins and no fall-back: the error does not depend on where the wake is or how far it has rolled up.
+                 Velocities within 2e-6 of max|u| of the 'f64' ones (DESIGN.md section 4.9 has the figures and the cost); every
+                 other result keeps its bits, and the paths repeat bit for bit however the run is cut, checkpoints included
+                 (they carry the value).  Refused: without `tracers`, with march=False, in a sweep; a run that cannot take the
+                 march raises instead of falling back to float64.  The object carries `tracer_precision` as used
       survey     None (default), or the points of a wake survey: a [2, K] array (x row, z row), or a dict(xmin, xmax, zmin, zmax,
                  dr) meaning the mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr), x-major as `flowfield` builds it
                  (1 <= K <= 1048576).  In every sampled step the field of `probes` is evaluated at the points and added to
@@ -268,6 +277,16 @@ class LUDVM:
             raise ValueError("survey_precision='f32' is evaluated inside the device-resident march: not with march=False")
 
     @staticmethod
+    def _check_tracer_precision(tracer_precision, traced, march=True):
+        """ValueError from the keywords alone (nothing else has been created yet)."""
+        if not isinstance(tracer_precision, str) or tracer_precision not in ('f64', 'f32x2'):
+            raise ValueError(f"tracer_precision must be 'f64' or 'f32x2' (got {tracer_precision!r})")
+        if tracer_precision != 'f64' and not traced:
+            raise ValueError("tracer_precision needs `tracers`")
+        if tracer_precision == 'f32x2' and not march:
+            raise ValueError("tracer_precision='f32x2' is evaluated inside the device-resident march: not with march=False")
+
+    @staticmethod
     def _check_tracers(tracers, tracer_release, tracer_frame, tracer_steps=None, nt=None):
         """-> (float64 [2, M], int64 [M], sorted steps or None), or ValueError (nothing else has been created yet)."""
         if tracer_frame not in ('lab', 'tunnel'):
@@ -317,7 +336,7 @@ class LUDVM:
                  engine=None, device=0, precision='auto', history='auto', snapshot_steps=(), run=True,
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
                  probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
-                 survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64'):
+                 survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64', tracer_precision='f64'):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -335,6 +354,7 @@ class LUDVM:
             raise ValueError("tracer_frame must be 'lab' or 'tunnel'")
         elif tracer_release is not None or tracer_steps is not None:
             raise ValueError("tracer_release / tracer_steps need `tracers`")
+        self._check_tracer_precision(tracer_precision, tracers is not None, march)
         if survey is not None:
             # refused before any engine, thread or communicator exists
             survey_xz, survey_shape, survey_win = self._check_survey(survey, survey_frame, survey_steps,
@@ -366,6 +386,9 @@ class LUDVM:
                               tracer_steps=tracer_rec)
             self.tracer_xz, self.tracer_release, self.tracer_frame = tracer_xz, tracer_rel, tracer_frame
             self._tracer_steps = tracer_rec
+            self.tracer_precision = tracer_precision
+            if self.tracer_precision != 'f64':      # (float64 tracers keep the checkpoints they had)
+                self._ctor.update(tracer_precision=self.tracer_precision)
         if survey is not None:              # (likewise; a mesh travels as its five numbers)
             self._ctor.update(survey={k: float(v) for k, v in survey.items()} if isinstance(survey, dict) else survey_xz.tolist(),
                               survey_frame=survey_frame, survey_steps=list(survey_win))
@@ -857,6 +880,9 @@ class LUDVM:
             raise RuntimeError("tracers: this engine marches but has no march_set_tracers (pass march=False for the per-step path)")
         if S.survey is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey'):
             raise RuntimeError("survey: this engine marches but has no march_set_survey (pass march=False for the per-step path)")
+        f32_tracers = S.tracers is not None and self.tracer_precision == 'f32x2'
+        if f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_precision'):
+            raise RuntimeError("tracer_precision='f32x2': this engine marches but has no march_set_tracer_precision")
         f32_survey = S.survey is not None and self.survey_precision == 'f32'
         if f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_precision'):
             raise RuntimeError("survey_precision='f32': this engine marches but has no march_set_survey_precision")
@@ -876,11 +902,17 @@ class LUDVM:
             if S.tracers is not None:
                 eng.march_set_tracers(S.tracers[0], S.tracers[1], release=self.tracer_release,
                                       shift_x=self.xpiv if self.tracer_frame == 'tunnel' else None, cur=S.tcur, record_steps=S.trec)
+                if f32_tracers:
+                    eng.march_set_tracer_precision('f32x2')
             if S.survey is not None:
                 eng.march_set_survey(S.survey[0], S.survey[1], shift_x=self.xpiv if self.survey_frame == 'tunnel' else None,
                                      steps=self.survey_steps, sums=S.ssums if S.scount else None, samples=S.scount)
                 if f32_survey:
                     eng.march_set_survey_precision('f32')
+        if f32_tracers and not S.can_march:
+            # (no float64 in its place: the per-step path has no fp32 tracer sums)
+            raise RuntimeError("tracer_precision='f32x2' is evaluated inside the device-resident march, which this run cannot take "
+                               "(an engine without march_run, method, Npoints or Ncoeffs outside its limits)")
         if f32_survey and not S.can_march:
             # (no float64 in its place: the per-step path has no fp32 survey sums)
             raise RuntimeError("survey_precision='f32' is evaluated inside the device-resident march, which this run cannot take "

@@ -1,20 +1,29 @@
 #!/usr/bin/env python3
 """What passive tracers cost (profiles/tracers_cost.txt): a marched run with `tracers=None` against the parent build, the
-added time per step with M tracers, and -- from rocprofv3 kernel statistics -- the tracer kernels' pairs/s beside pair_f64's
-and the probe kernel's on the same run.
+added time per step with M tracers, the same in both precisions of the tracers (tracer_precision 'f64' | 'f32x2', runs
+alternated in one process), and -- from rocprofv3 kernel statistics -- the tracer kernels' pairs/s beside pair_f64's and the
+probe kernel's on the same run.
 
     python tools/tracers_cost.py ab     --parent-lib LIB [--repeats R]       tracers=None: this build and the parent's library
                                                                               loaded in ONE process, runs alternated
     python tools/tracers_cost.py time   [--tracers M] [--probes P] [--repeats R]   wall time, added time per step, pair count
-    python tools/tracers_cost.py once   [--tracers M] [--probes P] [--induce M] [--lib LIB]
+    python tools/tracers_cost.py precision --tracers M [--steps N] [--release R] [--repeats R]
+                                                                              plain / 'f64' / 'f32x2' runs alternated: added time
+                                                                              per free step of each precision, and their ratio
+    python tools/tracers_cost.py once   [--tracers M] [--probes P] [--induce M] [--lib LIB] [--precision f64|f32x2|both]
                                                                               one warm-up + one run (under rocprofv3); --induce:
                                                                               also 5 Engine.induce f64 calls, M points x final wake
     python tools/tracers_cost.py stats  A_kernel_stats.csv [B_kernel_stats.csv] [--pairs N] [--induce-pairs N] [--probe-pairs N]
                                                                               kernel names and counts (equal?); the tracer, probe
                                                                               and pair_f64 kernels' time and pairs/s
+    python tools/tracers_cost.py trace  kernel_trace.csv --free N --pairs P   the N longest dispatches of each tracer kernel (the
+                                                                              free steps: a dispatch whose tiles are all held
+                                                                              returns at once): mean time, pairs/s at P pairs
 
 The run: 5000 steps of config 1's foil at dt = 1e-3, history='sparse', precision='f32' (DESIGN 4.7's 'long' case).  Tracers: a
-box of M seeds around the foil's path in the tunnel frame, a quarter released at step 1, 1250, 2500 and 3750 each."""
+box of M seeds around the foil's path in the tunnel frame, a quarter released at step 1, 1250, 2500 and 3750 each -- or, with
+--release R, all of them at step R (--steps 17000 --release 16000: every free step sees at least 16 000 sources, the run of
+tools/survey_cost.py)."""
 import argparse
 import csv
 import os
@@ -24,16 +33,19 @@ import time
 import numpy as np
 
 ap = argparse.ArgumentParser()
-ap.add_argument("mode", choices=["ab", "time", "once", "stats"])
+ap.add_argument("mode", choices=["ab", "time", "precision", "once", "stats", "trace"])
 ap.add_argument("files", nargs="*")
 ap.add_argument("--tracers", type=int, default=0)
 ap.add_argument("--probes", type=int, default=0)
 ap.add_argument("--induce", type=int, default=0)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--steps", type=int, default=5000)
+ap.add_argument("--release", type=int, default=0, help="release every tracer at this step (default: a quarter at four steps)")
+ap.add_argument("--precision", default="f64", choices=["f64", "f32x2", "both"], help="tracer_precision of `time` and `once`")
 ap.add_argument("--lib", default=None)
 ap.add_argument("--parent-lib", default=None)
 ap.add_argument("--pairs", type=float, default=0)
+ap.add_argument("--free", type=int, default=0, help="trace: the number of dispatches with free tracers")
 ap.add_argument("--induce-pairs", type=float, default=0)
 ap.add_argument("--probe-pairs", type=float, default=0)
 args = ap.parse_args()
@@ -43,6 +55,23 @@ def stats(path):
     with open(path) as f:
         return {r["Name"]: (int(r["Calls"]), int(r["TotalDurationNs"])) for r in csv.DictReader(f)}
 
+
+if args.mode == "trace":
+    took = {}
+    with open(args.files[0]) as f:
+        for r in csv.DictReader(f):
+            if "tracer_partial" in r["Kernel_Name"]:
+                took.setdefault(r["Kernel_Name"].split("(")[0], []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+    for k, ns in took.items():
+        ns.sort()
+        rest, free = ns[:len(ns) - args.free], ns[len(ns) - args.free:]
+        line = f"  {k}: {len(ns)} dispatches; the {len(free)} longest: {np.mean(free) / 1e3:.2f} us each (min {free[0] / 1e3:.2f})"
+        if args.pairs:
+            line += f", {args.pairs / (sum(free) * 1e-9):.3g} pairs/s"
+        if rest:
+            line += f"; the other {len(rest)}: {np.mean(rest) / 1e3:.2f} us each (max {rest[-1] / 1e3:.2f})"
+        print(line)
+    sys.exit(0)
 
 if args.mode == "stats":
     a = stats(args.files[0])
@@ -56,9 +85,10 @@ if args.mode == "stats":
                 if a.get(k, (0,))[0] != b.get(k, (0,))[0]:
                     print("  differs:", k[:90], a.get(k, (0,))[0], b.get(k, (0,))[0])
     for k, (calls, ns) in a.items():
-        pairs = {"march_tracer_partial": args.pairs, "march_probe_partial": args.probe_pairs, "pair_f64<": args.induce_pairs}
+        pairs = {"march_tracer_partial": args.pairs, "march_f32x2_tracer_partial": args.pairs, "march_probe_partial": args.probe_pairs,
+                 "pair_f64<": args.induce_pairs}
         hit = [p for name, p in pairs.items() if name in k]
-        if "march_tracer" in k or "march_probe" in k or (hit and "pair_f64_few" not in k):
+        if "march_tracer" in k or "march_f32x2_tracer" in k or "march_probe" in k or (hit and "pair_f64_few" not in k):
             rate = f", {hit[0] / (ns * 1e-9):.3g} pairs/s" if hit and hit[0] else ""
             print(f"  {k.split('(')[0]}: {calls} dispatches, {ns / 1e6:.2f} ms total, {ns / calls / 1e3:.2f} us each{rate}")
     sys.exit(0)
@@ -70,12 +100,15 @@ kw = dict(t0=0, tf=args.steps * 1e-3, dt=1e-3, chord=1, rho=1.225, Uinf=1, Npoin
           history="sparse", precision="f32")
 
 
-def extras(M, P):
+def extras(M, P, precision="f64"):
     e = {}
     if M:
         rng = np.random.default_rng(1)
+        quarters = np.array([1, args.steps // 4, args.steps // 2, 3 * args.steps // 4], dtype=np.int64)[np.arange(M) % 4]
         e.update(tracers=np.stack([rng.uniform(-1.0, 3.0, M), rng.uniform(-2.0, 2.0, M)]), tracer_frame="tunnel",
-                 tracer_release=np.array([1, args.steps // 4, args.steps // 2, 3 * args.steps // 4], dtype=np.int64)[np.arange(M) % 4])
+                 tracer_release=np.full(M, args.release, dtype=np.int64) if args.release else quarters)
+        if precision != "f64":          # (the keyword only where it is needed: --lib may name a build without it)
+            e.update(tracer_precision=precision)
     if P:
         e.update(probes=np.stack([np.full(P, 2.0), np.linspace(-2.0, 2.0, P)]), probe_frame="tunnel")
     return e
@@ -113,8 +146,45 @@ if args.mode == "ab":
           f"[{min(tb):.4f}, {max(tb):.4f}]: {min(tb) <= ma <= max(tb)}")
     sys.exit(0)
 
+def tracer_pairs(sim):
+    free = (sim.tracer_release[None, :] <= np.arange(1, sim.nt)[:, None]).sum(axis=1)
+    return float((free * sources_per_step(sim)[1:]).sum()), int((free > 0).sum())
+
+
 eng = Engine(0, lib_path=args.lib) if args.lib else Engine(0)
-extra = extras(args.tracers, args.probes)
+if args.mode == "precision":
+    run(eng)
+    for prec in ("f64", "f32x2"):
+        run(eng, **extras(args.tracers, 0, prec))
+    ts = {"plain": [], "f64": [], "f32x2": []}
+    for _ in range(args.repeats):
+        ts["plain"].append(run(eng)[0])
+        for prec in ("f64", "f32x2"):
+            t, sim = run(eng, **extras(args.tracers, 0, prec))
+            ts[prec].append(t)
+    pairs, free_steps = tracer_pairs(sim)
+    ns = sources_per_step(sim)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+    print(f"{sim.nt - 1} steps, M={args.tracers}, {free_steps} steps with free tracers, sources {ns[sim.nt - free_steps]} .. {ns[-1]}, "
+          f"{pairs:.6g} tracer pairs")
+    print(f"plain:          {spread(ts['plain'])}")
+    for prec in ("f64", "f32x2"):
+        add = med[prec] - med["plain"]
+        print(f"tracers {prec}:  {spread(ts[prec])}; added {add:.4f} s = {add / free_steps * 1e6:.2f} us per free step, "
+              f"{pairs / max(add, 1e-9):.3g} pairs/s of the added time")
+    print(f"added time per free step, f32x2 / f64: {(med['f32x2'] - med['plain']) / max(med['f64'] - med['plain'], 1e-9):.3f}")
+    sys.exit(0)
+
+if args.mode == "once" and args.precision == "both":
+    run(eng)
+    for prec in ("f64", "f32x2"):
+        t, sim = run(eng, **extras(args.tracers, args.probes, prec))
+        pairs, free_steps = tracer_pairs(sim)
+        print(f"M={args.tracers} {prec}: {t:.4f} s, {sim.nt - 1} steps, {free_steps} with free tracers, final wake {eng.wake_size()}; "
+              f"{pairs:.6g} tracer pairs in this run")
+    sys.exit(0)
+
+extra = extras(args.tracers, args.probes, args.precision)
 if args.mode == "once":
     run(eng, **extra)
     t, sim = run(eng, **extra)
