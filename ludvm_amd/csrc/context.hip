@@ -103,7 +103,7 @@ int ludvm_create(int device_ordinal, ludvm_ctx** out) {
     if (mx[0] == '1') c->tune_sym_rsplit = -1;
     if (mx[0] == '0') c->tune_sym_rsplit = -2;
   }
-  if (small_env) { c->small_tile_max = std::atoll(small_env); c->small_tile_max_f64 = std::min<long long>(c->small_tile_max, 12000); }
+  if (small_env) { c->small_tile_max = std::atoll(small_env); c->small_tile_max_f64 = std::min<long long>(c->small_tile_max, kSmallTileMaxF64Default); }
   const char* small64_env = LUDVM_EXP_ENV("LUDVM_SMALL_TILE_MAX_F64");
   if (small64_env) c->small_tile_max_f64 = std::atoll(small64_env);
   *out = c;

@@ -1,6 +1,6 @@
 // Shared by the translation units of libludvm_hip.so: the context, error plumbing, the staging arena, and the internal
 // host functions one unit offers the others.  Kernels are NOT here: templates and device helpers live in pair_kernels.hpp /
-// pair_sym_kernels.hpp (includable anywhere; the symmetric launch rule, host and device, in sym_rule.hpp); every non-template kernel lives in a header that exactly one unit includes
+// pair_sym_kernels.hpp (includable anywhere; the symmetric launch rule, host and device, in sym_rule.hpp, the direct launch plan in plan_rule.hpp); every non-template kernel lives in a header that exactly one unit includes
 // (sym_prepare_kernels.hpp -> launch.hip, induce_kernels.hpp -> induce.hip, wake_kernels.hpp -> wake.hip, march_kernels.hpp and
 // ensemble_kernels.hpp -> march.hip, field_kernels.hpp -> flowfield.hip, order_kernels.hpp -> order.hip).
 //
@@ -72,11 +72,11 @@ struct ludvm_ctx {
   long long sym_tail_items = kSymTailItems;  // mixed granularity: work kept for the fine-grained end (LUDVM_SYM_TAIL_ITEMS)
   int grid_kernel = 2;                       // flow-field grids (LUDVM_GRID_KERNEL): 1 = 4 points of a row per lane; 2 = patch,
                                              // 4 x 4 from 2^20 grid points and 2 x 4 below; 3 / 4 = always the 2 x 4 / 4 x 4 patch
-  long long small_tile_max = 14000;          // direct fp32 launches with at most this many sources use 256-source tiles
+  long long small_tile_max = kSmallTileMaxDefault;         // direct fp32 launches with at most this many sources use 256-source tiles
   bool sym_quad = true;                      // large symmetric launches: four I tiles per workgroup share each partner tile (LUDVM_SYM_QUAD=0: off)
   long long sym_quad_min_tiles = kSymQuadMinTiles;   //   ... from this many 512-vortex tiles on (LUDVM_SYM_QUAD_MIN_TILES)
   bool few_packed = true;                    // fp64 launches with <= 128 targets: several source splits per workgroup (LUDVM_FEW_PACKED=0: off)
-  long long small_tile_max_f64 = 12000;      // fp64 launches with at most this many sources use 128-source tiles
+  long long small_tile_max_f64 = kSmallTileMaxF64Default;     // fp64 launches with at most this many sources use 128-source tiles
                                              // (roll-up step 52 -> 26 us at 2400 vortices, 87 -> 72 at 8192 [MI355X])
 
   Buf part;   // partial slabs of the split reduction
@@ -209,19 +209,7 @@ struct Plan {
   dim3 grid;
 };
 
-constexpr int kTileF32 = 1024;
-// Small source sets (a young wake, a chord-sized launch): with 1024-source tiles a launch of a few hundred sources is
-// one tile walked by one wave per SIMD, which issues at ~40 % of the SIMD's rate; 256-source tiles give 4x more splits
-// (more workgroups, shorter walks): one self-advection step 21 -> 9-11 us up to 4096 vortices, 46 -> 37 us at
-// 12 288, no gain at 16 384 [MI355X].  LUDVM_SMALL_TILE_MAX (sources) overrides the switch-over, 0 disables.
-constexpr int kTileF32Small = 256;
-constexpr int kTileF64 = 512;
-constexpr int kTileF64Few = 128;         // fp64 launches with few targets (chord points): short tiles, more workgroups
-                                         // (64: more slabs than the shorter walks save, profiles/r06_march_chain_ab.txt)
-constexpr long long kFewTargets = 256;
-constexpr long long kTargetBlocks = 16384;  // total workgroups aimed for (2048 resident at 8/CU)
-constexpr int kMaxSplit = 2048;
-
+// (the plan itself -- constants, arithmetic, which instantiation -- is plan_rule.hpp; make_plan hands it the context's settings)
 Plan make_plan(const ludvm_ctx* c, long long nt_launch, long long ns, int precision, bool small_ok = true, long long plan_nt = 0,
                bool grid_patch = false);
 int timed_begin(ludvm_ctx* c, TimedLaunch& t, bool& active);

@@ -8,41 +8,28 @@
 
 namespace ludvm_host {
 
-// small_ok = false: the launch has no 256-source-tile kernel (generic flow-field grids), keep the chunk a multiple of 1024
-// plan_nt: the target count that DECIDES the plan -- tile size, targets per lane and the split of the sources into
-// partial sums, i.e. everything the rounding of a result depends on -- when the launch itself covers only a part of a
-// larger target set (a block of rows of a flow-field grid: the block then carries the whole grid's bits); 0 = nt.
+// The plan itself is plan_rule.hpp; these hand it the context's settings.
+PlanKnobs plan_knobs(const ludvm_ctx* c) {
+  PlanKnobs k;
+  k.small_tile_max = c->small_tile_max;
+  k.small_tile_max_f64 = c->small_tile_max_f64;
+  k.tune_tpl = c->tune_tpl;
+  k.tune_split = c->tune_split;
+  k.grid_kernel = c->grid_kernel;
+  k.few_packed = c->few_packed;
+  return k;
+}
+static_assert(kPlanF32 == LUDVM_PREC_F32 && kPlanF32X2 == LUDVM_PREC_F32X2 && kPlanF64 == LUDVM_PREC_F64, "plan_rule.hpp takes the ABI's precision codes");
+
 Plan make_plan(const ludvm_ctx* c, long long nt_launch, long long ns, int precision, bool small_ok, long long plan_nt, bool grid_patch) {
+  const DirectPlan d = direct_plan(plan_knobs(c), nt_launch, ns, precision, small_ok, plan_nt, grid_patch);
   Plan p{};
-  const long long nt = plan_nt > 0 ? plan_nt : nt_launch;
-  const bool f64 = precision == LUDVM_PREC_F64;
-  p.tile = f64 ? ((nt <= kFewTargets || ns <= c->small_tile_max_f64) ? kTileF64Few : kTileF64) : kTileF32;
-  if (!f64 && small_ok && ns <= c->small_tile_max) p.tile = kTileF32Small;
-  if (f64) {
-    p.tpl = 1;
-  } else if (c->tune_tpl == 1 || c->tune_tpl == 2 || c->tune_tpl == 4) {
-    p.tpl = c->tune_tpl;
-  } else {
-    p.tpl = nt >= 131072 ? 2 : 1;
-  }
-  // the small tile exists for TPL = 1 (and for the 4-points-per-lane grid kernel, whose TPL the launch fixes itself)
-  if (p.tile == kTileF32Small && (p.tpl != 1 || nt > 65536)) p.tile = kTileF32;
-  // target tiles = workgroups per source split.  The flow-field patch kernels hold 8 or 16 grid points per lane, not tpl:
-  // counted with tpl, a 4096 x 4096 grid looked like 32 768 workgroups and got ONE source split -- 4096 workgroups that
-  // each walk all the sources for a quarter of a second, and a launch that ends over half such a lifetime (config 5:
-  // 8.05e12 pairs/s with one split, 8.13e12 with four, 8.15e12 with eight [MI355X])
-  const long long per_wg = grid_patch ? (long long)kBlock * 4 * (nt >= (1LL << 20) ? 4 : 2) : (long long)kBlock * p.tpl;
-  const long long ttiles = std::max<long long>(1, (nt + per_wg - 1) / per_wg);
-  const long long max_split = std::max<long long>(1, (ns + p.tile - 1) / p.tile);
-  long long nsplit = c->tune_split > 0 ? c->tune_split : (kTargetBlocks + ttiles - 1) / ttiles;
-  nsplit = std::max<long long>(1, std::min<long long>(std::min<long long>(nsplit, max_split), kMaxSplit));
-  long long chunk = (std::max<long long>(ns, 1) + nsplit - 1) / nsplit;
-  chunk = (chunk + p.tile - 1) / p.tile * p.tile;
-  p.chunk = chunk;
-  p.nsplit = (int)std::max<long long>(1, (ns + chunk - 1) / chunk);
-  p.nt_pad = (nt_launch + 63) / 64 * 64;
-  const long long tiles_launch = std::max<long long>(1, (nt_launch + (long long)kBlock * p.tpl - 1) / ((long long)kBlock * p.tpl));
-  p.grid = dim3((unsigned)tiles_launch, (unsigned)p.nsplit, 1);
+  p.tpl = d.tpl;
+  p.tile = d.tile;
+  p.nsplit = d.nsplit;
+  p.chunk = d.chunk;
+  p.nt_pad = d.nt_pad;
+  p.grid = dim3((unsigned)d.grid_x, (unsigned)d.grid_y, 1);
   return p;
 }
 
@@ -80,25 +67,6 @@ int drain_timing(ludvm_ctx* c) {
   return LUDVM_OK;
 }
 
-// workgroups of a flow-field grid launch: 256 lanes of 4 row points (patch_rows = 0), or of patch_rows x 4 patches
-long long grid_kernel_blocks(const PairArgs& a, int patch_rows) {
-  if (patch_rows > 0) {
-    const long long nrows = a.nt / a.grid_nz, patches = ((nrows + patch_rows - 1) / patch_rows) * (a.grid_nz / 4);
-    return (patches + kBlock - 1) / kBlock;
-  }
-  return (a.nt + (long long)kBlock * 4 - 1) / ((long long)kBlock * 4);
-}
-
-// rows of the patch of grid points a lane owns (4 columns), 0 = the row kernel.  Every variant performs the same
-// operations on the same operands for a given grid point, so the choice never changes a result bit.
-constexpr long long kPatch4MinTargets = 1LL << 20;
-int grid_patch_rows(const ludvm_ctx* c, const PairArgs& a, const Plan& p) {
-  if (c->grid_kernel == 1) return 0;
-  if (c->grid_kernel == 3 || p.tile == kTileF32Small) return 2;       // (the 4 x 4 patch exists for 1024-source tiles)
-  if (c->grid_kernel == 4) return 4;
-  return a.nt >= kPatch4MinTargets ? 4 : 2;
-}
-
 // Launch the main pair kernel described by `a` (sources, targets and vc4 filled in by the caller)
 // under plan `p`; a.part / a.u / a.w / a.nt_pad / a.chunk are completed here.  With more than one
 // split the results are left in c->part for a finisher; with one split they go to (u, w).
@@ -121,77 +89,44 @@ int launch_pair(ludvm_ctx* c, PairArgs a, const Plan& p, int precision, void* u,
     a.u = c->part.p;
     a.w = static_cast<char*>(c->part.p) + (size_t)p.nt_pad * elt;
   }
+  // which instantiation, and how many workgroups of it: plan_rule.hpp (few array targets with their results in the slab:
+  // several source splits per workgroup -- sized from the host's target count; never when THAT lives on the device.  A
+  // source count on the device -- the march's chord sums, the launch pair_f64_few exists for -- does not matter)
+  DirectPlan d{};
+  d.tpl = p.tpl; d.tile = p.tile; d.nsplit = p.nsplit; d.chunk = p.chunk; d.nt_pad = p.nt_pad;
+  d.grid_x = grid.x; d.grid_y = grid.y;
+  const DirectVariant v = direct_variant(plan_knobs(c), d, precision, a.scx != nullptr, a.nt, a.grid_nz, a.part != nullptr,
+                                         a.nt_dev != 0);
+  void (*kernel)(PairArgs) = nullptr;
+#define LUDVM_PAIR_F32(TPL, TILE, HILO, GRID, LOCAL) \
+  case direct_key(TPL, TILE, HILO, GRID, LOCAL): kernel = pair_f32<TPL, TILE, HILO, GRID, LOCAL>; break;
+  if (v.kernel == kDirectF64Few) {
+    kernel = pair_f64_few<kTileF64Few>;
+  } else if (v.kernel == kDirectF64) {
+    kernel = v.tile == kTileF64Few ? pair_f64<kTileF64Few> : pair_f64<kTileF64>;
+  } else {
+    switch (direct_key(v.tpl, v.tile, v.hilo, v.grid, v.local)) {
+      // array (and generic-grid) targets: plain, hi+lo, local origins
+      LUDVM_PAIR_F32(1, kTileF32Small, false, 0, false) LUDVM_PAIR_F32(1, kTileF32Small, true, 0, false) LUDVM_PAIR_F32(1, kTileF32Small, false, 0, true)
+      LUDVM_PAIR_F32(1, kTileF32, false, 0, false) LUDVM_PAIR_F32(2, kTileF32, false, 0, false) LUDVM_PAIR_F32(4, kTileF32, false, 0, false)
+      LUDVM_PAIR_F32(1, kTileF32, true, 0, false) LUDVM_PAIR_F32(2, kTileF32, true, 0, false) LUDVM_PAIR_F32(4, kTileF32, true, 0, false)
+      LUDVM_PAIR_F32(1, kTileF32, false, 0, true) LUDVM_PAIR_F32(2, kTileF32, false, 0, true) LUDVM_PAIR_F32(4, kTileF32, false, 0, true)
+      // flow-field grids: 4 points of a row, a 2 x 4 patch, a 4 x 4 patch per lane
+      LUDVM_PAIR_F32(4, kTileF32Small, false, 1, false) LUDVM_PAIR_F32(4, kTileF32, false, 1, false)
+      LUDVM_PAIR_F32(4, kTileF32Small, false, 1, true) LUDVM_PAIR_F32(4, kTileF32, false, 1, true)
+      LUDVM_PAIR_F32(8, kTileF32Small, false, 2, false) LUDVM_PAIR_F32(8, kTileF32, false, 2, false)
+      LUDVM_PAIR_F32(8, kTileF32Small, false, 2, true) LUDVM_PAIR_F32(8, kTileF32, false, 2, true)
+      LUDVM_PAIR_F32(16, kTileF32, false, 2, false) LUDVM_PAIR_F32(16, kTileF32, false, 2, true)
+      default: break;
+    }
+  }
+#undef LUDVM_PAIR_F32
+  if (!kernel) return fail(c, LUDVM_E_ARG, "no direct pair kernel for this launch plan");
+  grid = dim3((unsigned)v.blocks_x, (unsigned)v.blocks_y, 1);
   TimedLaunch t{};
   bool active = false;
   CHK(timed_begin(c, t, active));
-  if (precision == LUDVM_PREC_F64) {
-    // few array targets, results in the slab: several source splits per workgroup (launch sized from the host's bound on
-    // the target count when that lives on the device: never, for these launches)
-    const long long nt_few = a.nt_dev ? 0 : a.nt;
-    if (p.tile == kTileF64Few && c->few_packed && a.part != nullptr && a.grid_nz == 0 && nt_few >= 1 && 2 * nt_few <= kBlock &&
-        grid.x == 1 && p.nsplit > 1) {
-      const int groups = (int)std::min<long long>(kBlock / nt_few, kFewGroupsMax);
-      grid = dim3(1, (unsigned)((p.nsplit + groups - 1) / groups), 1);
-      hipLaunchKernelGGL((pair_f64_few<kTileF64Few>), grid, dim3(kBlock), 0, c->stream, a);
-    } else if (p.tile == kTileF64Few)
-      hipLaunchKernelGGL((pair_f64<kTileF64Few>), grid, dim3(kBlock), 0, c->stream, a);
-    else
-      hipLaunchKernelGGL((pair_f64<kTileF64>), grid, dim3(kBlock), 0, c->stream, a);
-  } else if (a.scx != nullptr) {
-    // local-origin fp32 (LUDVM_PREC_F32 wherever the library lays the positions out itself)
-    if (a.grid_nz > 0 && a.grid_nz % 4 == 0 && c->tune_tpl == 0) {
-      // flow-field grid: a 2 x 4 patch (or 4 points of a row) per lane; the plan's grid is recomputed for it
-      const int prows = grid_patch_rows(c, a, p);
-      grid = dim3((unsigned)grid_kernel_blocks(a, prows), grid.y, 1);
-      if (prows == 4) {
-        hipLaunchKernelGGL((pair_f32<16, kTileF32, false, 2, true>), grid, dim3(kBlock), 0, c->stream, a);
-      } else if (prows == 2) {
-        if (p.tile == kTileF32Small) hipLaunchKernelGGL((pair_f32<8, kTileF32Small, false, 2, true>), grid, dim3(kBlock), 0, c->stream, a);
-        else hipLaunchKernelGGL((pair_f32<8, kTileF32, false, 2, true>), grid, dim3(kBlock), 0, c->stream, a);
-      } else {
-        if (p.tile == kTileF32Small) hipLaunchKernelGGL((pair_f32<4, kTileF32Small, false, 1, true>), grid, dim3(kBlock), 0, c->stream, a);
-        else hipLaunchKernelGGL((pair_f32<4, kTileF32, false, 1, true>), grid, dim3(kBlock), 0, c->stream, a);
-      }
-    } else if (p.tile == kTileF32Small) {
-      hipLaunchKernelGGL((pair_f32<1, kTileF32Small, false, 0, true>), grid, dim3(kBlock), 0, c->stream, a);
-    } else {
-      switch (p.tpl) {
-        case 1: hipLaunchKernelGGL((pair_f32<1, kTileF32, false, 0, true>), grid, dim3(kBlock), 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL((pair_f32<2, kTileF32, false, 0, true>), grid, dim3(kBlock), 0, c->stream, a); break;
-        default: hipLaunchKernelGGL((pair_f32<4, kTileF32, false, 0, true>), grid, dim3(kBlock), 0, c->stream, a); break;
-      }
-    }
-  } else if (p.tile == kTileF32Small && !(a.grid_nz > 0)) {
-    if (precision == LUDVM_PREC_F32X2)
-      hipLaunchKernelGGL((pair_f32<1, kTileF32Small, true>), grid, dim3(kBlock), 0, c->stream, a);
-    else
-      hipLaunchKernelGGL((pair_f32<1, kTileF32Small, false>), grid, dim3(kBlock), 0, c->stream, a);
-  } else if (precision == LUDVM_PREC_F32X2) {
-    switch (p.tpl) {
-      case 1: hipLaunchKernelGGL((pair_f32<1, kTileF32, true>), grid, dim3(kBlock), 0, c->stream, a); break;
-      case 2: hipLaunchKernelGGL((pair_f32<2, kTileF32, true>), grid, dim3(kBlock), 0, c->stream, a); break;
-      default: hipLaunchKernelGGL((pair_f32<4, kTileF32, true>), grid, dim3(kBlock), 0, c->stream, a); break;
-    }
-  } else if (a.grid_nz > 0 && a.grid_nz % 4 == 0 && c->tune_tpl == 0) {
-    // flow-field grid: a 2 x 4 patch (or 4 points of a row) per lane; the plan's grid is recomputed for it
-    const int prows = grid_patch_rows(c, a, p);
-    grid = dim3((unsigned)grid_kernel_blocks(a, prows), grid.y, 1);
-    if (prows == 4) {
-      hipLaunchKernelGGL((pair_f32<16, kTileF32, false, 2>), grid, dim3(kBlock), 0, c->stream, a);
-    } else if (prows == 2) {
-      if (p.tile == kTileF32Small) hipLaunchKernelGGL((pair_f32<8, kTileF32Small, false, 2>), grid, dim3(kBlock), 0, c->stream, a);
-      else hipLaunchKernelGGL((pair_f32<8, kTileF32, false, 2>), grid, dim3(kBlock), 0, c->stream, a);
-    } else {
-      if (p.tile == kTileF32Small) hipLaunchKernelGGL((pair_f32<4, kTileF32Small, false, 1>), grid, dim3(kBlock), 0, c->stream, a);
-      else hipLaunchKernelGGL((pair_f32<4, kTileF32, false, 1>), grid, dim3(kBlock), 0, c->stream, a);
-    }
-  } else {
-    switch (p.tpl) {
-      case 1: hipLaunchKernelGGL((pair_f32<1, kTileF32, false>), grid, dim3(kBlock), 0, c->stream, a); break;
-      case 2: hipLaunchKernelGGL((pair_f32<2, kTileF32, false>), grid, dim3(kBlock), 0, c->stream, a); break;
-      default: hipLaunchKernelGGL((pair_f32<4, kTileF32, false>), grid, dim3(kBlock), 0, c->stream, a); break;
-    }
-  }
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   CHK(timed_end(c, t, active));
   return LUDVM_OK;
@@ -207,7 +142,7 @@ int induce_device(ludvm_ctx* c, const PairArgs& a, long long nt, long long ns, i
     HIPCHK(c, hipMemsetAsync(w, 0, (size_t)nt * elt, c->stream));
     return LUDVM_OK;
   }
-  const bool grid_generic = a.grid_nz > 0 && !(a.grid_nz % 4 == 0 && c->tune_tpl == 0);
+  const bool grid_generic = grid_is_generic(plan_knobs(c), a.grid_nz);
   // (whatever form of the grid kernel runs -- LUDVM_GRID_KERNEL can force one --: the plan, and with it the bits, stays the same)
   const bool grid_patch = a.grid_nz > 0 && !grid_generic && precision == LUDVM_PREC_F32;
   Plan p = make_plan(c, nt, ns, precision, !grid_generic, plan_nt, grid_patch);

@@ -21,6 +21,7 @@
 // matrix core with.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "plan_rule.hpp"
 
 namespace ludvm {
 
@@ -28,6 +29,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlock = 256;  // threads per workgroup = 4 wavefronts, one per SIMD
+static_assert(kBlock == kPlanBlock, "plan_rule.hpp plans for this workgroup");
 // Local origins: fp32 positions are stored as offsets from the origin of their origin CLASS: the vortices
 // of one 256-vortex block (block b = indices [256 b, 256 b + 256)) that share an index parity -- class (b, p) holds
 // indices 256 b + p, 256 b + p + 2, ...; its origin is the fp32-rounded position of its middle member, stored at
@@ -43,8 +45,7 @@ constexpr int kBlock = 256;  // threads per workgroup = 4 wavefronts, one per SI
 // Measured [MI355X] on a wake at |x| ~ 50 with vortices 1e-3 apart (v_core = 1.3e-3): 1.4e-3 of max|u| with plain
 // fp32 coordinates, 1.7e-5 with 512-vortex blocks whose origin is their first vortex, < 1e-5 with 256-vortex
 // blocks whose origin is their middle vortex, 1e-6 with hi+lo positions.
-constexpr int kOriginShift = 8;
-constexpr int kOriginBlock = 1 << kOriginShift;   // = the 256-vortex tile of pair_sym_f32<4>
+// (kOriginShift, kOriginBlock, origin_slot, origin_index: plan_rule.hpp -- integer code a host compiler builds too)
 constexpr int kFinBlock = kOriginBlock;           // Euler finishers: one workgroup per origin block
 // number of origin records (2 per block) an array of n positions needs, with one spare block for tiles that straddle
 // the end
@@ -465,7 +466,7 @@ pair_f64(PairArgs a) {
 // one lane walking that split's sources in order, exactly as pair_f64 does: the slab -- and every bit of the result --
 // is the same.  In the overlapped march this launch runs beside the symmetric kernel and its waves take issue slots
 // from it: 2096 wave-walks per step at 67 000 vortices become 700.
-constexpr int kFewGroupsMax = 4;
+// (kFewGroupsMax: plan_rule.hpp)
 template <int TILE>
 __global__ void __launch_bounds__(kBlock)
 pair_f64_few(PairArgs a) {
@@ -584,20 +585,6 @@ struct Mirrors {
   float* xh; float* xl; float* zh; float* zl;
   float* xr; float* zr; float* cx; float* cz;
 };
-
-// origin record of vortex i
-__host__ __device__ __forceinline__ long long origin_slot(long long i) { return 2 * (i >> kOriginShift) + (i & 1); }
-
-// Which vortex lends origin class (block b, index parity p) its origin when n vortices are stored (n > 256 b): the
-// middle one of the class, or its newest while the class is less than half full; a class without a member yet (the
-// odd one of a block that holds a single vortex) borrows the block's first vortex, so that its record is a number.
-__host__ __device__ __forceinline__ long long origin_index(long long b, int p, long long n) {
-  const long long first = b << kOriginShift;
-  const long long mid = first + kOriginBlock / 2 + p;
-  if (mid < n) return mid;
-  const long long last = (n - 1) - (((n - 1) ^ p) & 1);       // the newest stored index of parity p
-  return last >= first ? last : first;
-}
 
 // Euler finishers (one workgroup per origin block): the threads that have just moved the two origin vortices of the
 // block publish the new origins -- org = [x even, x odd, z even, z odd] in LDS for the block's threads, and the records.

@@ -17,6 +17,7 @@ from oracle import ludvm_oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ludvm_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import plan_rule  # noqa: E402
 import sym_rule  # noqa: E402
 REGEN = "regenerate G8 with the case pair at the new value (oracle/g8_cases.py, python oracle/gen_golden.py g8)"
 
@@ -88,9 +89,10 @@ def test_g8_c_oracle_matches_the_reference(g8):
 
 
 def _library_constants():
-    """The symmetric rule's thresholds from the rule itself (tools/sym_rule.py), the direct kernel's plan constants from the source."""
+    """The symmetric rule's thresholds from the rule itself (tools/sym_rule.py), the direct kernels' plan constants from the plan
+    itself (tools/plan_rule.py), the routing constants of the entry points from the source."""
     rule = sym_rule.constants()
-    launch = open(os.path.join(CSRC, "launch.hip")).read()
+    plan = plan_rule.constants()
     ctx = open(os.path.join(CSRC, "ctx.hpp")).read()
 
     def one(pattern, text, conv=int):
@@ -100,11 +102,11 @@ def _library_constants():
     return {
         "kSymMinN": rule["kSymMinN"],
         "kSymT8MinN": rule["kSymT8MinN"],
-        "kPatch4MinTargets": 1 << one(r"constexpr long long kPatch4MinTargets = 1LL << (\d+);", launch),
-        "tpl2_min_targets": one(r"p\.tpl = nt >= (\d+) \? 2 : 1;", launch),
+        "kPatch4MinTargets": plan["kPatch4MinTargets"],
+        "tpl2_min_targets": plan["kTpl2MinTargets"],
         "kOrderMin": one(r"constexpr size_t kOrderMin = (\d+);", ctx),
         "kSmallSidePairsF64": one(r"constexpr double kSmallSidePairsF64 = ([0-9.]+);", ctx, float),
-        "small_tile_max": one(r"long long small_tile_max = (\d+);", ctx),
+        "small_tile_max": plan["kSmallTileMaxDefault"],
         "sym_quad_min_tiles": rule["kSymQuadMinTiles"],
         "kMaxExtentOverCore": one(r"constexpr double kMaxExtentOverCore = ([0-9.]+);", ctx, float),
         "kMaxExtentOverCoreCloud": one(r"constexpr double kMaxExtentOverCoreCloud = ([0-9.]+);", ctx, float),
@@ -115,13 +117,13 @@ def test_g8_pairs_straddle_the_librarys_thresholds():
     """Each pair of G8 cases is (t - 1, t), t = the first size on the far side of the library's current threshold."""
     k = _library_constants()
     first = {
-        "small_tile_max": k["small_tile_max"] + 1,           # launch.hip make_plan: ns <= small_tile_max -> 256-source tiles
+        "small_tile_max": k["small_tile_max"] + 1,           # plan_rule.hpp direct_plan: ns <= small_tile_max -> 256-source tiles
         "kSymMinN": k["kSymMinN"],                           # use_symmetric: n >= kSymMinN
         "kSymT8MinN": k["kSymT8MinN"],                       # sym_tile_t: n >= kSymT8MinN -> T = 8
         "sym_quad_min_tiles": sym_rule.rule(range(1, 4000000), first_quad=True)[0].n,    # the first size the rule itself marks quad
         "kOrderMin": k["kOrderMin"],                         # ludvm_induce_f64: min(ns, nt) < kOrderMin -> float64 / hi+lo
         "kSmallSidePairsF64": int(k["kSmallSidePairsF64"] // 512) + 1,     # ns * 512 <= 2^28 -> float64 (512 targets)
-        "tpl2_min_targets": k["tpl2_min_targets"],           # make_plan: nt >= 131072 -> 2 targets per lane
+        "tpl2_min_targets": k["tpl2_min_targets"],           # direct_plan: nt >= 131072 -> 2 targets per lane
     }
     for lo, hi, const in G8.PAIRS:
         a, b = G8.BY_NAME[lo], G8.BY_NAME[hi]
@@ -137,11 +139,11 @@ def test_g8_pairs_straddle_the_librarys_thresholds():
 def test_g8_grid_and_extent_cases_sit_on_their_sides():
     k = _library_constants()
     ff = {n: G8.BY_NAME[n] for n in ("ff_default", "ff_small", "ff_fine", "ff_ragged")}
-    # 2 x 4 patch below kPatch4MinTargets grid points, 4 x 4 from there (launch.hip grid_patch_rows)
+    # 2 x 4 patch below kPatch4MinTargets grid points, 4 x 4 from there (plan_rule.hpp grid_patch_rows)
     assert ff["ff_default"]["nt"] < k["kPatch4MinTargets"] <= ff["ff_fine"]["nt"], REGEN
     assert ff["ff_default"]["ns"] > k["small_tile_max"] and ff["ff_fine"]["ns"] > k["small_tile_max"], REGEN
-    # 256-source tiles: at most small_tile_max sources and 65 536 grid points (make_plan)
-    assert ff["ff_small"]["ns"] <= k["small_tile_max"] and ff["ff_small"]["nt"] <= 65536, REGEN
+    # 256-source tiles: at most small_tile_max sources and 65 536 grid points (direct_plan)
+    assert ff["ff_small"]["ns"] <= k["small_tile_max"] and ff["ff_small"]["nt"] <= 65536 == plan_rule.constants()["kSmallTileMaxTargets"], REGEN
     # the patch kernels need rows of a multiple of 4 points; the generic grid path takes the others
     assert ff["ff_ragged"]["nz"] % 4 != 0 and all(ff[n]["nz"] % 4 == 0 for n in ("ff_default", "ff_small", "ff_fine"))
     # the first G8 flow field is the reference's default grid (flowfield(), LUDVM.py:1186)

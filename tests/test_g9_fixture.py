@@ -5,6 +5,7 @@ regenerate G9 (python oracle/gen_golden.py g9).  The GPU tier runs the same case
 (tests/test_gpu_g9.py)."""
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -14,6 +15,8 @@ from oracle import g9_cases as G9
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ludvm_amd", "csrc")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import plan_rule  # noqa: E402
 REGEN = "regenerate G9 with the case pair at the new value (oracle/g9_cases.py, python oracle/gen_golden.py g9)"
 HOST_NPAN = (2, 64, 256)
 
@@ -76,11 +79,12 @@ def _constants():
         m = re.findall(pattern, open(path).read())
         assert len(m) == 1, (pattern, m)
         return conv(m[0])
+    plan = plan_rule.constants()        # the direct kernels' plan constants, from the plan itself (tools/plan_rule.py)
     k = {
         "kBlock": one(r"constexpr int kBlock = (\d+);", os.path.join(CSRC, "pair_kernels.hpp")),
-        "kFewGroupsMax": one(r"constexpr int kFewGroupsMax = (\d+);", os.path.join(CSRC, "pair_kernels.hpp")),
-        "kTileF64Few": one(r"constexpr int kTileF64Few = (\d+);", os.path.join(CSRC, "ctx.hpp")),
-        "kFewTargets": one(r"constexpr long long kFewTargets = (\d+);", os.path.join(CSRC, "ctx.hpp")),
+        "kFewGroupsMax": plan["kFewGroupsMax"],
+        "kTileF64Few": plan["kTileF64Few"],
+        "kFewTargets": plan["kFewTargets"],
         "kEnsSlicesMax": one(r"constexpr int kEnsSlicesMax = (\d+);", os.path.join(CSRC, "ensemble_kernels.hpp")),
         "kEnsGroup": one(r"constexpr int kEnsGroup = (\d+);", os.path.join(CSRC, "ensemble_kernels.hpp")),
         "ENSEMBLE_MAX_WAKE": one(r"#define LUDVM_ENSEMBLE_MAX_WAKE (\d+)", os.path.join(ROOT, "include", "ludvm_hip.h")),
@@ -93,17 +97,18 @@ def _constants():
 def test_g9_pairs_straddle_the_kernels_constants():
     """Each pair of neighbouring panel counts is (t - 1, t) at an edge of the lane arithmetic as the sources state it now:
     the sweep's chord sums (ensemble_kernels.hpp: ntt = npan + 1 targets, slices = min(kBlock / ntt, kEnsSlicesMax), a second
-    pass from ntt > kBlock) and the march's (launch.hip: nt = npan + 3 targets; pair_f64_few with groups = min(kBlock / nt,
+    pass from ntt > kBlock) and the march's (plan_rule.hpp: nt = npan + 3 targets; pair_f64_few with groups = min(kBlock / nt,
     kFewGroupsMax) while 2 nt <= kBlock; the short-tile plan up to kFewTargets targets); the wake counts sit on both sides of
     the source tiles and a member's slab is filled exactly."""
     from ludvm_amd import _ffi
     k = _constants()
-    launch = open(os.path.join(CSRC, "launch.hip")).read()
+    launch = open(os.path.join(CSRC, "plan_rule.hpp")).read()
     ens = open(os.path.join(CSRC, "ensemble_kernels.hpp")).read()
     # the rules themselves, as the sources state them
     assert re.search(r"\bntt = npan \+ 1\b", ens), REGEN
     assert re.search(r"int slices = kBlock / cnt;\s*if \(slices > kEnsSlicesMax\) slices = kEnsSlicesMax;", ens), REGEN
-    assert "2 * nt_few <= kBlock" in launch and "std::min<long long>(kBlock / nt_few, kFewGroupsMax)" in launch, REGEN
+    assert k["kBlock"] == plan_rule.constants()["kPlanBlock"]
+    assert "2 * nt_few <= kPlanBlock" in launch and "plan_min(kPlanBlock / nt_few, kFewGroupsMax)" in launch, REGEN
     assert "nt <= kFewTargets" in launch, REGEN
 
     def slices(npan):
@@ -115,6 +120,22 @@ def test_g9_pairs_straddle_the_kernels_constants():
     def groups(npan):          # 0: not pair_f64_few
         nt = npan + 3
         return min(k["kBlock"] // nt, k["kFewGroupsMax"]) if 2 * nt <= k["kBlock"] else 0
+    # ... and as the plan itself answers for the march's chord launch, with that launch's own arguments (march.hip,
+    # march_chord_launch: fp64, results in the slab, the SOURCE count on the device -- planned from the host's bound --, the npan + 3
+    # targets on the host): pair_f64_few wherever the lane arithmetic above says so.  A launch whose TARGET count is completed on
+    # the device (the march's roll-up) never is.
+    with open(os.path.join(CSRC, "march.hip")) as f:
+        chord = re.search(r"int march_chord_launch\(.*?\n}\n", f.read(), re.S).group(0)
+    assert "a.ns_dev = 1; a.nt_dev = 0;" in chord and "a.nt = (long long)NT;" in chord, REGEN
+    assert "launch_pair(c, a, p, LUDVM_PREC_F64, nullptr, nullptr)" in chord, REGEN
+    with open(os.path.join(CSRC, "launch.hip")) as f:
+        assert re.search(r"direct_variant\([^;]*a\.part != nullptr,\s*a\.nt_dev != 0\);", f.read()), REGEN
+    for npan in G9.A_NPAN:
+        for ns_bound in (300, 5000, 70000):
+            got, dev = plan_rule.plan([dict(precision="f64", ns=ns_bound, nt=npan + 3, slab=True),
+                                       dict(precision="f64", ns=ns_bound, nt=npan + 3, slab=True, nt_on_device=True)])
+            assert (got.groups, got.family == "f64_few") == (groups(npan), groups(npan) > 0), (npan, ns_bound)
+            assert dev.family == "f64" and dev.groups == 0, (npan, ns_bound)
     want = {"sweep slices 4|3": lambda a, b: (slices(a), slices(b)) == (4, 3) and passes(b) == 1,
             "sweep slices 3|2": lambda a, b: (slices(a), slices(b)) == (3, 2) and passes(b) == 1,
             "sweep slices 2|1": lambda a, b: (slices(a), slices(b)) == (2, 1) and passes(b) == 1,

@@ -171,10 +171,22 @@ def test_launch_shapes_agree_and_are_reproducible(eng):
                 assert _rel(u, w, ur, wr) < 1e-5, (tpl, splits)
                 u2, w2 = eng.induce(g, xs, zs, xs, zs, 0.065, precision="f32")
                 assert np.array_equal(u, u2) and np.array_equal(w, w2)   # no atomics: bitwise reproducible
-                results[(tpl, splits)] = u
+                results[(tpl, splits)] = (u, w)
     finally:
         eng.set_tuning(0, 0)
         eng.set_symmetric(1)
+    # the launch shapes agree: a target's sum is formed by the same operations in the same order whatever the targets per
+    # lane are (bitwise at equal splits); another split count is another partition into fp32 partial sums -- each within
+    # 1e-5 of the reference, so within 2e-5 max|u| of each other
+    scale = max(np.abs(ur).max(), np.abs(wr).max())
+    for splits in (1, 3, 16):
+        for tpl in (2, 4):
+            assert np.array_equal(results[(1, splits)][0], results[(tpl, splits)][0]), (tpl, splits)
+            assert np.array_equal(results[(1, splits)][1], results[(tpl, splits)][1]), (tpl, splits)
+    for tpl in (1, 2, 4):
+        for sa, sb in ((1, 3), (1, 16), (3, 16)):
+            for k in (0, 1):
+                assert np.abs(results[(tpl, sa)][k] - results[(tpl, sb)][k]).max() <= 2e-5 * scale, (tpl, sa, sb)
 
 
 def test_linearity_and_antisymmetry(eng):
