@@ -503,6 +503,39 @@ int ludvm_march_read_survey(ludvm_ctx* ctx, double* sums, long long* samples);
  *   precision is 0 enqueues exactly what it enqueued before this entry existed. */
 int ludvm_march_set_survey_precision(ludvm_ctx* ctx, int precision);
 
+/* ---- bins of the survey: phase-locked (conditional) averages inside the march (an addition to ABI 7: detect it by symbol) ----
+ *
+ * A survey can carry nbins bins and a table with one bin per kinematics row.  In a sampled step i whose bin is b =
+ * bin_of_row[i] >= 0, the five terms (u, w, u^2, w^2, u w) that the step adds to the plain sums -- the same (u, w)_i, formed
+ * exactly as above -- are added to bin b's own five sums [5][count] as well, and bin b's count grows by one.  A sampled step
+ * with bin -1 feeds the plain sums only; a step that is not sampled feeds nothing, whatever its entry.  With a table that
+ * follows the phase of a periodic motion, bin b's sums give the phase-averaged field at that phase.
+ * A binned step runs ONE finisher, as an unbinned one does (march_binned_survey_finish in place of march_survey_finish): the
+ * partial slab is read once, the plain sums are updated with the same expressions in the same order, then the bin's block.
+ * The host knows the bin of every step: no table goes to the device.  The bins' counts live on the host.
+ *
+ * ludvm_march_set_survey_bins: valid while a survey is set (LUDVM_E_STATE otherwise).  nbins = 0 removes the bins (the other
+ *   arguments are not looked at).  Otherwise 1 <= nbins <= LUDVM_MARCH_MAX_SURVEY_BINS; nbins * count <=
+ *   LUDVM_MARCH_MAX_SURVEY_BIN_POINTS (160 MiB of sums: a storage condition, not a measurement); rows must equal
+ *   ludvm_march_setup's kin_rows; every entry of bin_of_row lies in [-1, nbins); sums ([nbins][5][count], finite) and counts
+ *   ([nbins], >= 0) are both NULL (start from zero) or both given -- what ludvm_march_read_survey_bins returned when a run
+ *   is continued.  Everything is validated before anything is changed: a call refused with LUDVM_E_ARG leaves the bins that
+ *   were set, their sums and counts as they were.  A call that passes validation and then fails in the runtime leaves the
+ *   context WITHOUT bins.  ludvm_march_set_survey and ludvm_march_setup forget the bins; ludvm_march_set_survey_precision
+ *   does not.
+ * ludvm_march_read_survey_bins: sums[nbins][5][count] and counts[nbins] as they stand, at any time after the set call.
+ *   LUDVM_E_STATE when no bins are set.
+ * Guarantees: with bins set, everything ludvm_march_run produced before keeps its bits, the plain survey sums and the sample
+ *   count included; a context without bins enqueues exactly what it enqueued before.  Bin b's block equals, bit for bit, the
+ *   plain sums of a survey that samples exactly bin b's steps: the same slab, the same plan for a given step, the same
+ *   order.  The bin sums repeat bit for bit however a run is cut into ludvm_march_run calls (with sums and counts carried
+ *   over where the context is set up again).  Both survey precisions are served: they differ in the partial kernel only. */
+#define LUDVM_MARCH_MAX_SURVEY_BINS 64
+#define LUDVM_MARCH_MAX_SURVEY_BIN_POINTS 4194304
+int ludvm_march_set_survey_bins(ludvm_ctx* ctx, const int* bin_of_row, size_t rows, int nbins, const double* sums,
+                                const long long* counts);
+int ludvm_march_read_survey_bins(ludvm_ctx* ctx, double* sums, long long* counts);
+
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *
  * A parameter sweep (LESPcrit, k, alpha_max, dt, a gust vortex, 'Faure' / 'Ramesh') is `members` independent simulations,

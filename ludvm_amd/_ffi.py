@@ -36,6 +36,8 @@ ENSEMBLE_SURVEY_BYTES = 1 << 30  # most bytes of survey sums (members * 5 * 8 * 
 MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
 MARCH_MAX_TRACERS = 262144  # LUDVM_MARCH_MAX_TRACERS
 MARCH_MAX_SURVEY = 1048576  # LUDVM_MARCH_MAX_SURVEY
+MARCH_MAX_SURVEY_BINS = 64  # LUDVM_MARCH_MAX_SURVEY_BINS
+MARCH_MAX_SURVEY_BIN_POINTS = 4194304  # LUDVM_MARCH_MAX_SURVEY_BIN_POINTS: most bins x points (40 bytes of sums each) of ludvm_march_set_survey_bins
 SURVEY_PRECISIONS = {"f64": 0, "f32": 1}   # ludvm_march_set_survey_precision
 TRACER_PRECISIONS = {"f64": 0, "f32x2": 2}   # ludvm_march_set_tracer_precision (1 is left free: the survey's local-origin route)
 TRACER_F32X2_PER_LANE = 4  # kTracerF32PerLane (csrc/march_kernels.hpp): the hi+lo fp32 tracer kernel's tile is 256 lanes x this
@@ -103,6 +105,8 @@ SIGNATURES = {
     "ludvm_march_set_survey": [c_void_p, _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_longlong],
     "ludvm_march_read_survey": [c_void_p, _pd, POINTER(c_longlong)],
     "ludvm_march_set_survey_precision": [c_void_p, c_int],
+    "ludvm_march_set_survey_bins": [c_void_p, POINTER(c_int), c_size_t, c_int, _pd, POINTER(c_longlong)],
+    "ludvm_march_read_survey_bins": [c_void_p, _pd, POINTER(c_longlong)],
     "ludvm_march_set_tracer_precision": [c_void_p, c_int],
     "ludvm_ensemble_limits": [c_void_p, POINTER(c_longlong)],
     "ludvm_ensemble_run": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
@@ -140,7 +144,8 @@ SIGNATURES = {
 # added to ABI 7 without a new version number: a library of ABI 7 built before them is detected by the missing symbol
 ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm_march_read_tracers", "ludvm_march_tracer_state",
                   "ludvm_ensemble_run_traced", "ludvm_march_set_survey", "ludvm_march_read_survey", "ludvm_ensemble_run_surveyed",
-                  "ludvm_march_set_survey_precision", "ludvm_march_set_tracer_precision")
+                  "ludvm_march_set_survey_precision", "ludvm_march_set_tracer_precision", "ludvm_march_set_survey_bins",
+                  "ludvm_march_read_survey_bins")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -122,7 +122,7 @@ int ludvm_destroy(ludvm_ctx* c) {
                   c->xr, c->zr, c->cx, c->cz, c->march_tab.p, c->march_kin.p, c->march_rows.p, c->march_state.p, c->march_hist.p,
                   c->probe_xz.p, c->probe_shift.p, c->probe_part.p, c->probe_out.p, c->tracer_seed.p, c->tracer_release.p,
                   c->tracer_shift.p, c->tracer_cur.p, c->tracer_part.p, c->tracer_out.p, c->survey_xz.p, c->survey_shift.p, c->survey_sums.p,
-                  c->survey_part.p, c->ens_in.p, c->ens_work.p, c->ens_out.p};
+                  c->survey_part.p, c->survey_bin_sums.p, c->ens_in.p, c->ens_work.p, c->ens_out.p};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (auto& e : c->march_ev)

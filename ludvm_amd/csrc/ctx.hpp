@@ -131,6 +131,12 @@ struct ludvm_ctx {
   long long survey_first = 1, survey_stop = 0, survey_every = 1;   // sampled steps: first <= i < stop, (i - first) % every == 0
   long long survey_samples = 0;                // sampled steps the sums hold
   int survey_precision = 0;                    // 0: float64 pair sums; 1: fp32 on local origins (ludvm_march_set_survey_precision)
+  // bins of the survey (ludvm_march_set_survey_bins): the bin of every time step on the host (-1: none), one block of five
+  // sums per bin on the device [nbins][5][K], the samples of every bin on the host
+  Buf survey_bin_sums;
+  int survey_nbins = 0;                        // B (0: no bins)
+  std::vector<int> survey_bin_of_row;          // [kinematics rows]
+  std::vector<long long> survey_bin_samples;   // [B]
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

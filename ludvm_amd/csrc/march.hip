@@ -27,6 +27,7 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->survey_count = 0;      // ... and its survey (ludvm_march_set_survey)
   c->survey_samples = 0;
   c->survey_precision = 0;
+  c->survey_nbins = 0;      // ... and its bins (ludvm_march_set_survey_bins)
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -310,8 +311,15 @@ int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
                        (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
                        static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad, p.nsplit,
-                     (long long)K, static_cast<double*>(c->survey_sums.p));
+  // a step with a bin: one finisher, as without bins, that also updates the bin's block (the host knows the step's bin)
+  const int bin = c->survey_nbins ? c->survey_bin_of_row[(size_t)s] : -1;
+  if (bin >= 0)
+    hipLaunchKernelGGL(march_binned_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad,
+                       p.nsplit, (long long)K, static_cast<double*>(c->survey_sums.p),
+                       static_cast<double*>(c->survey_bin_sums.p) + (size_t)bin * kSurveySums * K);
+  else
+    hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad, p.nsplit,
+                       (long long)K, static_cast<double*>(c->survey_sums.p));
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
 }
@@ -341,6 +349,7 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
   c->survey_count = 0;
   c->survey_samples = 0;
   c->survey_precision = 0;         // float64 until ludvm_march_set_survey_precision says otherwise
+  c->survey_nbins = 0;             // (and no bins until ludvm_march_set_survey_bins)
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_xz, 2 * count * 8));
@@ -379,6 +388,56 @@ int ludvm_march_read_survey(ludvm_ctx* c, double* sums, long long* samples) {
   HIPCHK(c, hipMemcpyAsync(sums, c->survey_sums.p, kSurveySums * c->survey_count * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *samples = c->survey_samples;
+  return LUDVM_OK;
+}
+
+int ludvm_march_set_survey_bins(ludvm_ctx* c, const int* bin_of_row, size_t rows, int nbins, const double* sums,
+                                const long long* counts) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  const size_t K = c->survey_count;
+  if (nbins < 0 || nbins > LUDVM_MARCH_MAX_SURVEY_BINS)
+    return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_SURVEY_BINS) + " survey bins");
+  if (nbins == 0) {
+    c->survey_nbins = 0;
+    return LUDVM_OK;
+  }
+  if ((size_t)nbins * K > (size_t)LUDVM_MARCH_MAX_SURVEY_BIN_POINTS)
+    return fail(c, LUDVM_E_ARG, "march: survey bins x points over " + std::to_string(LUDVM_MARCH_MAX_SURVEY_BIN_POINTS) +
+                                    " (40 bytes of sums per bin and point)");
+  if (!bin_of_row) return fail(c, LUDVM_E_ARG, "null array");
+  if (rows != c->march_kin_rows) return fail(c, LUDVM_E_ARG, "march: survey bins must be one per kinematics row");
+  if ((sums == nullptr) != (counts == nullptr))
+    return fail(c, LUDVM_E_ARG, "march: survey bin sums and counts are given together or not at all");
+  for (size_t k = 0; k < rows; ++k)
+    if (bin_of_row[k] < -1 || bin_of_row[k] >= nbins) return fail(c, LUDVM_E_ARG, "march: a survey bin lies in [-1, nbins)");
+  const size_t doubles = (size_t)nbins * kSurveySums * K;
+  for (size_t k = 0; sums && k < doubles; ++k)
+    if (!std::isfinite(sums[k])) return fail(c, LUDVM_E_ARG, "march: survey bin sums must be finite");
+  for (int b = 0; counts && b < nbins; ++b)
+    if (counts[b] < 0) return fail(c, LUDVM_E_ARG, "march: survey bin counts must be >= 0");
+  c->survey_nbins = 0;             // (a failure from here on leaves the context without bins)
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->survey_bin_sums, doubles * 8));
+  if (sums) HIPCHK(c, hipMemcpyAsync(c->survey_bin_sums.p, sums, doubles * 8, hipMemcpyHostToDevice, c->stream));
+  else HIPCHK(c, hipMemsetAsync(c->survey_bin_sums.p, 0, doubles * 8, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->survey_bin_of_row.assign(bin_of_row, bin_of_row + rows);
+  if (counts) c->survey_bin_samples.assign(counts, counts + nbins);
+  else c->survey_bin_samples.assign((size_t)nbins, 0);
+  c->survey_nbins = nbins;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_survey_bins(ludvm_ctx* c, double* sums, long long* counts) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0 || c->survey_nbins == 0) return fail(c, LUDVM_E_STATE, "march: no survey bins are set");
+  if (!sums || !counts) return fail(c, LUDVM_E_ARG, "null array");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(sums, c->survey_bin_sums.p, (size_t)c->survey_nbins * kSurveySums * c->survey_count * 8,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < c->survey_nbins; ++b) counts[b] = c->survey_bin_samples[(size_t)b];
   return LUDVM_OK;
 }
 
@@ -569,6 +628,12 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   size_t trec_at = 0;               // the next recorded step
   const bool survey = c->survey_count != 0;
   long long surveyed = 0;           // sampled steps of this call
+  std::vector<long long> binned(survey ? (size_t)c->survey_nbins : 0, 0);     // ... and those of every bin
+  auto count_bin = [&](long long sstep) {
+    if (binned.empty()) return;
+    const int b = c->survey_bin_of_row[(size_t)sstep];
+    if (b >= 0) ++binned[(size_t)b];
+  };
 
   MarchState hs{};
   hs.n = n0;
@@ -703,6 +768,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
       if (survey && survey_samples_step(c, s)) {
         CHK(march_survey_launch(c, c->stream, n_ub, s));
         ++surveyed;
+        count_bin(s);
       }
       MarchSym ms;
       ms.scale = &S->sc[(s + 1) & 1]; ms.bad = &S->sym_bad; ms.n_lo = n_lo + 1; ms.march = overlap_ok;
@@ -742,6 +808,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
       if (rc == LUDVM_OK && survey && survey_samples_step(c, s)) {
         rc = march_survey_launch(c, c->stream_b, n_ub, s);
         ++surveyed;
+        count_bin(s);
       }
       c->stream = main_stream;
       CHK(rc);
@@ -803,6 +870,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   if (probes) c->probe_rows = (size_t)count;
   if (tracers) { c->tracer_rows = trec; c->tracer_ran = true; }
   c->survey_samples += surveyed;
+  for (size_t b = 0; b < binned.size(); ++b) c->survey_bin_samples[b] += binned[b];
   return LUDVM_OK;
 }
 

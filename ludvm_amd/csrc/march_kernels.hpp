@@ -716,6 +716,8 @@ march_tracer_finish(const double* slab, long long m_pad, int nsplit, const doubl
 //                       (split, point) partial sums to a slab [split][2][k_pad] of the survey's own
 // march_survey_finish   one lane per point: splits 0, 1, 2, ... in that order give (u, w), then sums[0..4][k] += with plain
 //                       loads and stores (the lane is the only writer of its point; steps follow each other in stream order)
+// march_binned_survey_finish  march_survey_finish for a sampled step that has a bin (ludvm_march_set_survey_bins), launched in its
+//                       place: the same (u, w) and the same update of sums, then the same five terms into the bin's own block
 // The splits are a function of the point count and of the step's anchor-derived bound alone (survey_plan, march.hip), every
 // partial sum is formed by one lane in source order, the splits are combined in split order and the steps in step order: the
 // sums repeat bit for bit however a run is cut into calls.  Both kernels write the survey's buffers only.
@@ -966,6 +968,37 @@ march_survey_finish(const double* slab, long long k_pad, int nsplit, long long c
   s[2 * count] = __builtin_fma(u, u, s[2 * count]);
   s[3 * count] = __builtin_fma(w, w, s[3 * count]);
   s[4 * count] = __builtin_fma(u, w, s[4 * count]);
+}
+
+// The finisher of a sampled step that has a bin (ludvm_march_set_survey_bins), launched INSTEAD of march_survey_finish: the
+// slab is read once, `sums` is updated with march_survey_finish's very expressions in its order (the plain sums cannot change a
+// bit), then the bin's own block bin_sums[5][count] -- the host knows the step's bin and passes the block -- with the same
+// five terms in the same way: a bin's block is, bit for bit, the plain sums of a survey that samples that bin's steps alone.
+// One lane per point, loads and stores at stride `count` (coalesced), no LDS; serves both survey precisions, which differ
+// only in the partial kernel.  Writes the survey's buffers only.
+__global__ void __launch_bounds__(kBlock)
+march_binned_survey_finish(const double* slab, long long k_pad, int nsplit, long long count, double* sums, double* bin_sums) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (m >= count) return;
+  double u = 0.0, w = 0.0;
+  const double* c0 = slab + m;
+  for (int sidx = 0; sidx < nsplit; ++sidx) {
+    u += c0[(long long)sidx * 2 * k_pad];
+    w += c0[(long long)sidx * 2 * k_pad + k_pad];
+  }
+  double* s = sums + m;
+  s[0] += u;
+  s[count] += w;
+  s[2 * count] = __builtin_fma(u, u, s[2 * count]);
+  s[3 * count] = __builtin_fma(w, w, s[3 * count]);
+  s[4 * count] = __builtin_fma(u, w, s[4 * count]);
+  double* b = bin_sums + m;
+  b[0] += u;
+  b[count] += w;
+  b[2 * count] = __builtin_fma(u, u, b[2 * count]);
+  b[3 * count] = __builtin_fma(w, w, b[3 * count]);
+  b[4 * count] = __builtin_fma(u, w, b[4 * count]);
 }
 
 // ---- the tracers' field in hi+lo fp32 (ludvm_march_set_tracer_precision) ---------------------------------------------------------

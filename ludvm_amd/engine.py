@@ -373,6 +373,7 @@ class Engine:
         self._march_nprobes = 0          # (ludvm_march_setup forgets any probes)
         self._march_ntracers = 0         # (... and any tracers)
         self._march_nsurvey = 0          # (... and any survey)
+        self._march_nbins = 0            # (... and its bins)
 
     def march_run(self, first_step, count, precision, state, hist_nmax=0, anchors=None):
         """Advance the resident wake through time steps [first_step, first_step + count) without a host round
@@ -482,6 +483,40 @@ class Engine:
         self._check(self._lib.ludvm_march_set_survey(self._ctx, _pd(xs), _pd(zs), len(xs), _pd(sh), 0 if sh is None else len(sh),
                                                      int(first), stop, int(every), _pd(sm), int(samples)))
         self._march_nsurvey = len(xs)
+        self._march_nbins = 0            # (ludvm_march_set_survey forgets any bins)
+
+    def march_set_survey_bins(self, table, nbins, sums=None, counts=None):
+        """Bins of the survey (ludvm_march_set_survey_bins); valid while a survey is set.  table: one bin per kinematics row,
+        -1 .. nbins - 1 -- a sampled step i with table[i] = b >= 0 also adds its five terms to bin b's own sums and one to
+        bin b's count.  sums [nbins, 5, K] and counts [nbins] continue a run (what `march_survey_bins` returned), both or
+        neither.  nbins = 0 removes the bins."""
+        if not hasattr(self._lib, "ludvm_march_set_survey_bins"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_survey_bins")
+        tb = np.ascontiguousarray(table, dtype=np.intc).reshape(-1)
+        nbins = int(nbins)
+        sm = cn = None
+        if sums is not None:
+            sm = np.ascontiguousarray(sums, dtype=np.float64)
+            if sm.shape != (nbins, 5, getattr(self, "_march_nsurvey", 0)):
+                raise ValueError("march_set_survey_bins: sums must be [nbins, 5, K]")
+        if counts is not None:
+            cn = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+            if len(cn) != nbins:
+                raise ValueError("march_set_survey_bins: counts must be [nbins]")
+        self._check(self._lib.ludvm_march_set_survey_bins(
+            self._ctx, tb.ctypes.data_as(POINTER(ctypes.c_int)) if len(tb) else None, len(tb), nbins, _pd(sm),
+            None if cn is None else cn.ctypes.data_as(POINTER(c_longlong))))
+        self._march_nbins = nbins
+
+    def march_survey_bins(self):
+        """(sums float64 [B, 5, K], counts int64 [B]): the raw sums of every bin of the survey and the sampled steps each holds
+        (ludvm_march_read_survey_bins)."""
+        if not hasattr(self._lib, "ludvm_march_read_survey_bins"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_read_survey_bins")
+        B = getattr(self, "_march_nbins", 0)
+        sums, counts = np.empty([B, 5, getattr(self, "_march_nsurvey", 0)]), np.zeros(max(B, 1), dtype=np.int64)
+        self._check(self._lib.ludvm_march_read_survey_bins(self._ctx, _pd(sums), counts.ctypes.data_as(POINTER(c_longlong))))
+        return sums, counts[:B].copy()
 
     def march_set_tracer_precision(self, precision):
         """How the marched steps evaluate the field at the released tracers (ludvm_march_set_tracer_precision): 'f64' (what

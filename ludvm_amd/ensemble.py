@@ -38,6 +38,9 @@ _REFUSED = {
     "survey": (None, "the survey of a sweep is common to it: sweep(cases, survey=...)"),
     "survey_steps": (None, "the survey of a sweep is common to it: sweep(cases, survey=...)"),
     "survey_frame": ("lab", "the survey of a sweep is common to it: sweep(cases, survey=...)"),
+    "survey_bins": (None, "binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)"),
+    "survey_period": (None, "binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)"),
+    "survey_phase0": (None, "binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)"),
 }
 
 
@@ -240,6 +243,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     if "tracer_precision" in common:
         raise ValueError(f"sweep: tracer_precision={common['tracer_precision']!r}: the tracers of a sweep are advected in float64 "
                          "(fp32 tracer sums: run a member on its own, LUDVM(..., tracers=..., tracer_precision='f32x2'))")
+    for key in ("survey_bins", "survey_period", "survey_phase0"):
+        if common.get(key) is not None:
+            raise ValueError(f"sweep: {key}={common[key]!r}: binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)")
     cases = list(cases)
     if not cases:
         return []

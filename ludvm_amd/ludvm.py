@@ -20,6 +20,7 @@ import timeit
 
 import numpy as np
 
+from . import _ffi
 from .engine import Engine
 
 __all__ = ["LUDVM", "SparseHistory"]
@@ -160,6 +161,26 @@ class LUDVM:
                  however the run is cut, checkpoints included (they carry the value).  Refused: without `survey`, with
                  march=False, in a sweep; a run that cannot take the march raises instead of falling back to float64.  The
                  object carries `survey_precision` as used
+      survey_bins  None (default), or the bins of a phase-locked (conditional) survey: an int B (1 .. 64) divides the motion's
+                 period into B equal phase bins -- with t = self.t, tau = (t - survey_phase0) / survey_period, the bin of a step is
+                 floor(B (tau - floor(tau)) + 1e-9) % B -- or an integer array [nt] with values -1 .. B-1 (B = max + 1) gives the
+                 bin of every time step by any criterion (-1: none).  In a sampled step whose bin is b >= 0 the five terms the
+                 step adds to the survey's sums are added to bin b's own five sums as well (inside the device-resident march: one
+                 finisher kernel per sampled step, as without bins; or beside the plain sums on the per-step path); B x K <=
+                 4194304.  Results, mesh-shaped as the survey's: `survey_nbins`, `survey_bin_of_step` (int64 [nt]: the table as
+                 the run uses it, -1 where a step is not sampled or has no bin), `survey_bin_count` [B], `survey_bin_sums`
+                 [B, 5, ...], `survey_bin_mean_u`, `survey_bin_mean_w`, the central moments within each bin `survey_bin_uu`,
+                 `survey_bin_ww`, `survey_bin_uw` (nan for an empty bin), `survey_phase` [B] (bin centres (b + 0.5) / B; None for
+                 a table), and the triple decomposition over the binned samples (N = sum n_b): `survey_coherent_uu`, `_ww`, `_uw`
+                 = sum_b n_b (a_b - a)(b_b - b) / N of the bin means about the mean, `survey_random_uu`, `_ww`, `_uw` = sum_b
+                 n_b survey_bin_ab[b] / N; coherent + random is the total central moment, `survey_uu` / `ww` / `uw` when every
+                 sampled step has a bin.  A bin's sums are, bit for bit, the plain sums of a survey that samples that bin's steps;
+                 the plain sums and every other result keep their bits; the bin sums repeat bit for bit however the run is cut,
+                 checkpoints included.  Refused: without `survey`, B outside 1 .. 64, B x K over the
+                 cap, a table that is not [nt] integers >= -1, a window in which no sampled step has a bin, in a sweep
+      survey_period  the period, a time, of the int form of `survey_bins`; default 1 / self.f, the period of the motion (refused
+                 when that is infinite, and when not finite and positive)
+      survey_phase0  the time of phase 0 of the int form of `survey_bins`; default t0
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -277,6 +298,58 @@ class LUDVM:
             raise ValueError("survey_precision='f32' is evaluated inside the device-resident march: not with march=False")
 
     @staticmethod
+    def _check_survey_bins(survey_bins, survey_period, survey_phase0, K, win, t, t0, f):
+        """-> (survey_bin_of_step int64 [nt]: the bin of every sampled step, -1 elsewhere; B; the bin centres [B] or None for an
+        explicit table), or ValueError (nothing else has been created yet).  K: survey points; win: the window as used; t: the
+        time levels; f: the motion's frequency."""
+        most, nt = _ffi.MARCH_MAX_SURVEY_BINS, len(t)
+        if survey_bins is None:
+            raise ValueError("survey_period / survey_phase0 need `survey_bins`")
+        for name, v in (("survey_period", survey_period), ("survey_phase0", survey_phase0)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v)):
+                raise ValueError(f"{name} must be a finite number (got {v!r})")
+        if survey_period is not None and not survey_period > 0:
+            raise ValueError(f"survey_period must be finite and > 0 (got {survey_period!r})")
+        if isinstance(survey_bins, bool):
+            raise ValueError("survey_bins must be an int B or an integer array [nt]")
+        if isinstance(survey_bins, (int, np.integer)):
+            B = int(survey_bins)
+            if not 1 <= B <= most:
+                raise ValueError(f"survey_bins: 1 <= B <= {most} (got {B})")
+            if survey_period is None:
+                if not f > 0:
+                    raise ValueError("survey_bins: the motion has no period (k = 0): give survey_period")
+                survey_period = 1.0 / f
+            tau = (t - (t0 if survey_phase0 is None else survey_phase0)) / survey_period
+            table = (np.floor(B * (tau - np.floor(tau)) + 1e-9).astype(np.int64)) % B
+            phase = (np.arange(B) + 0.5) / B
+        else:
+            if survey_period is not None or survey_phase0 is not None:
+                raise ValueError("survey_period / survey_phase0 go with survey_bins=B (an int), not with an explicit table")
+            try:
+                raw = np.asarray(survey_bins)
+            except (TypeError, ValueError) as e:
+                raise ValueError("survey_bins must be an int B or an integer array [nt]") from e
+            if raw.dtype.kind not in 'iu' or raw.shape != (nt,):
+                raise ValueError(f"survey_bins: a table holds one integer per time step, [nt] with nt = {nt}")
+            table = raw.astype(np.int64)
+            if table.min() < -1:
+                raise ValueError("survey_bins: a table's entries are -1 (no bin) or a bin 0 .. B-1")
+            B, phase = int(table.max()) + 1, None
+            if B > most:
+                raise ValueError(f"survey_bins: at most {most} bins (the table's largest entry is {B - 1})")
+        if B * K > _ffi.MARCH_MAX_SURVEY_BIN_POINTS:
+            raise ValueError(f"survey_bins: {B} bins x {K} points: at most {_ffi.MARCH_MAX_SURVEY_BIN_POINTS} bins x points "
+                             "(40 bytes of sums each)")
+        first, stop, every = win
+        sampled = np.zeros(nt, dtype=bool)
+        sampled[first:stop:every] = True
+        table = np.where(sampled, table, -1)
+        if B < 1 or not (table >= 0).any():
+            raise ValueError("survey_bins: no sampled step of the window has a bin")
+        return table, B, phase
+
+    @staticmethod
     def _check_tracer_precision(tracer_precision, traced, march=True):
         """ValueError from the keywords alone (nothing else has been created yet)."""
         if not isinstance(tracer_precision, str) or tracer_precision not in ('f64', 'f32x2'):
@@ -336,7 +409,8 @@ class LUDVM:
                  engine=None, device=0, precision='auto', history='auto', snapshot_steps=(), run=True,
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
                  probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
-                 survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64', tracer_precision='f64'):
+                 survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64', tracer_precision='f64',
+                 survey_bins=None, survey_period=None, survey_phase0=None):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -366,6 +440,13 @@ class LUDVM:
         elif survey_steps is not None:
             raise ValueError("survey_steps needs `survey`")
         self._check_survey_precision(survey_precision, survey is not None, march)
+        binned = survey_bins is not None or survey_period is not None or survey_phase0 is not None
+        if binned:
+            if survey is None:
+                raise ValueError("survey_bins / survey_period / survey_phase0 need `survey`")
+            bin_table, bin_count, bin_phase = self._check_survey_bins(
+                survey_bins, survey_period, survey_phase0, survey_xz.shape[1], survey_win, np.arange(t0, tf + dt, dt), t0,
+                k * Uinf / (2 * np.pi * chord))
         # the smallest section the method runs: two panels; the loads read A0 .. A3 (LUDVM.py:1035-1090)
         if Npoints < 3:
             raise ValueError(f"Npoints={Npoints}: a section has at least 3 points (2 panels)")
@@ -398,6 +479,11 @@ class LUDVM:
             self.survey_precision = survey_precision
             if self.survey_precision != 'f64':      # (a float64 survey keeps the checkpoints it had)
                 self._ctor.update(survey_precision=self.survey_precision)
+            if binned:                              # (a survey without bins keeps the checkpoints it had)
+                self._ctor.update(survey_bins=int(survey_bins) if np.ndim(survey_bins) == 0 else [int(v) for v in np.asarray(survey_bins).reshape(-1)],
+                                  survey_period=None if survey_period is None else float(survey_period),
+                                  survey_phase0=None if survey_phase0 is None else float(survey_phase0))
+                self.survey_nbins, self.survey_bin_of_step, self.survey_phase = bin_count, bin_table, bin_phase
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -675,6 +761,8 @@ class LUDVM:
                 self.tracer_last = eng.march_tracer_state() if S.can_march else S.tcur
             if S.survey is not None:
                 self._survey_results(*(eng.march_survey() if S.can_march else (S.ssums, S.scount)))
+            if S.sbins is not None:
+                self._survey_bin_results(*(eng.march_survey_bins() if S.can_march else (S.sbsums, S.sbcounts)))
         finally:
             if self._shard is not None:
                 self._shard.detach(eng)
@@ -688,7 +776,7 @@ class LUDVM:
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
             'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
-            'tracers', 'trec', 'tcur', 'survey', 'ssums', 'scount',
+            'tracers', 'trec', 'tcur', 'survey', 'ssums', 'scount', 'sbins', 'sbsums', 'sbcounts',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
@@ -800,6 +888,12 @@ class LUDVM:
         if S.survey is not None:
             # the five raw sums the per-step path accumulates (the march keeps its own on the device), or a checkpoint's
             S.ssums = np.zeros([5, S.survey.shape[1]])
+        S.sbins = getattr(self, 'survey_bin_of_step', None)
+        S.sbsums = S.sbcounts = None
+        if S.sbins is not None:
+            # likewise for the bins: [B][5][K] and the samples of every bin
+            S.sbsums = np.zeros([self.survey_nbins, 5, S.survey.shape[1]])
+            S.sbcounts = np.zeros(self.survey_nbins, dtype=np.int64)
         return S
 
     def _survey_sampled(self, step):
@@ -822,6 +916,31 @@ class LUDVM:
             mu, mw = su / n, sw / n
             self.survey_mean_u, self.survey_mean_w = mu, mw
             self.survey_uu, self.survey_ww, self.survey_uw = suu / n - mu * mu, sww / n - mw * mw, suw / n - mu * mw
+
+    def _survey_bin_results(self, sums, counts):
+        """The binned survey's attributes from the raw sums [B, 5, K] and the samples [B] of every bin: the phase averages, the
+        central moments within each bin, and the triple decomposition of the binned samples' fluctuation into its coherent part
+        (the bin means about the overall mean) and its random part (the scatter within the bins)."""
+        shape, B = self._survey_shape, self.survey_nbins
+        self.survey_bin_count = np.array(counts, dtype=np.int64)
+        self.survey_bin_sums = np.array(sums, dtype=np.float64).reshape((B, 5) + shape)
+        n = self.survey_bin_count.reshape((B,) + (1,) * len(shape)).astype(np.float64)
+        su, sw, suu, sww, suw = (self.survey_bin_sums[:, c] for c in range(5))
+        with np.errstate(divide='ignore', invalid='ignore'):       # (an empty bin: nan, as n = 0 gives for the plain moments)
+            mu, mw = su / n, sw / n
+            self.survey_bin_mean_u, self.survey_bin_mean_w = mu, mw
+            self.survey_bin_uu, self.survey_bin_ww, self.survey_bin_uw = suu / n - mu * mu, sww / n - mw * mw, suw / n - mu * mw
+        N = float(self.survey_bin_count.sum())
+        full = self.survey_bin_count > 0
+        nb = n[full]
+        with np.errstate(divide='ignore', invalid='ignore'):       # (N = 0: a run that stopped before its first binned step)
+            tu, tw = su[full].sum(axis=0) / N, sw[full].sum(axis=0) / N          # the mean of the binned samples
+            du, dw = mu[full] - tu, mw[full] - tw
+            self.survey_coherent_uu, self.survey_coherent_ww = (nb * du * du).sum(axis=0) / N, (nb * dw * dw).sum(axis=0) / N
+            self.survey_coherent_uw = (nb * du * dw).sum(axis=0) / N
+            self.survey_random_uu = (nb * self.survey_bin_uu[full]).sum(axis=0) / N
+            self.survey_random_ww = (nb * self.survey_bin_ww[full]).sum(axis=0) / N
+            self.survey_random_uw = (nb * self.survey_bin_uw[full]).sum(axis=0) / N
 
     def _tracer_seeds(self, step):
         """Lab coordinates [2, M] of the seeds at time step `step` ('tunnel' frame: x + xpiv[step])."""
@@ -861,6 +980,8 @@ class LUDVM:
                 self.tracer_path.store(int(srow), row.copy())
         if S.survey is not None:
             S.ssums, S.scount = R['survey_sums'].copy(), int(R['survey_samples'])
+        if S.sbins is not None:
+            S.sbsums, S.sbcounts = R['survey_bin_sums'].copy(), R['survey_bin_counts'].astype(np.int64)
         for key in ('TEV', 'LEV', 'FREE'):
             if self.history == 'full':
                 P[key][:S.first_step] = R['path_' + key]
@@ -880,6 +1001,9 @@ class LUDVM:
             raise RuntimeError("tracers: this engine marches but has no march_set_tracers (pass march=False for the per-step path)")
         if S.survey is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey'):
             raise RuntimeError("survey: this engine marches but has no march_set_survey (pass march=False for the per-step path)")
+        if S.sbins is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_bins'):
+            raise RuntimeError("survey_bins: this engine marches but has no march_set_survey_bins (pass march=False for the per-step "
+                               "path)")
         f32_tracers = S.tracers is not None and self.tracer_precision == 'f32x2'
         if f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_precision'):
             raise RuntimeError("tracer_precision='f32x2': this engine marches but has no march_set_tracer_precision")
@@ -909,6 +1033,10 @@ class LUDVM:
                                      steps=self.survey_steps, sums=S.ssums if S.scount else None, samples=S.scount)
                 if f32_survey:
                     eng.march_set_survey_precision('f32')
+                if S.sbins is not None:
+                    carried = bool(S.sbcounts.any())
+                    eng.march_set_survey_bins(S.sbins, self.survey_nbins, sums=S.sbsums if carried else None,
+                                              counts=S.sbcounts if carried else None)
         if f32_tracers and not S.can_march:
             # (no float64 in its place: the per-step path has no fp32 tracer sums)
             raise RuntimeError("tracer_precision='f32x2' is evaluated inside the device-resident march, which this run cannot take "
@@ -1271,6 +1399,11 @@ class LUDVM:
             for acc, term in zip(S.ssums, (u, w, u * u, w * w, u * w)):
                 acc += term
             S.scount += 1
+            if S.sbins is not None and S.sbins[i] >= 0:
+                # ... and to the sums of the step's bin, the same terms in the same order
+                for acc, term in zip(S.sbsums[S.sbins[i]], (u, w, u * u, w * w, u * w)):
+                    acc += term
+                S.sbcounts[S.sbins[i]] += 1
         n_after = n_wake + len(new_x)
         one_trip = (not record) and sb is not None and i < nt - 1 and hasattr(eng, 'wake_step_into')
         if not one_trip:
@@ -1373,6 +1506,8 @@ class LUDVM:
             d['tracer_rows'] = np.stack([self.tracer_path[q] for q in steps_t])
         if S.survey is not None:        # (likewise; the sums and the count of sampled steps so far)
             d['survey_sums'], d['survey_samples'] = self.engine.march_survey() if S.can_march else (S.ssums, S.scount)
+        if S.sbins is not None:         # (likewise; the sums and the samples of every bin so far)
+            d['survey_bin_sums'], d['survey_bin_counts'] = self.engine.march_survey_bins() if S.can_march else (S.sbsums, S.sbcounts)
         if self.history == 'full':
             for key in ('TEV', 'LEV', 'FREE'):
                 d['path_' + key] = P[key][:next_step]

@@ -9,6 +9,10 @@ pair_f64's and pair_f32's on the same points and wake.
     python tools/survey_cost.py time   --survey K [--repeats R] [--every E] [--first F]
                                                                               wall time, added time per sampled step and pair
                                                                               count: a float64 and an fp32 column, and their ratio
+    python tools/survey_cost.py time   --survey K --bins B [--repeats R] [--every E] [--first F] [--precision f64|f32]
+                                                                              the same run with the survey alone and with B phase
+                                                                              bins (survey_bins=B), alternated: the added time
+                                                                              per sampled step of each, side by side
     python tools/survey_cost.py once   --survey K [--induce] [--every E] [--first F]
                                                                               one run per precision (under rocprofv3); --induce:
                                                                               also 5 Engine.induce calls in f64 and 5 in f32, K
@@ -34,6 +38,8 @@ ap.add_argument("mode", choices=["ab", "time", "once", "stats"])
 ap.add_argument("files", nargs="*")
 ap.add_argument("--survey", type=int, default=0)
 ap.add_argument("--every", type=int, default=1)
+ap.add_argument("--bins", type=int, default=0, help="time: B phase bins against the survey alone")
+ap.add_argument("--precision", default="f64", choices=["f64", "f32"], help="the survey's precision of the --bins comparison")
 ap.add_argument("--first", type=int, default=1)
 ap.add_argument("--lespcrit", type=float, default=0.2, help="10: no leading-edge vortex is shed, the wake is one sheet")
 ap.add_argument("--induce", action="store_true")
@@ -139,6 +145,27 @@ if args.mode == "once":
             for _ in range(5):
                 eng.induce(g, x, z, px + sim.xpiv[-1], pz, sim.v_core, precision=prec)
         print(f"Engine.induce: 5 calls in f64 and 5 in f32 of {args.survey} points x {n} sources = {5.0 * args.survey * n:.6g} pairs each")
+elif args.bins:
+    base = extras(args.survey, args.precision)
+    binned = dict(base, survey_bins=args.bins)
+    for extra in ({}, base, binned):
+        run(eng, **extra)
+    ts = {"plain": [], "survey": [], "binned": []}
+    for _ in range(args.repeats):
+        ts["plain"].append(run(eng)[0])
+        ts["survey"].append(run(eng, **base)[0])
+        t, sim = run(eng, **binned)
+        ts["binned"].append(t)
+    nb = int(sim.survey_bin_count.sum())
+    med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+    print(f"{sim.nt - 1} steps, K={args.survey}, survey_precision={args.precision}, {sim.survey_count} sampled steps (first {args.first}, "
+          f"every {args.every}), {args.bins} bins holding {nb} of them ({sim.survey_bin_count.min()} .. {sim.survey_bin_count.max()} per bin)")
+    print(f"plain:            {spread(ts['plain'])}")
+    for name, label in (("survey", "survey alone:    "), ("binned", f"survey, {args.bins:2d} bins: ")):
+        add = med[name] - med["plain"]
+        print(f"{label} {spread(ts[name])}; added {add:.4f} s = {add / sim.survey_count * 1e6:.2f} us per sampled step")
+    print(f"the bins add {(med['binned'] - med['survey']) / max(nb, 1) * 1e6:.2f} us per binned step (one finisher per sampled step "
+          "either way; the binned one also updates the bin's five sums)")
 else:
     run(eng)
     for prec in ("f64", "f32"):
