@@ -119,26 +119,18 @@ void march_workspace(const ludvm_ctx* c, long long n_ub, int precision, size_t n
   part_bytes = std::max(part_bytes, (size_t)q.nsplit * 2 * (size_t)q.nt_pad * 8);
 }
 
-// Launch rule of the probe kernels.  P probes in tiles of 64 (one wavefront each); the sources -- at most ns_ub = n_ub + nfoil,
-// n_ub the step's anchor-derived bound of the wake size after its solve -- in `nsplit` splits of `chunk` sources, a multiple
-// of the 256-source LDS tile, chosen so that tiles x splits comes to about 1024 wavefronts (one per SIMD of the device).  A
-// function of P and n_ub alone: the summation order of a step does not depend on where the calls of a run begin.
-struct ProbePlan { long long ptiles, p_pad, chunk; int nsplit; };
-constexpr long long kProbeWaves = 1024;
-ProbePlan probe_plan(size_t count, long long ns_ub) {
-  ProbePlan p;
-  p.ptiles = ((long long)count + kProbeLanes - 1) / kProbeLanes;
-  p.p_pad = p.ptiles * kProbeLanes;
-  const long long want = std::max<long long>(1, kProbeWaves / p.ptiles);
-  ns_ub = std::max<long long>(ns_ub, 1);
-  p.chunk = std::max<long long>(kProbeTile, ((ns_ub + want - 1) / want + kProbeTile - 1) / kProbeTile * kProbeTile);
-  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
-  return p;
+// The launch rule of the observer kernels is observer_plan (plan_rule.hpp); its tiles are the kernels'.
+constexpr bool rule_is(ObserverKind kind, int point_tile, int src_tile) {
+  return kObserverRules[kind].point_tile == point_tile && kObserverRules[kind].src_tile == src_tile;
 }
-// the slab of any step: nsplit <= max(1, 1024 / ptiles) whatever the wake size
-size_t probe_slab_bytes(size_t count) {
-  const ProbePlan p = probe_plan(count, 1);
-  return (size_t)std::max<long long>(1, kProbeWaves / p.ptiles) * 2 * (size_t)p.p_pad * 8;
+static_assert(rule_is(kObsProbes, kProbeLanes, kFieldTile) && rule_is(kObsTracers, kTracerTile, kFieldTile) &&
+                  rule_is(kObsTracersF32x2, kTracerF32Tile, kHiloTile) && rule_is(kObsSurvey, kSurveyTile, kFieldTile) &&
+                  rule_is(kObsSurveyF32, kSurveyF32Tile, kLocalTile),
+              "the observer rules' point and source tiles are the kernels'");
+
+// the x offset of time step s (NULL: the lab frame)
+const double* step_shift(const Buf& shift, bool shifted, long long s) {
+  return shifted ? static_cast<const double*>(shift.p) + s : nullptr;
 }
 
 // Probe row `rel` of the call: the field of [0, S->n + nfoil) -- the wake before step s's roll-up, its shed vortices, the
@@ -149,62 +141,19 @@ size_t probe_slab_bytes(size_t count) {
 int march_probe_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s, long long rel, long long rows) {
   const MarchSetup& m = c->msetup;
   const size_t P = c->probe_count;
-  const ProbePlan p = probe_plan(P, n_ub + (long long)m.npan);
+  const ObserverPlan p = observer_plan(kObserverRules[kObsProbes], (long long)P, n_ub + (long long)m.npan);
   const double* pxz = static_cast<const double*>(c->probe_xz.p);
-  const double* shift = c->probe_shifted ? static_cast<const double*>(c->probe_shift.p) + s : nullptr;
+  const double* shift = step_shift(c->probe_shift, c->probe_shifted, s);
   double* slab = static_cast<double*>(c->probe_part.p);
   double* out = static_cast<double*>(c->probe_out.p);
-  hipLaunchKernelGGL(march_probe_partial, dim3((unsigned)p.ptiles, (unsigned)p.nsplit), dim3(kProbeLanes), 0, st, pxz, pxz + P, shift,
-                     (int)P, p.p_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+  hipLaunchKernelGGL(march_probe_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kProbeLanes), 0, st, pxz, pxz + P, shift,
+                     (int)P, p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
                      static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(march_probe_finish, dim3(blocks_for((long long)(2 * P * 64))), dim3(kBlock), 0, st, (const double*)slab, p.p_pad,
+  hipLaunchKernelGGL(march_probe_finish, dim3(blocks_for((long long)(2 * P * 64))), dim3(kBlock), 0, st, (const double*)slab, p.pad,
                      p.nsplit, (int)P, out + (size_t)rel * P, out + ((size_t)rows + (size_t)rel) * P);
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
-}
-
-// Launch rule of the tracer kernels.  M tracers in tiles of kTracerTile (256 lanes x kTracerPerLane); the sources -- at most
-// ns_ub = n_ub + nfoil, n_ub the step's anchor-derived bound of the wake size after its solve -- in `nsplit` splits of `chunk`
-// sources, a multiple of the 256-source LDS tile, chosen so that tiles x splits comes to about 1024 workgroups (four per
-// CU), with at most 64 splits (the finisher adds them one after the other).  A function of M and n_ub alone: the summation
-// order of a step does not depend on where the calls of a run begin.
-struct TracerPlan { long long ttiles, m_pad, chunk; int nsplit; };
-constexpr long long kTracerGroups = 1024, kTracerMaxSplit = 64;
-long long tracer_want(long long ttiles) { return std::min(kTracerMaxSplit, std::max<long long>(1, kTracerGroups / ttiles)); }
-TracerPlan tracer_plan(size_t count, long long ns_ub) {
-  TracerPlan p;
-  p.ttiles = ((long long)count + kTracerTile - 1) / kTracerTile;
-  p.m_pad = p.ttiles * kTracerTile;
-  const long long want = tracer_want(p.ttiles);
-  ns_ub = std::max<long long>(ns_ub, 1);
-  p.chunk = std::max<long long>(kTracerSrcTile, ((ns_ub + want - 1) / want + kTracerSrcTile - 1) / kTracerSrcTile * kTracerSrcTile);
-  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
-  return p;
-}
-// the slab of any step: nsplit <= tracer_want(ttiles) whatever the wake size (at most 8 MiB)
-size_t tracer_slab_bytes(size_t count) {
-  const TracerPlan p = tracer_plan(count, 1);
-  return (size_t)tracer_want(p.ttiles) * 2 * (size_t)p.m_pad * 8;
-}
-
-// Launch rule of the hi+lo fp32 tracer kernel (march_f32x2_tracer_partial): tracer_plan's form and constants with its own
-// tracer tile (256 lanes x kTracerF32PerLane).  `chunk` is a multiple of the 256-source tile the kernel stages.  A function of M
-// and n_ub alone.
-TracerPlan tracer_plan_f32x2(size_t count, long long ns_ub) {
-  TracerPlan p;
-  p.ttiles = ((long long)count + kTracerF32Tile - 1) / kTracerF32Tile;
-  p.m_pad = p.ttiles * kTracerF32Tile;
-  const long long want = tracer_want(p.ttiles);
-  ns_ub = std::max<long long>(ns_ub, 1);
-  p.chunk = std::max<long long>(kHiloTile, ((ns_ub + want - 1) / want + kHiloTile - 1) / kHiloTile * kHiloTile);
-  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
-  return p;
-}
-// the fp32 kernel's slab of any step (at most 16 MiB: want x m_pad <= 1024 tiles of 1024 tracers)
-size_t tracer_slab_bytes_f32x2(size_t count) {
-  const TracerPlan p = tracer_plan_f32x2(count, 1);
-  return (size_t)tracer_want(p.ttiles) * 2 * (size_t)p.m_pad * 8;
 }
 
 // The tracers' Euler step of time step s (rec_row >= 0: also row rec_row of the call's record): enqueued where the probes
@@ -216,73 +165,24 @@ int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   const MarchSetup& m = c->msetup;
   const size_t M = c->tracer_count;
   const bool f32x2 = c->tracer_precision == 2;
-  const TracerPlan p = f32x2 ? tracer_plan_f32x2(M, n_ub + (long long)m.npan) : tracer_plan(M, n_ub + (long long)m.npan);
+  const ObserverPlan p = observer_plan(kObserverRules[f32x2 ? kObsTracersF32x2 : kObsTracers], (long long)M, n_ub + (long long)m.npan);
   const double* seed = static_cast<const double*>(c->tracer_seed.p);
   const long long* release = static_cast<const long long*>(c->tracer_release.p);
-  const double* shift = c->tracer_shifted ? static_cast<const double*>(c->tracer_shift.p) + s : nullptr;
+  const double* shift = step_shift(c->tracer_shift, c->tracer_shifted, s);
   double* cur = static_cast<double*>(c->tracer_cur.p);
   double* slab = static_cast<double*>(c->tracer_part.p);
   double* out = static_cast<double*>(c->tracer_out.p);
-  if (f32x2)
-    hipLaunchKernelGGL(march_f32x2_tracer_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M,
-                       release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.m_pad,
-                       (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
-                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
-  else
-    hipLaunchKernelGGL(march_tracer_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M, release,
-                       release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.m_pad,
-                       (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
-                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
+  hipLaunchKernelGGL(f32x2 ? march_f32x2_tracer_partial : march_tracer_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock),
+                     0, st, seed, seed + M, release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M,
+                     p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                     static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
   double* rec_x = rec_row >= 0 ? out + (size_t)rec_row * M : nullptr;
   double* rec_z = rec_row >= 0 ? out + (rec_rows + (size_t)rec_row) * M : nullptr;
-  hipLaunchKernelGGL(march_tracer_finish, dim3(blocks_for((long long)M)), dim3(kBlock), 0, st, (const double*)slab, p.m_pad, p.nsplit,
+  hipLaunchKernelGGL(march_tracer_finish, dim3(blocks_for((long long)M)), dim3(kBlock), 0, st, (const double*)slab, p.pad, p.nsplit,
                      seed, seed + M, release, shift, s, (long long)M, m.dt, cur, cur + M, rec_x, rec_z);
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
-}
-
-// Launch rule of the survey kernels: tracer_plan's form.  K points in tiles of kSurveyTile (256 lanes x kSurveyPerLane); the
-// sources -- at most ns_ub = n_ub + nfoil, n_ub the step's anchor-derived bound of the wake size after its solve -- in
-// `nsplit` splits of `chunk` sources, a multiple of the 256-source LDS tile, chosen so that tiles x splits comes to about 1024
-// workgroups, with at most 64 splits (the finisher adds them one after the other).  A function of K and n_ub alone: the
-// summation order of a step does not depend on where the calls of a run begin.
-struct SurveyPlan { long long ttiles, k_pad, chunk; int nsplit; };
-constexpr long long kSurveyGroups = 1024, kSurveyMaxSplit = 64;
-long long survey_want(long long ttiles) { return std::min(kSurveyMaxSplit, std::max<long long>(1, kSurveyGroups / ttiles)); }
-SurveyPlan survey_plan(size_t count, long long ns_ub) {
-  SurveyPlan p;
-  p.ttiles = ((long long)count + kSurveyTile - 1) / kSurveyTile;
-  p.k_pad = p.ttiles * kSurveyTile;
-  const long long want = survey_want(p.ttiles);
-  ns_ub = std::max<long long>(ns_ub, 1);
-  p.chunk = std::max<long long>(kSurveySrcTile, ((ns_ub + want - 1) / want + kSurveySrcTile - 1) / kSurveySrcTile * kSurveySrcTile);
-  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
-  return p;
-}
-// the slab of any step: nsplit <= survey_want(ttiles) whatever the wake size (at most 16 MiB)
-size_t survey_slab_bytes(size_t count) {
-  const SurveyPlan p = survey_plan(count, 1);
-  return (size_t)survey_want(p.ttiles) * 2 * (size_t)p.k_pad * 8;
-}
-
-// Launch rule of the fp32 survey kernel (march_f32_survey_partial): survey_plan's form and constants with its own point tile
-// (256 lanes x kSurveyF32PerLane).  `chunk` is a multiple of the 256-source tile, so every split starts on a tile -- and
-// origin-class -- boundary counted from slot 0.  A function of K and n_ub alone.
-SurveyPlan survey_plan_f32(size_t count, long long ns_ub) {
-  SurveyPlan p;
-  p.ttiles = ((long long)count + kSurveyF32Tile - 1) / kSurveyF32Tile;
-  p.k_pad = p.ttiles * kSurveyF32Tile;
-  const long long want = survey_want(p.ttiles);
-  ns_ub = std::max<long long>(ns_ub, 1);
-  p.chunk = std::max<long long>(kLocalTile, ((ns_ub + want - 1) / want + kLocalTile - 1) / kLocalTile * kLocalTile);
-  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
-  return p;
-}
-// the fp32 kernel's slab of any step (at most 16 MiB: want x k_pad <= 1024 tiles of 1024 points)
-size_t survey_slab_bytes_f32(size_t count) {
-  const SurveyPlan p = survey_plan_f32(count, 1);
-  return (size_t)survey_want(p.ttiles) * 2 * (size_t)p.k_pad * 8;
 }
 
 // is time step s one of the survey's sampled steps?
@@ -298,30 +198,63 @@ int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   const MarchSetup& m = c->msetup;
   const size_t K = c->survey_count;
   const bool f32 = c->survey_precision == 1;
-  const SurveyPlan p = f32 ? survey_plan_f32(K, n_ub + (long long)m.npan) : survey_plan(K, n_ub + (long long)m.npan);
+  const ObserverPlan p = observer_plan(kObserverRules[f32 ? kObsSurveyF32 : kObsSurvey], (long long)K, n_ub + (long long)m.npan);
   const double* pxz = static_cast<const double*>(c->survey_xz.p);
-  const double* shift = c->survey_shifted ? static_cast<const double*>(c->survey_shift.p) + s : nullptr;
+  const double* shift = step_shift(c->survey_shift, c->survey_shifted, s);
   double* slab = static_cast<double*>(c->survey_part.p);
+  // (the two precisions' argument lists differ: the fp32 kernel's guard is in units of v_core)
   if (f32)
-    hipLaunchKernelGGL(march_f32_survey_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
-                       (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+    hipLaunchKernelGGL(march_f32_survey_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
+                       (long long)K, p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
                        static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, c->march_vcore, slab);
   else
-    hipLaunchKernelGGL(march_survey_partial, dim3((unsigned)p.ttiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
-                       (long long)K, p.k_pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+    hipLaunchKernelGGL(march_survey_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
+                       (long long)K, p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
                        static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
   // a step with a bin: one finisher, as without bins, that also updates the bin's block (the host knows the step's bin)
   const int bin = c->survey_nbins ? c->survey_bin_of_row[(size_t)s] : -1;
   if (bin >= 0)
-    hipLaunchKernelGGL(march_binned_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad,
+    hipLaunchKernelGGL(march_binned_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.pad,
                        p.nsplit, (long long)K, static_cast<double*>(c->survey_sums.p),
                        static_cast<double*>(c->survey_bin_sums.p) + (size_t)bin * kSurveySums * K);
   else
-    hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.k_pad, p.nsplit,
+    hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.pad, p.nsplit,
                        (long long)K, static_cast<double*>(c->survey_sums.p));
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
+}
+
+// What the observers' setters share: `count` points (x, z) and, optionally, one x offset per kinematics row.  check_points
+// validates them (`points` / `offsets`: the observer's nouns for the messages) and changes nothing; upload_points stores
+// x | z in `xz` and the offsets in `shift`, enqueued on c->stream: the caller waits for the copies.
+int check_points(ludvm_ctx* c, const double* x, const double* z, size_t count, const double* shift_x, size_t shift_rows,
+                 const std::string& points, const std::string& offsets) {
+  if (count && (!x || !z)) return fail(c, LUDVM_E_ARG, "null array");
+  if (count && shift_x && shift_rows != c->march_kin_rows)
+    return fail(c, LUDVM_E_ARG, "march: " + offsets + " must be one per kinematics row");
+  for (size_t k = 0; k < count; ++k)
+    if (!std::isfinite(x[k]) || !std::isfinite(z[k])) return fail(c, LUDVM_E_ARG, "march: " + points + " must be finite");
+  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
+    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: " + offsets + " must be finite");
+  return LUDVM_OK;
+}
+
+int upload_points(ludvm_ctx* c, Buf& xz, Buf& shift, bool& shifted, const double* x, const double* z, size_t count,
+                  const double* shift_x, size_t shift_rows) {
+  CHK(ensure(c, xz, 2 * count * 8));
+  if (shift_x) CHK(ensure(c, shift, shift_rows * 8));
+  double* pxz = static_cast<double*>(xz.p);
+  HIPCHK(c, hipMemcpyAsync(pxz, x, count * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(pxz + count, z, count * 8, hipMemcpyHostToDevice, c->stream));
+  if (shift_x) HIPCHK(c, hipMemcpyAsync(shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+  shifted = shift_x != nullptr;
+  return LUDVM_OK;
+}
+
+// the largest slab either precision's kernel of an observer may write
+size_t slab_bytes(ObserverKind f64, ObserverKind f32, size_t count) {
+  return std::max(observer_slab_bytes(kObserverRules[f64], (long long)count), observer_slab_bytes(kObserverRules[f32], (long long)count));
 }
 
 }  // namespace
@@ -335,15 +268,9 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
   if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
     return fail(c, LUDVM_E_STATE, "march: the context is sharded; a survey runs on one device");
   if (count > LUDVM_MARCH_MAX_SURVEY) return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_SURVEY) + " survey points");
-  if (count && (!x || !z)) return fail(c, LUDVM_E_ARG, "null array");
-  if (count && shift_x && shift_rows != c->march_kin_rows)
-    return fail(c, LUDVM_E_ARG, "march: survey offsets must be one per kinematics row");
+  CHK(check_points(c, x, z, count, shift_x, shift_rows, "survey points", "survey offsets"));
   if (count && (first < 1 || every < 1)) return fail(c, LUDVM_E_ARG, "march: the survey window needs first >= 1 and every >= 1");
   if (count && sums && samples < 0) return fail(c, LUDVM_E_ARG, "march: survey samples must be >= 0");
-  for (size_t k = 0; k < count; ++k)
-    if (!std::isfinite(x[k]) || !std::isfinite(z[k])) return fail(c, LUDVM_E_ARG, "march: survey points must be finite");
-  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
-    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: survey offsets must be finite");
   for (size_t k = 0; count && sums && k < kSurveySums * count; ++k)
     if (!std::isfinite(sums[k])) return fail(c, LUDVM_E_ARG, "march: survey sums must be finite");
   c->survey_count = 0;
@@ -352,18 +279,12 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
   c->survey_nbins = 0;             // (and no bins until ludvm_march_set_survey_bins)
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  CHK(ensure(c, c->survey_xz, 2 * count * 8));
   CHK(ensure(c, c->survey_sums, kSurveySums * count * 8));
-  CHK(ensure(c, c->survey_part, std::max(survey_slab_bytes(count), survey_slab_bytes_f32(count))));   // either precision's
-  if (shift_x) CHK(ensure(c, c->survey_shift, shift_rows * 8));
-  double* pxz = static_cast<double*>(c->survey_xz.p);
-  HIPCHK(c, hipMemcpyAsync(pxz, x, count * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pxz + count, z, count * 8, hipMemcpyHostToDevice, c->stream));
+  CHK(ensure(c, c->survey_part, slab_bytes(kObsSurvey, kObsSurveyF32, count)));
+  CHK(upload_points(c, c->survey_xz, c->survey_shift, c->survey_shifted, x, z, count, shift_x, shift_rows));
   if (sums) HIPCHK(c, hipMemcpyAsync(c->survey_sums.p, sums, kSurveySums * count * 8, hipMemcpyHostToDevice, c->stream));
   else HIPCHK(c, hipMemsetAsync(c->survey_sums.p, 0, kSurveySums * count * 8, c->stream));
-  if (shift_x) HIPCHK(c, hipMemcpyAsync(c->survey_shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->survey_shifted = shift_x != nullptr;
   c->survey_first = first;
   c->survey_stop = std::min<long long>(stop, (long long)c->march_kin_rows);
   c->survey_every = every;
@@ -447,18 +368,13 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
   if (count > LUDVM_MARCH_MAX_TRACERS) return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_TRACERS) + " tracers");
-  if (count && (!seed_x || !seed_z)) return fail(c, LUDVM_E_ARG, "null array");
+  CHK(check_points(c, seed_x, seed_z, count, shift_x, shift_rows, "tracer seeds", "tracer offsets"));
   if (count && ((cur_x == nullptr) != (cur_z == nullptr))) return fail(c, LUDVM_E_ARG, "march: tracer positions need both cur_x and cur_z");
   if (count && nrecord && !record_steps) return fail(c, LUDVM_E_ARG, "null array");
-  if (count && shift_x && shift_rows != c->march_kin_rows)
-    return fail(c, LUDVM_E_ARG, "march: tracer offsets must be one per kinematics row");
   for (size_t k = 0; k < count; ++k) {
-    if (!std::isfinite(seed_x[k]) || !std::isfinite(seed_z[k])) return fail(c, LUDVM_E_ARG, "march: tracer seeds must be finite");
     if (cur_x && (!std::isfinite(cur_x[k]) || !std::isfinite(cur_z[k]))) return fail(c, LUDVM_E_ARG, "march: tracer positions must be finite");
     if (release && release[k] < 1) return fail(c, LUDVM_E_ARG, "march: tracer release steps must be >= 1");
   }
-  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
-    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: tracer offsets must be finite");
   for (size_t k = 0; count && k < nrecord; ++k)
     if (record_steps[k] < 1 || (size_t)record_steps[k] >= c->march_kin_rows || (k && record_steps[k] <= record_steps[k - 1]))
       return fail(c, LUDVM_E_ARG, "march: tracer record steps must be ascending and inside the kinematics table");
@@ -469,11 +385,11 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
   c->tracer_precision = 0;         // float64 until ludvm_march_set_tracer_precision says otherwise
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const TracerPlan p = tracer_plan(count, 1);
+  const long long ttiles = observer_tiles(kObserverRules[kObsTracers], (long long)count);
   // host images: release steps (NULL: all 1) with the earliest release of every tile behind them; the first positions
-  std::vector<long long> rel(count + (size_t)p.ttiles);
+  std::vector<long long> rel(count + (size_t)ttiles);
   for (size_t k = 0; k < count; ++k) rel[k] = release ? release[k] : 1;
-  for (long long t = 0; t < p.ttiles; ++t) {
+  for (long long t = 0; t < ttiles; ++t) {
     const size_t lo = (size_t)t * kTracerTile, hi = std::min(count, lo + (size_t)kTracerTile);
     rel[count + (size_t)t] = *std::min_element(rel.begin() + lo, rel.begin() + hi);
   }
@@ -482,19 +398,13 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
     cur[k] = cur_x ? cur_x[k] : seed_x[k] + (shift_x ? shift_x[0] : 0.0);
     cur[count + k] = cur_z ? cur_z[k] : seed_z[k];
   }
-  CHK(ensure(c, c->tracer_seed, 2 * count * 8));
   CHK(ensure(c, c->tracer_release, rel.size() * 8));
   CHK(ensure(c, c->tracer_cur, 2 * count * 8));
-  CHK(ensure(c, c->tracer_part, std::max(tracer_slab_bytes(count), tracer_slab_bytes_f32x2(count))));   // either precision's
-  if (shift_x) CHK(ensure(c, c->tracer_shift, shift_rows * 8));
-  double* seed = static_cast<double*>(c->tracer_seed.p);
-  HIPCHK(c, hipMemcpyAsync(seed, seed_x, count * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(seed + count, seed_z, count * 8, hipMemcpyHostToDevice, c->stream));
+  CHK(ensure(c, c->tracer_part, slab_bytes(kObsTracers, kObsTracersF32x2, count)));
+  CHK(upload_points(c, c->tracer_seed, c->tracer_shift, c->tracer_shifted, seed_x, seed_z, count, shift_x, shift_rows));
   HIPCHK(c, hipMemcpyAsync(c->tracer_release.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->tracer_cur.p, cur.data(), 2 * count * 8, hipMemcpyHostToDevice, c->stream));
-  if (shift_x) HIPCHK(c, hipMemcpyAsync(c->tracer_shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));     // (rel and cur live on this frame)
-  c->tracer_shifted = shift_x != nullptr;
   c->tracer_record.assign(record_steps, record_steps + nrecord);
   c->tracer_count = count;
   return LUDVM_OK;
@@ -545,26 +455,14 @@ int ludvm_march_set_probes(ludvm_ctx* c, const double* x, const double* z, size_
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
   if (count > LUDVM_MARCH_MAX_PROBES) return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_PROBES) + " probes");
-  if (count && (!x || !z)) return fail(c, LUDVM_E_ARG, "null array");
-  if (count && shift_x && shift_rows != c->march_kin_rows)
-    return fail(c, LUDVM_E_ARG, "march: probe offsets must be one per kinematics row");
-  for (size_t k = 0; k < count; ++k)
-    if (!std::isfinite(x[k]) || !std::isfinite(z[k])) return fail(c, LUDVM_E_ARG, "march: probe positions must be finite");
-  for (size_t k = 0; count && shift_x && k < shift_rows; ++k)
-    if (!std::isfinite(shift_x[k])) return fail(c, LUDVM_E_ARG, "march: probe offsets must be finite");
+  CHK(check_points(c, x, z, count, shift_x, shift_rows, "probe positions", "probe offsets"));
   c->probe_count = 0;
   c->probe_rows = 0;
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  CHK(ensure(c, c->probe_xz, 2 * count * 8));
-  CHK(ensure(c, c->probe_part, probe_slab_bytes(count)));
-  if (shift_x) CHK(ensure(c, c->probe_shift, shift_rows * 8));
-  double* pxz = static_cast<double*>(c->probe_xz.p);
-  HIPCHK(c, hipMemcpyAsync(pxz, x, count * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(pxz + count, z, count * 8, hipMemcpyHostToDevice, c->stream));
-  if (shift_x) HIPCHK(c, hipMemcpyAsync(c->probe_shift.p, shift_x, shift_rows * 8, hipMemcpyHostToDevice, c->stream));
+  CHK(ensure(c, c->probe_part, observer_slab_bytes(kObserverRules[kObsProbes], (long long)count)));
+  CHK(upload_points(c, c->probe_xz, c->probe_shift, c->probe_shifted, x, z, count, shift_x, shift_rows));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->probe_shifted = shift_x != nullptr;
   c->probe_count = count;
   return LUDVM_OK;
 }

@@ -494,37 +494,95 @@ march_finish_sym(long long* acc_u, long long* acc_w, const SymScale* sc, MarchSt
 //                      the device; (split, probe) partial sums go to a slab [split][2][p_pad]
 // march_probe_finish   one wavefront per output column (component x probe): splits lane, lane + 64, ... then the fixed
 //                      shuffle tree of march_chord_finish; writes the step's row of the call's probe buffer
-// The splits are a function of the probe count and of the step's anchor-derived bound alone (probe_plan, march.hip), and
-// every partial sum is formed by one lane in source order: the bits do not depend on how a run is cut into calls.
+// The splits are a function of the probe count and of the step's anchor-derived bound alone (observer_plan, plan_rule.hpp),
+// and every partial sum is formed by one lane in source order: the bits do not depend on how a run is cut into calls.
+//
+// ---- what every marched observer is made of ------------------------------------------------------------------------------------
+// A partial kernel (probes, tracers, survey; float64, fp32 on local origins, hi+lo fp32) is a point loader, one field body
+// and observer_store; grid = point tiles x source splits, the slab [split][2][pad] is the observer's own.  A workgroup of
+// LANES lanes owns LANES x PPL points: point  blockIdx.x * LANES * PPL + k * LANES + lane  in register set k of the lane.
+// A body (field_f64, local_field_f32, hilo_field_f32) takes the lane's PPL points (xp, zp: float64) against the sources
+// [s_begin, s_end) -> au += sum G dz / sqrt(r^4 + vc^4), aw += sum G dx / sqrt(..) (no 1 / 2 pi, no sign); every lane of the
+// workgroup calls it (barriers inside).  One lane forms a partial sum in source order, then tile order.
 constexpr int kProbeLanes = 64;
-constexpr int kProbeTile = 256;
+constexpr int kFieldTile = 256;                    // sources per LDS tile of field_f64
 
-__global__ void __launch_bounds__(kProbeLanes)
-march_probe_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, int count, long long p_pad,
-                    const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
-                    const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
-  __shared__ __attribute__((aligned(16))) double lx[kProbeTile];
-  __shared__ __attribute__((aligned(16))) double lz[kProbeTile];
-  __shared__ __attribute__((aligned(16))) double lg[kProbeTile];
-  // like the solve chain, these waves run beside a roll-up kernel that keeps every SIMD's issue slots busy
-  __builtin_amdgcn_s_setprio(3);
-  const int lane = threadIdx.x;
-  const long long p = (long long)blockIdx.x * kProbeLanes + lane;
+template <int PPL, int LANES>
+__device__ __forceinline__ long long observer_point(int k) {
+  return ((long long)blockIdx.x * (LANES * PPL) + threadIdx.x) + (long long)k * LANES;
+}
+
+// the sources of split blockIdx.y: [s_begin, s_end) of the step's [0, S->n + nfoil), the count read on the device
+struct SplitRange { long long begin, end; };
+__device__ __forceinline__ SplitRange split_range(const MarchState* S, int nfoil, long long chunk) {
   const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
   const long long s_begin = (long long)blockIdx.y * chunk;
   long long s_end = s_begin + chunk;
   if (s_end > ns) s_end = ns;
-  double xp = 0.0, zp = 0.0;
-  if (p < count) {
-    xp = px[p] + (shift ? *shift : 0.0);
-    zp = pz[p];
+  return {s_begin, s_end};
+}
+
+// points that stay where they are: (px[m] + the step's shift, pz[m]) and zero sums; a lane without a point walks along at
+// `absent`
+template <int PPL, int LANES>
+__device__ __forceinline__ void load_fixed_points(const double* __restrict__ px, const double* __restrict__ pz, const double* shift,
+                                                  long long count, double absent, double (&xp)[PPL], double (&zp)[PPL],
+                                                  double (&au)[PPL], double (&aw)[PPL]) {
+  const double sh = shift ? *shift : 0.0;
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long m = observer_point<PPL, LANES>(k);
+    const bool on = m < count;
+    xp[k] = on ? px[m] + sh : absent;
+    zp[k] = on ? pz[m] : absent;
+    au[k] = 0.0; aw[k] = 0.0;
   }
-  double au = 0.0, aw = 0.0;
-  for (long long base = s_begin; base < s_end; base += kProbeTile) {
+}
+
+// the lane's rows of split blockIdx.y's slab, for the points that on(k, m) says it has (a split past the end of the sources
+// leaves exact zeros: the finisher sums every split of the launch)
+template <int PPL, int LANES, class On>
+__device__ __forceinline__ void observer_store(double* slab, long long pad, On on, const double (&au)[PPL], const double (&aw)[PPL]) {
+  double* row = slab + (long long)blockIdx.y * 2 * pad;
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long m = observer_point<PPL, LANES>(k);
+    if (on(k, m)) {
+      row[m] = au[k] * kInv2PiD;
+      row[pad + m] = -aw[k] * kInv2PiD;
+    }
+  }
+}
+
+// the float64 pair update (pair_f64's arithmetic)
+__device__ __forceinline__ void pair_acc_f64(double xp, double zp, double sx, double sz, double sg, double vc4, double& au,
+                                             double& aw) {
+  const double dx = xp - sx;
+  const double dz = zp - sz;
+  const double r2 = __builtin_fma(dz, dz, dx * dx);
+  const double q = __builtin_fma(r2, r2, vc4);
+  const double s = sg * rsqrt_f64(q);
+  au = __builtin_fma(dz, s, au);
+  aw = __builtin_fma(dx, s, aw);
+}
+
+// The float64 body: kFieldTile-source tiles staged in three LDS planes (kFieldTile / LANES slots per lane; slots past the
+// end are pair_f64's padding: kPadPosD, G = 0), every lane walks a tile in source order and every broadcast read of a
+// source serves its PPL pairs.  UNROLL: sources per trip of the walk.
+template <int PPL, int LANES, int UNROLL>
+__device__ __forceinline__ void field_f64(const double (&xp)[PPL], const double (&zp)[PPL], const double* __restrict__ xs,
+                                          const double* __restrict__ zs, const double* __restrict__ gs, long long s_begin,
+                                          long long s_end, double vc4, double (&au)[PPL], double (&aw)[PPL]) {
+  static_assert(kFieldTile % LANES == 0, "whole source slots per lane");
+  __shared__ __attribute__((aligned(16))) double lx[kFieldTile];
+  __shared__ __attribute__((aligned(16))) double lz[kFieldTile];
+  __shared__ __attribute__((aligned(16))) double lg[kFieldTile];
+  const int tid = threadIdx.x;
+  for (long long base = s_begin; base < s_end; base += kFieldTile) {
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < kProbeTile / kProbeLanes; ++k) {
-      const int l = lane + k * kProbeLanes;
+    for (int k = 0; k < kFieldTile / LANES; ++k) {
+      const int l = tid + k * LANES;
       const long long si = base + l;
       const bool ok = si < s_end;
       lx[l] = ok ? xs[si] : kPadPosD;
@@ -532,23 +590,26 @@ march_probe_partial(const double* __restrict__ px, const double* __restrict__ pz
       lg[l] = ok ? gs[si] : 0.0;
     }
     __syncthreads();
-#pragma unroll 4
-    for (int j = 0; j < kProbeTile; ++j) {
-      const double dx = xp - lx[j];
-      const double dz = zp - lz[j];
-      const double r2 = __builtin_fma(dz, dz, dx * dx);
-      const double q = __builtin_fma(r2, r2, vc4);
-      const double s = lg[j] * rsqrt_f64(q);
-      au = __builtin_fma(dz, s, au);
-      aw = __builtin_fma(dx, s, aw);
+#pragma unroll UNROLL
+    for (int j = 0; j < kFieldTile; ++j) {
+      const double sx = lx[j], sz = lz[j], sg = lg[j];
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) pair_acc_f64(xp[k], zp[k], sx, sz, sg, vc4, au[k], aw[k]);
     }
   }
-  if (p < count) {
-    // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
-    double* row = slab + (long long)blockIdx.y * 2 * p_pad;
-    row[p] = au * kInv2PiD;
-    row[p_pad + p] = -aw * kInv2PiD;
-  }
+}
+
+__global__ void __launch_bounds__(kProbeLanes)
+march_probe_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, int count, long long p_pad,
+                    const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
+                    const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
+  // like the solve chain, these waves run beside a roll-up kernel that keeps every SIMD's issue slots busy
+  __builtin_amdgcn_s_setprio(3);
+  const SplitRange src = split_range(S, nfoil, chunk);
+  double xp[1], zp[1], au[1], aw[1];
+  load_fixed_points<1, kProbeLanes>(px, pz, shift, count, 0.0, xp, zp, au, aw);
+  field_f64<1, kProbeLanes, 4>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw);
+  observer_store<1, kProbeLanes>(slab, p_pad, [=](int, long long m) { return m < count; }, au, aw);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -579,18 +640,17 @@ march_probe_finish(const double* slab, long long p_pad, int nsplit, int count, d
 //
 // march_tracer_partial  grid = tracer tiles (kTracerTile = 256 lanes x kTracerPerLane tracers: tracer t0 + k * 256 + lane in
 //                       register set k of the lane) x source splits; 256-source tiles staged in LDS, every broadcast read of a
-//                       source serves kTracerPerLane pairs; pair_f64's arithmetic; the source count is read on the device;
+//                       source serves kTracerPerLane pairs (field_f64); the source count is read on the device;
 //                       (split, tracer) partial sums to a slab [split][2][m_pad] of the tracers' own.  A tile whose earliest
 //                       release (tile_min, precomputed by the host) is after step i leaves at once; a held lane of a mixed
 //                       tile walks along at the pad position and stores nothing
 // march_tracer_finish   one lane per tracer: splits 0, 1, 2, ... in that order, `start` by the rule above, the new position
 //                       into the resident cur_x / cur_z (held: seed + shift[i]) and -- rec_x given -- into the call's row
-// The splits are a function of the tracer count and of the step's anchor-derived bound alone (tracer_plan, march.hip), every
-// partial sum is formed by one lane in source order and the splits are combined in split order: a trajectory repeats bit
-// for bit however a run is cut into calls.  Both kernels write the tracers' buffers only.
+// The splits are a function of the tracer count and of the step's anchor-derived bound alone (observer_plan, plan_rule.hpp),
+// every partial sum is formed by one lane in source order and the splits are combined in split order: a trajectory repeats
+// bit for bit however a run is cut into calls.  Both kernels write the tracers' buffers only.
 constexpr int kTracerPerLane = 2;
 constexpr int kTracerTile = kBlock * kTracerPerLane;
-constexpr int kTracerSrcTile = 256;
 
 __device__ __forceinline__ void tracer_start(const double* __restrict__ seed_x, const double* __restrict__ seed_z,
                                              const double* cur_x, const double* cur_z, long long m, long long rel, long long step,
@@ -604,71 +664,65 @@ __device__ __forceinline__ void tracer_start(const double* __restrict__ seed_x, 
   }
 }
 
+// is every tracer of the workgroup's SUB tiles of kTracerTile still held?  (`tile_min`: one entry per kTracerTile tracers)
+template <int SUB>
+__device__ __forceinline__ bool tiles_held(const long long* __restrict__ tile_min, long long step, long long count) {
+  const long long nsub = (count + kTracerTile - 1) / kTracerTile;
+  bool held = true;
+#pragma unroll
+  for (int q = 0; q < SUB; ++q) {
+    const long long e = (long long)blockIdx.x * SUB + q;
+    if (e < nsub && tile_min[e] <= step) held = false;
+  }
+  return held;
+}
+
+// the lane's tracers of step `step`: free_[k], the start of a released one and zero sums; a held lane (or one without a tracer) of a
+// mixed tile walks along at `absent` and stores nothing
+template <int PPL>
+__device__ __forceinline__ void load_tracers(const double* __restrict__ seed_x, const double* __restrict__ seed_z,
+                                             const long long* __restrict__ release, const double* cur_x, const double* cur_z,
+                                             const double* shift, long long step, long long count, double absent,
+                                             double (&xp)[PPL], double (&zp)[PPL], double (&au)[PPL], double (&aw)[PPL],
+                                             bool (&free_)[PPL]) {
+  const double sh = shift ? *shift : 0.0;
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long m = observer_point<PPL, kBlock>(k);
+    xp[k] = absent; zp[k] = absent; au[k] = 0.0; aw[k] = 0.0;
+    bool free = false;
+    if (m < count) {
+      const long long rel = release[m];
+      free = rel <= step;
+      if (free) tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, xp[k], zp[k]);
+    }
+    free_[k] = free;
+  }
+}
+
+// (u, w) of point m: its column of the slab, splits 0, 1, 2, ... in that order
+__device__ __forceinline__ void split_sums(const double* slab, long long pad, int nsplit, long long m, double& u, double& w) {
+  u = 0.0; w = 0.0;
+  const double* c0 = slab + m;
+  for (int sidx = 0; sidx < nsplit; ++sidx) {
+    u += c0[(long long)sidx * 2 * pad];
+    w += c0[(long long)sidx * 2 * pad + pad];
+  }
+}
+
 __global__ void __launch_bounds__(kBlock)
 march_tracer_partial(const double* __restrict__ seed_x, const double* __restrict__ seed_z, const long long* __restrict__ release,
                      const long long* __restrict__ tile_min, const double* cur_x, const double* cur_z, const double* shift,
                      long long step, long long count, long long m_pad, const double* __restrict__ xs, const double* __restrict__ zs,
                      const double* __restrict__ gs, const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
-  __shared__ __attribute__((aligned(16))) double lx[kTracerSrcTile];
-  __shared__ __attribute__((aligned(16))) double lz[kTracerSrcTile];
-  __shared__ __attribute__((aligned(16))) double lg[kTracerSrcTile];
-  if (tile_min[blockIdx.x] > step) return;         // every tracer of the tile is still held (uniform: before any barrier)
+  if (tiles_held<1>(tile_min, step, count)) return;         // (uniform: before any barrier)
   __builtin_amdgcn_s_setprio(3);
-  const int tid = threadIdx.x;
-  const long long t0 = (long long)blockIdx.x * kTracerTile + tid;
-  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
-  const long long s_begin = (long long)blockIdx.y * chunk;
-  long long s_end = s_begin + chunk;
-  if (s_end > ns) s_end = ns;
-  const double sh = shift ? *shift : 0.0;
+  const SplitRange src = split_range(S, nfoil, chunk);
   double xp[kTracerPerLane], zp[kTracerPerLane], au[kTracerPerLane], aw[kTracerPerLane];
   bool free_[kTracerPerLane];
-#pragma unroll
-  for (int k = 0; k < kTracerPerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    xp[k] = kPadPosD; zp[k] = kPadPosD; au[k] = 0.0; aw[k] = 0.0;
-    free_[k] = false;
-    if (m < count) {
-      const long long rel = release[m];
-      free_[k] = rel <= step;
-      if (free_[k]) tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, xp[k], zp[k]);
-    }
-  }
-  for (long long base = s_begin; base < s_end; base += kTracerSrcTile) {
-    __syncthreads();
-    {
-      const long long si = base + tid;
-      const bool ok = si < s_end;
-      lx[tid] = ok ? xs[si] : kPadPosD;
-      lz[tid] = ok ? zs[si] : kPadPosD;
-      lg[tid] = ok ? gs[si] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int j = 0; j < kTracerSrcTile; ++j) {
-      const double sx = lx[j], sz = lz[j], sg = lg[j];
-#pragma unroll
-      for (int k = 0; k < kTracerPerLane; ++k) {
-        const double dx = xp[k] - sx;
-        const double dz = zp[k] - sz;
-        const double r2 = __builtin_fma(dz, dz, dx * dx);
-        const double q = __builtin_fma(r2, r2, vc4);
-        const double s = sg * rsqrt_f64(q);
-        au[k] = __builtin_fma(dz, s, au[k]);
-        aw[k] = __builtin_fma(dx, s, aw[k]);
-      }
-    }
-  }
-  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
-  double* row = slab + (long long)blockIdx.y * 2 * m_pad;
-#pragma unroll
-  for (int k = 0; k < kTracerPerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    if (free_[k]) {
-      row[m] = au[k] * kInv2PiD;
-      row[m_pad + m] = -aw[k] * kInv2PiD;
-    }
-  }
+  load_tracers<kTracerPerLane>(seed_x, seed_z, release, cur_x, cur_z, shift, step, count, kPadPosD, xp, zp, au, aw, free_);
+  field_f64<kTracerPerLane, kBlock, 2>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw);
+  observer_store<kTracerPerLane, kBlock>(slab, m_pad, [&](int k, long long) { return free_[k]; }, au, aw);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -686,12 +740,8 @@ march_tracer_finish(const double* slab, long long m_pad, int nsplit, const doubl
     z = seed_z[m];
   } else {
     tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, x, z);
-    double u = 0.0, w = 0.0;
-    const double* c0 = slab + m;
-    for (int sidx = 0; sidx < nsplit; ++sidx) {
-      u += c0[(long long)sidx * 2 * m_pad];
-      w += c0[(long long)sidx * 2 * m_pad + m_pad];
-    }
+    double u, w;
+    split_sums(slab, m_pad, nsplit, m, u, w);
     x = __builtin_fma(dt, u, x);
     z = __builtin_fma(dt, w, z);
   }
@@ -712,79 +762,29 @@ march_tracer_finish(const double* slab, long long m_pad, int nsplit, const doubl
 //
 // march_survey_partial  grid = point tiles (kSurveyTile = 256 lanes x kSurveyPerLane points: point t0 + k * 256 + lane in
 //                       register set k of the lane) x source splits; 256-source tiles staged in LDS, every broadcast read of a
-//                       source serves kSurveyPerLane pairs; pair_f64's arithmetic; the source count is read on the device;
+//                       source serves kSurveyPerLane pairs (field_f64); the source count is read on the device;
 //                       (split, point) partial sums to a slab [split][2][k_pad] of the survey's own
 // march_survey_finish   one lane per point: splits 0, 1, 2, ... in that order give (u, w), then sums[0..4][k] += with plain
 //                       loads and stores (the lane is the only writer of its point; steps follow each other in stream order)
 // march_binned_survey_finish  march_survey_finish for a sampled step that has a bin (ludvm_march_set_survey_bins), launched in its
 //                       place: the same (u, w) and the same update of sums, then the same five terms into the bin's own block
-// The splits are a function of the point count and of the step's anchor-derived bound alone (survey_plan, march.hip), every
-// partial sum is formed by one lane in source order, the splits are combined in split order and the steps in step order: the
-// sums repeat bit for bit however a run is cut into calls.  Both kernels write the survey's buffers only.
+// The splits are a function of the point count and of the step's anchor-derived bound alone (observer_plan, plan_rule.hpp),
+// every partial sum is formed by one lane in source order, the splits are combined in split order and the steps in step
+// order: the sums repeat bit for bit however a run is cut into calls.  Both kernels write the survey's buffers only.
 constexpr int kSurveyPerLane = 2;
 constexpr int kSurveyTile = kBlock * kSurveyPerLane;
-constexpr int kSurveySrcTile = 256;
 constexpr int kSurveySums = 5;
 
 __global__ void __launch_bounds__(kBlock)
 march_survey_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, long long count,
                      long long k_pad, const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
                      const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
-  __shared__ __attribute__((aligned(16))) double lx[kSurveySrcTile];
-  __shared__ __attribute__((aligned(16))) double lz[kSurveySrcTile];
-  __shared__ __attribute__((aligned(16))) double lg[kSurveySrcTile];
   __builtin_amdgcn_s_setprio(3);
-  const int tid = threadIdx.x;
-  const long long t0 = (long long)blockIdx.x * kSurveyTile + tid;
-  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
-  const long long s_begin = (long long)blockIdx.y * chunk;
-  long long s_end = s_begin + chunk;
-  if (s_end > ns) s_end = ns;
-  const double sh = shift ? *shift : 0.0;
+  const SplitRange src = split_range(S, nfoil, chunk);
   double xp[kSurveyPerLane], zp[kSurveyPerLane], au[kSurveyPerLane], aw[kSurveyPerLane];
-#pragma unroll
-  for (int k = 0; k < kSurveyPerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    const bool on = m < count;
-    xp[k] = on ? px[m] + sh : kPadPosD;
-    zp[k] = on ? pz[m] : kPadPosD;
-    au[k] = 0.0; aw[k] = 0.0;
-  }
-  for (long long base = s_begin; base < s_end; base += kSurveySrcTile) {
-    __syncthreads();
-    {
-      const long long si = base + tid;
-      const bool ok = si < s_end;
-      lx[tid] = ok ? xs[si] : kPadPosD;
-      lz[tid] = ok ? zs[si] : kPadPosD;
-      lg[tid] = ok ? gs[si] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int j = 0; j < kSurveySrcTile; ++j) {
-      const double sx = lx[j], sz = lz[j], sg = lg[j];
-#pragma unroll
-      for (int k = 0; k < kSurveyPerLane; ++k) {
-        const double dx = xp[k] - sx;
-        const double dz = zp[k] - sz;
-        const double r2 = __builtin_fma(dz, dz, dx * dx);
-        const double q = __builtin_fma(r2, r2, vc4);
-        const double s = sg * rsqrt_f64(q);
-        au[k] = __builtin_fma(dz, s, au[k]);
-        aw[k] = __builtin_fma(dx, s, aw[k]);
-      }
-    }
-  }
-  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
-  double* row = slab + (long long)blockIdx.y * 2 * k_pad;
-#pragma unroll
-  for (int k = 0; k < kSurveyPerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    if (m < count) {
-      row[m] = au[k] * kInv2PiD;
-      row[k_pad + m] = -aw[k] * kInv2PiD;
-    }
-  }
+  load_fixed_points<kSurveyPerLane, kBlock>(px, pz, shift, count, kPadPosD, xp, zp, au, aw);
+  field_f64<kSurveyPerLane, kBlock, 2>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw);
+  observer_store<kSurveyPerLane, kBlock>(slab, k_pad, [=](int, long long m) { return m < count; }, au, aw);
 }
 
 // ---- the survey's field in fp32 on local origins (ludvm_march_set_survey_precision) ------------------------------------------------
@@ -802,10 +802,10 @@ march_survey_partial(const double* __restrict__ px, const double* __restrict__ p
 //            then class 0 and class 1, in that order, added to the lane's float64 (u, w)
 //   guard    while staging, the workgroup reduces each class's extent, max over its members of max(|x offset|, |z offset|); a
 //            class whose extent exceeds kSurveyF32MaxExtent x v_core is struck from the fp32 tile (padding) and evaluated by
-//            march_survey_partial's float64 loop on the float64 values instead -- a sparse set has no neighbours within a few
+//            pair_acc_f64 on the float64 values instead -- a sparse set has no neighbours within a few
 //            cores whose differences need the precision, but an fp32 offset of that size no longer resolves the core
 //            (DESIGN section 3's calibration).  The branch is uniform over the workgroup
-// One lane forms every partial sum in tile order, the class sums in class order: with survey_plan_f32 (march.hip) a function of
+// One lane forms every partial sum in tile order, the class sums in class order: with the plan (observer_plan) a function of
 // K and the step's bound alone, the sums repeat bit for bit however a run is cut into calls.
 // local_field_f32 is the body: PPL points of the lane (xd, zd: float64; a lane without a point passes -kPadPosF, away
 // from the sources' padding) against the
@@ -897,15 +897,7 @@ __device__ __forceinline__ void local_field_f32(const double (&xd)[PPL], const d
         for (int j = p; j < kLocalTile; j += 2) {
           const double sx = mx[j], sz = mz[j], sg = mg[j];
 #pragma unroll
-          for (int k = 0; k < PPL; ++k) {
-            const double dx = xd[k] - sx;
-            const double dz = zd[k] - sz;
-            const double r2 = __builtin_fma(dz, dz, dx * dx);
-            const double q = __builtin_fma(r2, r2, vc4);
-            const double s = sg * rsqrt_f64(q);
-            cu[k] = __builtin_fma(dz, s, cu[k]);
-            cw[k] = __builtin_fma(dx, s, cw[k]);
-          }
+          for (int k = 0; k < PPL; ++k) pair_acc_f64(xd[k], zd[k], sx, sz, sg, vc4, cu[k], cw[k]);
         }
 #pragma unroll
         for (int k = 0; k < PPL; ++k) { au[k] += cu[k]; aw[k] += cw[k]; }
@@ -923,32 +915,20 @@ march_f32_survey_partial(const double* __restrict__ px, const double* __restrict
                          const double* __restrict__ gs, const MarchState* S, int nfoil, long long chunk, double vc4, double v_core,
                          double* slab) {
   __builtin_amdgcn_s_setprio(3);
-  const long long t0 = (long long)blockIdx.x * kSurveyF32Tile + threadIdx.x;
-  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
-  const long long s_begin = (long long)blockIdx.y * chunk;
-  long long s_end = s_begin + chunk;
-  if (s_end > ns) s_end = ns;
-  const double sh = shift ? *shift : 0.0;
+  const SplitRange src = split_range(S, nfoil, chunk);
   double xp[kSurveyF32PerLane], zp[kSurveyF32PerLane], au[kSurveyF32PerLane], aw[kSurveyF32PerLane];
-#pragma unroll
-  for (int k = 0; k < kSurveyF32PerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    const bool on = m < count;
-    xp[k] = on ? px[m] + sh : -(double)kPadPosF;
-    zp[k] = on ? pz[m] : -(double)kPadPosF;
-    au[k] = 0.0; aw[k] = 0.0;
-  }
-  local_field_f32<kSurveyF32PerLane>(xp, zp, xs, zs, gs, s_begin, s_end, vc4, (float)(kSurveyF32MaxExtent * v_core), au, aw);
-  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
-  double* row = slab + (long long)blockIdx.y * 2 * k_pad;
-#pragma unroll
-  for (int k = 0; k < kSurveyF32PerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    if (m < count) {
-      row[m] = au[k] * kInv2PiD;
-      row[k_pad + m] = -aw[k] * kInv2PiD;
-    }
-  }
+  load_fixed_points<kSurveyF32PerLane, kBlock>(px, pz, shift, count, -(double)kPadPosF, xp, zp, au, aw);
+  local_field_f32<kSurveyF32PerLane>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, (float)(kSurveyF32MaxExtent * v_core), au, aw);
+  observer_store<kSurveyF32PerLane, kBlock>(slab, k_pad, [=](int, long long m) { return m < count; }, au, aw);
+}
+
+// one sample (u, w) of a point into its five raw sums s[0..4][count] (s: at the point's column), with plain loads and stores
+__device__ __forceinline__ void survey_add(double* s, long long count, double u, double w) {
+  s[0] += u;
+  s[count] += w;
+  s[2 * count] = __builtin_fma(u, u, s[2 * count]);
+  s[3 * count] = __builtin_fma(w, w, s[3 * count]);
+  s[4 * count] = __builtin_fma(u, w, s[4 * count]);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -956,24 +936,15 @@ march_survey_finish(const double* slab, long long k_pad, int nsplit, long long c
   __builtin_amdgcn_s_setprio(3);
   const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (m >= count) return;
-  double u = 0.0, w = 0.0;
-  const double* c0 = slab + m;
-  for (int sidx = 0; sidx < nsplit; ++sidx) {
-    u += c0[(long long)sidx * 2 * k_pad];
-    w += c0[(long long)sidx * 2 * k_pad + k_pad];
-  }
-  double* s = sums + m;
-  s[0] += u;
-  s[count] += w;
-  s[2 * count] = __builtin_fma(u, u, s[2 * count]);
-  s[3 * count] = __builtin_fma(w, w, s[3 * count]);
-  s[4 * count] = __builtin_fma(u, w, s[4 * count]);
+  double u, w;
+  split_sums(slab, k_pad, nsplit, m, u, w);
+  survey_add(sums + m, count, u, w);
 }
 
 // The finisher of a sampled step that has a bin (ludvm_march_set_survey_bins), launched INSTEAD of march_survey_finish: the
-// slab is read once, `sums` is updated with march_survey_finish's very expressions in its order (the plain sums cannot change a
-// bit), then the bin's own block bin_sums[5][count] -- the host knows the step's bin and passes the block -- with the same
-// five terms in the same way: a bin's block is, bit for bit, the plain sums of a survey that samples that bin's steps alone.
+// slab is read once, `sums` is updated as march_survey_finish does (the plain sums cannot change a bit), then the bin's own
+// block bin_sums[5][count] -- the host knows the step's bin and passes the block -- with the same five terms in the same
+// way: a bin's block is, bit for bit, the plain sums of a survey that samples that bin's steps alone.
 // One lane per point, loads and stores at stride `count` (coalesced), no LDS; serves both survey precisions, which differ
 // only in the partial kernel.  Writes the survey's buffers only.
 __global__ void __launch_bounds__(kBlock)
@@ -981,24 +952,10 @@ march_binned_survey_finish(const double* slab, long long k_pad, int nsplit, long
   __builtin_amdgcn_s_setprio(3);
   const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (m >= count) return;
-  double u = 0.0, w = 0.0;
-  const double* c0 = slab + m;
-  for (int sidx = 0; sidx < nsplit; ++sidx) {
-    u += c0[(long long)sidx * 2 * k_pad];
-    w += c0[(long long)sidx * 2 * k_pad + k_pad];
-  }
-  double* s = sums + m;
-  s[0] += u;
-  s[count] += w;
-  s[2 * count] = __builtin_fma(u, u, s[2 * count]);
-  s[3 * count] = __builtin_fma(w, w, s[3 * count]);
-  s[4 * count] = __builtin_fma(u, w, s[4 * count]);
-  double* b = bin_sums + m;
-  b[0] += u;
-  b[count] += w;
-  b[2 * count] = __builtin_fma(u, u, b[2 * count]);
-  b[3 * count] = __builtin_fma(w, w, b[3 * count]);
-  b[4 * count] = __builtin_fma(u, w, b[4 * count]);
+  double u, w;
+  split_sums(slab, k_pad, nsplit, m, u, w);
+  survey_add(sums + m, count, u, w);
+  survey_add(bin_sums + m, count, u, w);
 }
 
 // ---- the tracers' field in hi+lo fp32 (ludvm_march_set_tracer_precision) ---------------------------------------------------------
@@ -1014,7 +971,7 @@ march_binned_survey_finish(const double* slab, long long k_pad, int nsplit, long
 //            + 2 v_rsq_f32 per two pairs and point; the sources come by broadcast ds_read_b128
 //   sums     two levels: a tile's contributions in fp32 packed registers (even sources in the low halves, odd ones in the high
 //            halves), then low half and high half, in that order, added to the lane's float64 (u, w)
-// One lane forms every partial sum in source order and the tiles in tile order: with tracer_plan_f32x2 (march.hip) a function of
+// One lane forms every partial sum in source order and the tiles in tile order: with the plan (observer_plan) a function of
 // M and the step's bound alone, a trajectory repeats bit for bit however a run is cut into calls.
 // hilo_field_f32 is the body: PPL points of the lane (xd, zd: float64; a lane without a point passes -kPadPosF, away from the
 // sources' padding) against the sources [s_begin, s_end) -> au += sum G dz / sqrt(r^4 + vc^4), aw += sum G dx / sqrt(..) (no
@@ -1098,49 +1055,14 @@ march_f32x2_tracer_partial(const double* __restrict__ seed_x, const double* __re
                            const double* __restrict__ zs, const double* __restrict__ gs, const MarchState* S, int nfoil,
                            long long chunk, double vc4, double* slab) {
   static_assert(kTracerF32Tile % kTracerTile == 0, "whole tile_min entries per workgroup");
-  constexpr int kSub = kTracerF32Tile / kTracerTile;
-  {
-    // every tracer of the tile is still held: leave (uniform: before any barrier)
-    const long long nsub = (count + kTracerTile - 1) / kTracerTile;
-    bool held = true;
-#pragma unroll
-    for (int q = 0; q < kSub; ++q) {
-      const long long e = (long long)blockIdx.x * kSub + q;
-      if (e < nsub && tile_min[e] <= step) held = false;
-    }
-    if (held) return;
-  }
+  if (tiles_held<kTracerF32Tile / kTracerTile>(tile_min, step, count)) return;      // (uniform: before any barrier)
   __builtin_amdgcn_s_setprio(3);
-  const long long t0 = (long long)blockIdx.x * kTracerF32Tile + threadIdx.x;
-  const long long ns = S->n + nfoil;               // old wake + shed vortices + staged bound vortices
-  const long long s_begin = (long long)blockIdx.y * chunk;
-  long long s_end = s_begin + chunk;
-  if (s_end > ns) s_end = ns;
-  const double sh = shift ? *shift : 0.0;
+  const SplitRange src = split_range(S, nfoil, chunk);
   double xp[kTracerF32PerLane], zp[kTracerF32PerLane], au[kTracerF32PerLane], aw[kTracerF32PerLane];
   bool free_[kTracerF32PerLane];
-#pragma unroll
-  for (int k = 0; k < kTracerF32PerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    xp[k] = -(double)kPadPosF; zp[k] = -(double)kPadPosF; au[k] = 0.0; aw[k] = 0.0;
-    free_[k] = false;
-    if (m < count) {
-      const long long rel = release[m];
-      free_[k] = rel <= step;
-      if (free_[k]) tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, xp[k], zp[k]);
-    }
-  }
-  hilo_field_f32<kTracerF32PerLane>(xp, zp, xs, zs, gs, s_begin, s_end, vc4, au, aw);
-  // (a split past the end of the sources leaves exact zeros: the finisher sums every split of the launch)
-  double* row = slab + (long long)blockIdx.y * 2 * m_pad;
-#pragma unroll
-  for (int k = 0; k < kTracerF32PerLane; ++k) {
-    const long long m = t0 + (long long)k * kBlock;
-    if (free_[k]) {
-      row[m] = au[k] * kInv2PiD;
-      row[m_pad + m] = -aw[k] * kInv2PiD;
-    }
-  }
+  load_tracers<kTracerF32PerLane>(seed_x, seed_z, release, cur_x, cur_z, shift, step, count, -(double)kPadPosF, xp, zp, au, aw, free_);
+  hilo_field_f32<kTracerF32PerLane>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw);
+  observer_store<kTracerF32PerLane, kBlock>(slab, m_pad, [&](int k, long long) { return free_[k]; }, au, aw);
 }
 
 }  // namespace ludvm

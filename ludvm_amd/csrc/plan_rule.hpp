@@ -209,6 +209,41 @@ __host__ __device__ inline long long origin_index(long long b, int p, long long 
   return last >= first ? last : first;
 }
 
+// ---- launch rule of the marched observers (march_kernels.hpp: probes, tracers, survey) ---------------------------------------
+// `count` points in tiles of point_tile (one workgroup each, padded to `pad` columns of the slab [split][2][pad]); the sources --
+// at most ns_ub = n_ub + nfoil, n_ub the step's anchor-derived bound of the wake size after its solve -- in `nsplit` splits of
+// `chunk` sources, a multiple of the src_tile sources a kernel stages at once, chosen so that tiles x splits comes to about
+// `groups` workgroups, with at most max_split splits (the tracer and survey finishers add them one after the other).  A
+// function of count and ns_ub alone: the summation order of a step does not depend on where the calls of a run begin.
+struct ObserverRule { long long point_tile, src_tile, groups, max_split; };
+struct ObserverPlan { long long tiles, pad, chunk; int nsplit; };
+
+enum ObserverKind { kObsProbes = 0, kObsTracers, kObsTracersF32x2, kObsSurvey, kObsSurveyF32, kObserverKinds };
+// probes: one wavefront per tile, about one per SIMD of the device, no cap (their finisher sums the splits as a tree);
+// the others: 256 lanes x 2 (float64) or x 4 (fp32) points, about four workgroups per CU
+constexpr ObserverRule kObserverRules[kObserverKinds] = {
+    {64, 256, 1024, 1024}, {512, 256, 1024, 64}, {1024, 256, 1024, 64}, {512, 256, 1024, 64}, {1024, 256, 1024, 64}};
+
+inline long long observer_tiles(const ObserverRule& r, long long count) { return (count + r.point_tile - 1) / r.point_tile; }
+// the splits a step may have, whatever the wake size (count >= 1)
+inline long long observer_want(const ObserverRule& r, long long count) {
+  return plan_min(r.max_split, plan_max(1, r.groups / observer_tiles(r, count)));
+}
+inline ObserverPlan observer_plan(const ObserverRule& r, long long count, long long ns_ub) {
+  ObserverPlan p;
+  p.tiles = observer_tiles(r, count);
+  p.pad = p.tiles * r.point_tile;
+  const long long want = observer_want(r, count);
+  ns_ub = plan_max(ns_ub, 1);
+  p.chunk = plan_max(r.src_tile, ((ns_ub + want - 1) / want + r.src_tile - 1) / r.src_tile * r.src_tile);
+  p.nsplit = (int)((ns_ub + p.chunk - 1) / p.chunk);       // <= want
+  return p;
+}
+// the slab of any step: nsplit <= observer_want whatever the wake size (probes: at most 1 MiB; the others: at most 16 MiB)
+inline size_t observer_slab_bytes(const ObserverRule& r, long long count) {
+  return (size_t)observer_want(r, count) * 2 * (size_t)(observer_tiles(r, count) * r.point_tile) * 8;
+}
+
 // the instantiation's name as a profiler prints it
 inline void direct_kernel_name(const DirectVariant& v, char* out, size_t len) {
   if (v.kernel == kDirectF64Few) std::snprintf(out, len, "pair_f64_few<%d>", v.tile);

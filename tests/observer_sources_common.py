@@ -10,8 +10,8 @@ one trailing-edge vortex per step, in step i of a fresh run (anchor: step 0 for 
     ns(i)    = nfree + i + 80        the sources the kernels walk (read on the device)
     ns_ub(i) = nfree + 2 i + 80      the bound the host plans the launch with
 
-The launch rules themselves (probe_plan, tracer_plan, survey_plan of march.hip) are NOT restated in code here; the
-arithmetic of the three cases, for the reader:
+The launch rule itself (observer_plan of plan_rule.hpp) is NOT restated in code here (tests/test_observer_rule_host.py asks it
+for the plans quoted below); the arithmetic of the three cases, for the reader:
 
 case A  nfree = 1180, 24 steps.  ns_ub = 1280 at step 10: five full splits of 256; 1282 at step 11: a sixth split, empty
         through step 20; ns = 1280 exactly at step 20, 1281 at step 21: one source in the sixth split.  chunk = 256 in the

@@ -2,7 +2,8 @@
 states how a launch of the direct pair kernels divides its sources and targets and which instantiation serves it, in plain
 C++17.  This module compiles, once per process, a few lines of main() around it with the host C++ compiler and returns what
 they print: constants() -- the plan's constants and default knobs --, plan(cases) -- a Plan per case --, origin_index(b, p, n)
--- which vortex lends origin class (block b, index parity p) of n stored vortices its origin.
+-- which vortex lends origin class (block b, index parity p) of n stored vortices its origin --, observer_plan(kind, count, ns_ub)
+-- the launch of a marched observer's kernels (probes, tracers, survey) over `count` points with at most ns_ub sources.
 A case is a dict: precision ('f32' | 'f32x2' | 'f64'), ns, nt, and optionally local (positions on local origins: what
 LUDVM_PREC_F32 is wherever the library lays the positions out itself), grid_nz (> 0: a flow-field grid of that many points per
 row, nt = its points), slab (the results stay in the partial slabs for a fused finisher), plan_nt (the whole grid's points
@@ -24,10 +25,20 @@ CONSTANTS = ("kPlanBlock", "kTileF32", "kTileF32Small", "kTileF64", "kTileF64Few
 KNOBS = ("small_tile_max", "small_tile_max_f64", "tune_tpl", "tune_split", "grid_kernel", "few_packed")
 PRECISIONS = {"f32": 0, "f32x2": 1, "f64": 2}
 # stdin: precision ns nt local grid_nz slab plan_nt nt_on_device, then the six knobs (-1 = the product's); with an argument:
-# stdin: b p n per line -> origin_index
+# stdin: b p n per line -> origin_index; with the argument 'observer': stdin: kind count ns_ub per line -> ObserverPlan
+OBSERVER_KINDS = ("probes", "tracers", "tracers_f32x2", "survey", "survey_f32")       # (= ObserverKind)
 MAIN = r'''
 using namespace ludvm;
-int main(int argc, char**) {
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "observer") == 0) {
+    for (long long kind, count, ns; std::scanf("%lld %lld %lld", &kind, &count, &ns) == 3;) {
+      const ObserverRule& r = kObserverRules[kind];
+      const ObserverPlan p = observer_plan(r, count, ns);
+      std::printf("%lld %lld %lld %d %lld %zu %lld %lld\n", p.tiles, p.pad, p.chunk, p.nsplit, observer_want(r, count),
+                  observer_slab_bytes(r, count), r.point_tile, r.src_tile);
+    }
+    return 0;
+  }
   if (argc > 1) {
     for (long long b, p, n; std::scanf("%lld %lld %lld", &b, &p, &n) == 3;) std::printf("%lld\n", origin_index(b, (int)p, n));
     return 0;
@@ -69,7 +80,7 @@ def _program(tmp=tempfile.TemporaryDirectory(prefix="plan_rule_")):       # (rem
     """The dump program, built from HEADER -- the file the library's units include -- with the compiler oracle/Makefile uses."""
     cxx = next(c for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "hipcc", "/opt/rocm/bin/hipcc") if c and shutil.which(c))
     with open(os.path.join(tmp.name, "dump.cpp"), "w") as f:
-        f.write(f'#include "{HEADER}"\n' + MAIN)
+        f.write(f'#include "{HEADER}"\n#include <cstring>\n' + MAIN)
     subprocess.run([cxx, "-O1", "-std=c++17", "-x", "c++", "-o", os.path.join(tmp.name, "dump"), f.name], check=True, timeout=300)
     return os.path.join(tmp.name, "dump")
 
@@ -105,3 +116,19 @@ def origin_index(queries):
     out = _ask(["%d %d %d\n" % q for q in queries], "origin")
     assert len(out) == len(queries)
     return [int(l) for l in out]
+
+
+# tiles x nsplit workgroups; pad columns per slab row and component; nsplit splits of chunk sources (the last may hold fewer,
+# or none); want: the splits any step may have; slab_bytes: what the setter allocates; point_tile, src_tile: the rule's
+ObserverPlan = collections.namedtuple("ObserverPlan", "tiles pad chunk nsplit want slab_bytes point_tile src_tile")
+
+
+def observer_plan(kind, count, ns_ub):
+    """The launch of observer `kind` (one of OBSERVER_KINDS) with `count` >= 1 points in a step whose sources number at most
+    ns_ub; arrays of counts and bounds give a list over their product (count-major)."""
+    counts, bounds = ([int(v) for v in (a if hasattr(a, "__len__") else [a])] for a in (count, ns_ub))
+    k = OBSERVER_KINDS.index(kind)
+    out = _ask(["%d %d %d\n" % (k, c, n) for c in counts for n in bounds], "observer")
+    assert len(out) == len(counts) * len(bounds)
+    rows = [ObserverPlan(*map(int, l.split())) for l in out]
+    return rows if hasattr(count, "__len__") or hasattr(ns_ub, "__len__") else rows[0]

@@ -2,12 +2,13 @@
 """What velocity probes cost (profiles/probes_cost.txt): wall time of a marched run with P probes, and the parent's only way
 to one probe row -- Engine.induce(precision='f64') against the final wake -- beside it.
 
-    python tools/probes_cost.py time   [--case config1|long] [--probes P] [--repeats R] [--root DIR]
+    python tools/probes_cost.py time   [--case config1|long] [--probes P] [--repeats R] [--root DIR] [--lib LIB]
     python tools/probes_cost.py once   [--case ...] [--probes P] [--root DIR]      one run, no warm-up (under rocprofv3)
     python tools/probes_cost.py induce [--probes P]                                 Engine.induce f64, P points x final wake
     python tools/probes_cost.py stats  A_kernel_stats.csv [B_kernel_stats.csv]      kernel names and counts (equal?), probe kernels
 
---root DIR imports ludvm_amd from another checkout (A/B against another build; probes need this one).
+--root DIR imports ludvm_amd from another checkout (A/B against another build; probes need this one); --lib LIB loads another
+build of the library into this checkout's package (A/B of two libraries: one process each, processes alternated).
 'long' = 5000 steps at dt = 1e-3, history='sparse', precision='f32'; 'config1' = the README case."""
 import argparse
 import csv
@@ -24,6 +25,7 @@ ap.add_argument("--case", default="long", choices=["config1", "long"])
 ap.add_argument("--probes", type=int, default=0)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--lib", default=None)
 args = ap.parse_args()
 
 CONFIG1 = dict(t0=0, tf=20, dt=5e-2, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012")
@@ -59,7 +61,7 @@ extra = {}
 if args.probes:
     # a rake behind the foil in the frame of the pivot, P points over z in [-2, 2]
     extra = dict(probes=np.stack([np.full(args.probes, 2.0), np.linspace(-2.0, 2.0, args.probes)]), probe_frame="tunnel")
-eng = Engine(0)
+eng = Engine(0, lib_path=args.lib)
 
 
 def run():
@@ -79,7 +81,7 @@ elif args.mode == "time":
     if args.probes:
         n_src = eng.wake_size() / 2 + sim.Npoints - 1           # mean number of sources over the run, roughly
         pairs = args.probes * n_src * (sim.nt - 1)
-    print(f"{args.case} P={args.probes} root={os.path.basename(os.path.abspath(args.root))}: "
+    print(f"{args.case} P={args.probes} root={os.path.basename(os.path.abspath(args.root))} lib={args.lib or 'own'}: "
           f"min {min(ts):.4f} median {sorted(ts)[len(ts) // 2]:.4f} max {max(ts):.4f} s over {len(ts)} runs, {sim.nt - 1} steps, "
           f"final wake {eng.wake_size()}" + (f", ~{pairs:.3g} probe pairs" if pairs else ""))
 else:

@@ -10,7 +10,12 @@ of ludvm_amd/ludvm.py (a refactoring must not move a bit).
     python tools/result_hash.py --ensemble [--lib path/to/libludvm_hip.so]
 fingerprints a sweep WITHOUT probes -- the 12-member grid of tests/test_gpu_ensemble.py, snapshot steps 1, 2, 10, 50: every
 member's loads, circulations, Fourier coefficients, LEV shedding and recorded wakes -- to A/B ensemble_march<false> against
-the kernel of the commit before the probes (profiles/ensemble_probes_result_hash.json)."""
+the kernel of the commit before the probes (profiles/ensemble_probes_result_hash.json).
+    python tools/result_hash.py --observers [--lib path/to/libludvm_hip.so]
+fingerprints every array the marched observers return (probe rows, tracer paths and last positions, survey sums; bin sums and
+counts) in cases A and C of tests/observer_sources_common.py with the `few` and the `many` observer sets in float64, and case
+A / few again with survey_precision='f32', with tracer_precision='f32x2' and with three survey bins: several point tiles, the
+64-split cap, the probe finisher's strided leg and an empty last split (profiles/observer_refactor_result_hash.json)."""
 import argparse
 import hashlib
 import json
@@ -26,6 +31,7 @@ ap.add_argument("--lib", default="")
 ap.add_argument("--sizes", type=int, nargs="*", default=[20000, 40000, 70000, 200000, 400000, 600001, 1000000])
 ap.add_argument("--timeloop", action="store_true")
 ap.add_argument("--ensemble", action="store_true")
+ap.add_argument("--observers", action="store_true")
 ap.add_argument("--ludvm-module", default="ludvm_amd.ludvm")
 a = ap.parse_args()
 from ludvm_amd import _ffi  # noqa: E402
@@ -35,6 +41,30 @@ import torch  # noqa: E402
 from ludvm_amd import Engine  # noqa: E402
 
 eng = Engine(0)
+if a.observers:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import observer_sources_common as C
+    from ludvm_amd import LUDVM
+
+    def observed(case, which, **extra):
+        kw = dict(C.case_keywords(case), verbose=False, engine=eng, precision="f64", history="full", **C.run_keywords(C.observers(case, which)))
+        sim = LUDVM(**dict(kw, **extra))
+        parts = [sim.probe_u, sim.probe_w, sim.tracer_last, sim.survey_sums] + [sim.tracer_path[s] for s in sim.tracer_path.steps()]
+        if "survey_bins" in extra:
+            parts += [sim.survey_bin_sums, sim.survey_bin_count]
+        h = hashlib.sha256()
+        for v in parts:
+            h.update(np.ascontiguousarray(v, dtype=np.float64).tobytes())
+        return h.hexdigest()[:16]
+    out = {"lib": os.path.relpath(_ffi.LIB_PATH, ROOT)}
+    for case in ("A", "C"):
+        for which in C.SETS:
+            out[f"{case}_{which}_f64"] = observed(case, which)
+    out["A_few_survey_f32"] = observed("A", "few", survey_precision="f32")
+    out["A_few_tracers_f32x2"] = observed("A", "few", tracer_precision="f32x2")
+    out["A_few_survey_bins"] = observed("A", "few", survey_bins=np.arange(C.CASES["A"][1] + 1) % 3)
+    print(json.dumps(out))
+    sys.exit(0)
 if a.ensemble:
     import warnings
     from ludvm_amd import sweep

@@ -6,9 +6,11 @@ pair_f64's and pair_f32's on the same points and wake.
 
     python tools/survey_cost.py ab     --parent-lib LIB [--repeats R]        survey=None: this build and the parent's library
                                                                               loaded in ONE process, runs alternated
-    python tools/survey_cost.py time   --survey K [--repeats R] [--every E] [--first F]
+    python tools/survey_cost.py time   --survey K [--repeats R] [--every E] [--first F] [--lib LIB]
                                                                               wall time, added time per sampled step and pair
                                                                               count: a float64 and an fp32 column, and their ratio
+                                                                              (--lib: another build of the library, also with
+                                                                              --bins; A/B of two libraries: one process each)
     python tools/survey_cost.py time   --survey K --bins B [--repeats R] [--every E] [--first F] [--precision f64|f32]
                                                                               the same run with the survey alone and with B phase
                                                                               bins (survey_bins=B), alternated: the added time
@@ -45,6 +47,7 @@ ap.add_argument("--lespcrit", type=float, default=0.2, help="10: no leading-edge
 ap.add_argument("--induce", action="store_true")
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--steps", type=int, default=5000)
+ap.add_argument("--lib", default=None)
 ap.add_argument("--parent-lib", default=None)
 ap.add_argument("--pairs", type=float, default=0)
 ap.add_argument("--induce-pairs", type=float, default=0)
@@ -127,7 +130,9 @@ if args.mode == "ab":
           f"[{min(tb):.4f}, {max(tb):.4f}]: {min(tb) <= ma <= max(tb)}")
     sys.exit(0)
 
-eng = Engine(0)
+eng = Engine(0, lib_path=args.lib)
+if args.lib:
+    print(f"library: {args.lib}")
 if args.mode == "once":
     run(eng)
     for prec in ("f64", "f32"):
