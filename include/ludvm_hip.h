@@ -92,6 +92,14 @@ int ludvm_set_tuning(ludvm_ctx* ctx, int targets_per_lane, int source_splits);
  * mode 0 = never (direct kernel), 1 = automatic (default; fp32, N >= 16384),
  * mode >= 2 = automatic with that value as the smallest N that takes the symmetric kernel. */
 int ludvm_set_symmetric(ludvm_ctx* ctx, int mode);
+/* Symmetric launches on plain fp32 DEVICE arrays (ludvm_induce_dev_f32 with the sources as targets, ludvm_advect_dev_f32
+ * over the whole array; LUDVM.py:549-570 on one array) may be evaluated in Morton order: box, keys, stable sort and gather
+ * on the context's stream, the pair kernel on the ordered copies, every result written at the caller's own index by the
+ * finisher.  The sum does not care about the order; the kernel's operands become spatially coherent, which lets the chip
+ * hold a higher clock under it.  Keys, sort and fixed-point sums depend on the input alone: a call repeats bit for bit.
+ * mode 0 = never, 1 = from the size the library's rule states (default; csrc/sym_rule.hpp, kSelfOrderMin; smaller
+ * launches are what they were, bit for bit), 2 = whenever the symmetric kernel runs (tests, A/B). */
+int ludvm_set_self_order(ludvm_ctx* ctx, int mode);
 /* Tuning of the symmetric kernel (tests; 0 = the library's rule by launch size): vortices per lane (4: 256-vortex tiles,
  * 8: 512-vortex tiles; plain fp32 positions only) and the number of wavefronts (1, 2, 4) that share the 64 rotation steps
  * of one tile pair.  Results change only through the partition into fp32 partial sums.  (The measurement build also takes

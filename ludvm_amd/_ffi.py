@@ -58,6 +58,7 @@ SIGNATURES = {
     "ludvm_synchronize": [c_void_p],
     "ludvm_set_tuning": [c_void_p, c_int, c_int],
     "ludvm_set_symmetric": [c_void_p, c_int],
+    "ludvm_set_self_order": [c_void_p, c_int],
     "ludvm_set_shard": [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t],
     "ludvm_set_sym_tuning": [c_void_p, c_int, c_int],
     "ludvm_comm_unique_id": [c_void_p, c_size_t],

@@ -221,4 +221,11 @@ int ludvm_set_symmetric(ludvm_ctx* c, int mode) {
   return LUDVM_OK;
 }
 
+int ludvm_set_self_order(ludvm_ctx* c, int mode) {
+  if (!c) return LUDVM_E_ARG;
+  if (mode < 0 || mode > 2) return fail(c, LUDVM_E_ARG, "self-order mode must be 0 (never), 1 (by size) or 2 (always)");
+  c->self_order = mode;
+  return LUDVM_OK;
+}
+
 }  // extern "C"

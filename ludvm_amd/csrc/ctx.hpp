@@ -4,7 +4,7 @@
 // (sym_prepare_kernels.hpp -> launch.hip, induce_kernels.hpp -> induce.hip, wake_kernels.hpp -> wake.hip, march_kernels.hpp and
 // ensemble_kernels.hpp -> march.hip, field_kernels.hpp -> flowfield.hip, order_kernels.hpp -> order.hip).
 //
-//   context.hip    lifecycle, streams, tuning, the error string, staging copies            (ludvm_create ... ludvm_set_symmetric)
+//   context.hip    lifecycle, streams, tuning, the error string, staging copies            (ludvm_create ... ludvm_set_self_order)
 //   launch.hip     plans and launches of the pair kernels, direct and symmetric; timing    (internal; ludvm_kernel_time_ms)
 //   comm.hip       the library's own RCCL communicator                                     (ludvm_comm_*)
 //   order.hip      spatial order of unordered inputs                                       (ludvm_spatial_order)
@@ -67,6 +67,7 @@ struct ludvm_ctx {
   int tune_tpl = 0;
   int tune_split = 0;
   int sym_mode = 1;
+  int self_order = 1;                        // ludvm_set_self_order: 0 never, 1 by the rule (kSelfOrderMin), 2 always
   int tune_sym_t = 0, tune_sym_rsplit = 0;   // ludvm_set_sym_tuning (0 = heuristics)
   int xcd_run = 0;                           // chunks per run of the XCD placement (LUDVM_XCD_RUN; 0 = a launch's chunks / 8)
   long long sym_tail_items = kSymTailItems;  // mixed granularity: work kept for the fine-grained end (LUDVM_SYM_TAIL_ITEMS)
@@ -83,7 +84,8 @@ struct ludvm_ctx {
   Buf acc;    // raw (u, w) sums of the symmetric kernel: [2][nt_pad] 64-bit fixed-point integers
   Buf symsc;  // SymScale of the current symmetric launch, followed by its NaN counter (long long)
   Buf arena;  // staging for the host-pointer entry points
-  Buf orderws;  // spatial order of unordered inputs: two permutations, class extents, the sort's temporaries
+  Buf orderws;  // spatial order of unordered inputs: two permutations, class extents, the sort's temporaries; or (self_order_f32)
+                // one permutation, the three gathered fp32 arrays, the box and the sort's temporaries
   char* pin = nullptr;  // pinned host ring for small uploads from entry points that do not synchronize
   size_t pin_off = 0;
   char* pin_out = nullptr;  // pinned host buffer for small synchronous read-backs
@@ -226,6 +228,7 @@ int induce_device(ludvm_ctx* c, const PairArgs& a, long long nt, long long ns, i
                   long long plan_nt = 0);
 long long sym_threshold(const ludvm_ctx* c, bool march = false);
 bool use_symmetric(const ludvm_ctx* c, long long n, double vc4, bool march = false);
+bool use_self_order(const ludvm_ctx* c, long long n);
 int sym_tile_t(const ludvm_ctx* c, long long n, bool hilo);
 
 struct SymOperands {
@@ -274,6 +277,14 @@ int spatial_order_if_needed(ludvm_ctx* c, const OrderWs& w, int slot, const doub
 int order_gather(ludvm_ctx* c, const double* s0, const double* s1, const double* s2, const unsigned* order, long long n, double* d0,
                  double* d1, double* d2);
 int order_scatter(ludvm_ctx* c, const double* s0, const double* s1, const unsigned* order, long long n, double* d0, double* d1);
+// Morton order of n plain fp32 device positions and the arrays gathered into it: x[k] = d_x[order[k]] ...  Everything is
+// issued on the context's stream and lives in c->orderws until the next call that orders: no host synchronisation (once
+// the workspace has its size), no host-side decision, nothing kept from call to call.
+struct SelfOrdered {
+  const unsigned* order;
+  const float *x, *z, *g;
+};
+int self_order_f32(ludvm_ctx* c, const float* d_x, const float* d_z, const float* d_g, size_t n, SelfOrdered* out);
 // fp32 on local origins resolves a pair difference to ~6e-8 of its class's extent; next to a core of radius v_core that is
 // up to ~5e-8 extent / v_core of max|u| for an area-filling cloud [MI355X, profiles/r04_extent_rule_calibration.txt: 2e5 ... 2e6
 // vortices in a 10 x 4 box, v_core 6.5e-4 ... 6.5e-2, Morton order: errors 0.5 ... 5e-8 per unit of extent / v_core, a tail

@@ -6,6 +6,27 @@
 #include "ctx.hpp"
 #include "induce_kernels.hpp"
 
+namespace {
+
+// Symmetric self-interaction of plain fp32 device arrays (the device-pointer entry points): raw sums in the context's
+// accumulators; where the rule asks for it (sym_rule.hpp, kSelfOrderMin; ludvm_set_self_order) the kernel runs on copies in
+// Morton order and *order says which caller element each slot of the sums belongs to (NULL: slot i is element i).
+int sym_self_dev(ludvm_ctx* c, const float* d_x, const float* d_z, const float* d_g, long long n, double vc4, long long* nt_pad,
+                 const long long** acc, const long long** bad, const unsigned** order) {
+  SymOperands o{};
+  o.x = d_x; o.z = d_z; o.g = d_g;
+  *order = nullptr;
+  if (use_self_order(c, n)) {
+    SelfOrdered so{};
+    CHK(self_order_f32(c, d_x, d_z, d_g, (size_t)n, &so));
+    o.x = so.x; o.z = so.z; o.g = so.g;
+    *order = so.order;
+  }
+  return launch_sym(c, o, n, vc4, nt_pad, acc, bad);
+}
+
+}  // namespace
+
 extern "C" {
 
 /* ---- stateless pair sum ------------------------------------------------------------------- */
@@ -134,7 +155,7 @@ int ludvm_induce_f64(ludvm_ctx* c, const double* xs, const double* zs, const dou
       const long long *acc = nullptr, *bad = nullptr;
       CHK(launch_sym(c, o, (long long)ns, a.vc4, &nt_pad, &acc, &bad));
       hipLaunchKernelGGL(finish_sym, dim3(blocks_for((long long)nt)), dim3(kBlock), 0, c->stream, acc, acc + nt_pad, ctx_scale(c),
-                         bad, (long long)nt, fu, fw);
+                         bad, (const unsigned*)nullptr, (long long)nt, fu, fw);
       HIPCHK(c, hipGetLastError());
     } else {
       a.xs = fxs; a.zs = fzs; a.gs = fgs;
@@ -211,12 +232,11 @@ int ludvm_induce_dev_f32(ludvm_ctx* c, const float* d_xs, const float* d_zs, con
   const double v2 = (double)vcore * (double)vcore;
   if (d_xt == d_xs && d_zt == d_zs && nt == ns && use_symmetric(c, (long long)ns, v2 * v2)) {
     long long nt_pad = 0;
-    SymOperands o{};
-    o.x = d_xs; o.z = d_zs; o.g = d_gs;
     const long long *acc = nullptr, *bad = nullptr;
-    CHK(launch_sym(c, o, (long long)ns, v2 * v2, &nt_pad, &acc, &bad));
+    const unsigned* order = nullptr;
+    CHK(sym_self_dev(c, d_xs, d_zs, d_gs, (long long)ns, v2 * v2, &nt_pad, &acc, &bad, &order));
     hipLaunchKernelGGL(finish_sym, dim3(blocks_for((long long)nt)), dim3(kBlock), 0, c->stream, acc, acc + nt_pad, ctx_scale(c),
-                       bad, (long long)nt, d_u, d_w);
+                       bad, order, (long long)nt, d_u, d_w);
     HIPCHK(c, hipGetLastError());
     return LUDVM_OK;
   }
@@ -237,12 +257,11 @@ int ludvm_advect_dev_f32(ludvm_ctx* c, const float* d_xs, const float* d_zs, con
   const double v2 = (double)vcore * (double)vcore;
   if (t_first == 0 && nt == ns && use_symmetric(c, (long long)ns, v2 * v2)) {
     long long nt_pad = 0;
-    SymOperands o{};
-    o.x = d_xs; o.z = d_zs; o.g = d_gs;
     const long long *acc = nullptr, *bad = nullptr;
-    CHK(launch_sym(c, o, (long long)ns, v2 * v2, &nt_pad, &acc, &bad));
+    const unsigned* order = nullptr;
+    CHK(sym_self_dev(c, d_xs, d_zs, d_gs, (long long)ns, v2 * v2, &nt_pad, &acc, &bad, &order));
     hipLaunchKernelGGL(finish_sym_advect, dim3(blocks_for((long long)nt)), dim3(kBlock), 0, c->stream, acc, acc + nt_pad,
-                       ctx_scale(c), bad, d_xs, d_zs, 0LL, (long long)nt, dt, d_x_out, d_z_out);
+                       ctx_scale(c), bad, order, d_xs, d_zs, 0LL, (long long)nt, dt, d_x_out, d_z_out);
     HIPCHK(c, hipGetLastError());
     return LUDVM_OK;
   }
@@ -296,8 +315,8 @@ int ludvm_advect_from_sums_dev_f32(ludvm_ctx* c, const long long* d_sum_u, const
   if (nt == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   hipLaunchKernelGGL(finish_sym_advect, dim3(blocks_for((long long)nt)), dim3(kBlock), 0, c->stream, d_sum_u, d_sum_w,
-                     static_cast<const SymScale*>(d_scale), d_bad, d_x, d_z, (long long)t_first, (long long)nt, dt, d_x_out,
-                     d_z_out);
+                     static_cast<const SymScale*>(d_scale), d_bad, (const unsigned*)nullptr, d_x, d_z, (long long)t_first,
+                     (long long)nt, dt, d_x_out, d_z_out);
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
 }

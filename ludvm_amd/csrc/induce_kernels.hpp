@@ -73,26 +73,29 @@ cvt_packed_outputs(const float* u, const float* w, double* out, long long nt) {
   out[k] = k < nt ? (double)u[k] : (double)w[k - nt];
 }
 
-// acc -> velocities
+// acc -> velocities.  order (may be NULL): the launch ran on arrays gathered in that order (order.hip, self_order_f32), slot i
+// of the sums belongs to the caller's element order[i] -- the way back costs no pass of its own.
 __global__ void __launch_bounds__(kBlock)
-finish_sym(const long long* acc_u, const long long* acc_w, const SymScale* sc, const long long* bad, long long n, float* u,
-           float* w) {
+finish_sym(const long long* acc_u, const long long* acc_w, const SymScale* sc, const long long* bad, const unsigned* order,
+           long long n, float* u, float* w) {
   const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
+  const long long p = order ? (long long)order[i] : i;
   const float s = (float)kInv2PiD;
-  u[i] = fx_read(acc_u, i, sc, bad) * s;
-  w[i] = -fx_read(acc_w, i, sc, bad) * s;
+  u[p] = fx_read(acc_u, i, sc, bad) * s;
+  w[p] = -fx_read(acc_w, i, sc, bad) * s;
 }
 
-// raw sums of targets [t_first, t_first + nt) (sum_u[i], sum_w[i] belong to target t_first + i) -> Euler step
+// raw sums of targets [t_first, t_first + nt) (sum_u[i], sum_w[i] belong to target t_first + i, or t_first + order[i]) -> Euler step
 __global__ void __launch_bounds__(kBlock)
-finish_sym_advect(const long long* sum_u, const long long* sum_w, const SymScale* sc, const long long* bad, const float* x,
-                  const float* z, long long t_first, long long nt, float dt, float* x_out, float* z_out) {
+finish_sym_advect(const long long* sum_u, const long long* sum_w, const SymScale* sc, const long long* bad, const unsigned* order,
+                  const float* x, const float* z, long long t_first, long long nt, float dt, float* x_out, float* z_out) {
   const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (i >= nt) return;
+  const long long p = order ? (long long)order[i] : i;
   const float s = (float)kInv2PiD;
-  x_out[i] = __builtin_fmaf(dt, fx_read(sum_u, i, sc, bad) * s, x[t_first + i]);
-  z_out[i] = __builtin_fmaf(dt, -fx_read(sum_w, i, sc, bad) * s, z[t_first + i]);
+  x_out[p] = __builtin_fmaf(dt, fx_read(sum_u, i, sc, bad) * s, x[t_first + p]);
+  z_out[p] = __builtin_fmaf(dt, -fx_read(sum_w, i, sc, bad) * s, z[t_first + p]);
 }
 
 }  // namespace ludvm

@@ -167,6 +167,7 @@ static_assert(64 * 8 == LUDVM_SYM_TILE, "the multi-GPU entry points always use t
 SymKnobs sym_knobs(const ludvm_ctx* c) {
   SymKnobs k;
   k.sym_mode = c->sym_mode;
+  k.self_order = c->self_order;
   k.tile_t = c->tune_sym_t;
   k.tune_split = c->tune_split;
   k.tune_rsplit = c->tune_sym_rsplit;
@@ -179,6 +180,7 @@ long long sym_threshold(const ludvm_ctx* c, bool march) { return sym_min_n(sym_k
 bool use_symmetric(const ludvm_ctx* c, long long n, double vc4, bool march) {
   return sym_use(sym_knobs(c), n, (float)vc4 > 0.0f, march);
 }
+bool use_self_order(const ludvm_ctx* c, long long n) { return sym_self_order(sym_knobs(c), n); }
 // (local origins fit both tiles: a 512-vortex tile keeps its targets twice)
 int sym_tile_t(const ludvm_ctx* c, long long n, bool hilo) { return sym_tile(sym_knobs(c), n, hilo); }
 

@@ -99,6 +99,34 @@ int order_scatter(ludvm_ctx* c, const double* s0, const double* s1, const unsign
   return LUDVM_OK;
 }
 
+// ---- Morton order of plain fp32 device arrays (the device-pointer self-interaction launches, sym_rule.hpp kSelfOrderMin) ----
+// Not for accuracy -- these entry points take plain positions, whose pair differences round the same in any order -- but
+// for the pair kernel's operand statistics (see kSelfOrderMin).  Box (two fixed stages), keys, rocPRIM's stable sort, one
+// gather; min / max, the keys and the sort depend on the input alone, so the same call gives the same order every time.
+int self_order_f32(ludvm_ctx* c, const float* d_x, const float* d_z, const float* d_g, size_t n, SelfOrdered* out) {
+  if (n >= ((size_t)1 << 32)) return fail(c, LUDVM_E_ARG, "too many points");
+  const long long nblk = (long long)((n + kBoxChunk - 1) / kBoxChunk);
+  const size_t tb = spatial_order_temp_bytes(n), nb = up256(n * 4);
+  // sized once, before the first launch (a later grow would free arrays in use)
+  CHK(ensure(c, c->orderws, 4 * nb + up256((size_t)nblk * 4 * sizeof(float)) + 256 + tb));
+  char* p = static_cast<char*>(c->orderws.p);
+  unsigned* order = reinterpret_cast<unsigned*>(p); p += nb;
+  float* xo = reinterpret_cast<float*>(p); p += nb;
+  float* zo = reinterpret_cast<float*>(p); p += nb;
+  float* go = reinterpret_cast<float*>(p); p += nb;
+  float* part = reinterpret_cast<float*>(p); p += up256((size_t)nblk * 4 * sizeof(float));
+  OrderBox* box = reinterpret_cast<OrderBox*>(p); p += 256;
+  hipLaunchKernelGGL(box_partial_f32, dim3((unsigned)nblk), dim3(256), 0, c->stream, d_x, d_z, (long long)n, part);
+  hipLaunchKernelGGL(box_final_f32, dim3(1), dim3(256), 0, c->stream, part, nblk, box);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, spatial_order_sort_f32(d_x, d_z, n, box, p, tb, order, c->stream));
+  hipLaunchKernelGGL(gather_f32, dim3(blocks_for((long long)n)), dim3(kBlock), 0, c->stream, d_x, d_z, d_g, order, (long long)n, xo,
+                     zo, go);
+  HIPCHK(c, hipGetLastError());
+  *out = SelfOrdered{order, xo, zo, go};
+  return LUDVM_OK;
+}
+
 }  // namespace ludvm_host
 
 extern "C" {

@@ -2,6 +2,7 @@
 // order, and the gathers / scatters that apply an order.  See order.hip, spatial_order_if_needed (the only unit that includes this header).
 #pragma once
 #include "pair_kernels.hpp"
+#include "spatial_order.hpp"
 
 namespace ludvm {
 
@@ -63,6 +64,69 @@ __global__ void __launch_bounds__(256) reduce_extents(const double* ext, long lo
     __syncthreads();
   }
   if (threadIdx.x < 5) out[threadIdx.x] = red[0][threadIdx.x];
+}
+
+// Bounding box of the finite positions among (x, z)[0, n), plain fp32, in two fixed stages that leave it in device memory.
+// Stage 1: workgroup b reduces points [b kBoxChunk, (b + 1) kBoxChunk) to part[4 b ..] = xmin, xmax, zmin, zmax (+inf / -inf
+// where it holds no finite point).
+constexpr int kBoxChunk = 4096;
+__device__ __forceinline__ void box_merge(float& x0, float& x1, float& z0, float& z1, float a, float b, float c, float d) {
+  x0 = __builtin_fminf(x0, a); x1 = __builtin_fmaxf(x1, b); z0 = __builtin_fminf(z0, c); z1 = __builtin_fmaxf(z1, d);
+}
+// workgroup of 256: every lane's bounds -> the workgroup's, valid in thread 0
+__device__ __forceinline__ void box_reduce_block(float& x0, float& x1, float& z0, float& z1) {
+  for (int s = 1; s < 64; s <<= 1)
+    box_merge(x0, x1, z0, z1, __shfl_xor(x0, s), __shfl_xor(x1, s), __shfl_xor(z0, s), __shfl_xor(z1, s));
+  __shared__ float red[4][4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { red[wv][0] = x0; red[wv][1] = x1; red[wv][2] = z0; red[wv][3] = z1; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < 4; ++w) box_merge(x0, x1, z0, z1, red[w][0], red[w][1], red[w][2], red[w][3]);
+}
+__global__ void __launch_bounds__(256) box_partial_f32(const float* x, const float* z, long long n, float* part) {
+  const float inf = __builtin_inff();
+  float x0 = inf, x1 = -inf, z0 = inf, z1 = -inf;
+  const long long base = (long long)blockIdx.x * kBoxChunk;
+  for (int j = 0; j < kBoxChunk / 256; ++j) {
+    const long long i = base + j * 256 + threadIdx.x;
+    if (i < n) {
+      const float vx = x[i], vz = z[i];
+      if (__builtin_fabsf(vx) < inf && __builtin_fabsf(vz) < inf) box_merge(x0, x1, z0, z1, vx, vx, vz, vz);
+    }
+  }
+  box_reduce_block(x0, x1, z0, z1);
+  if (threadIdx.x == 0) {
+    float* o = part + 4 * (long long)blockIdx.x;
+    o[0] = x0; o[1] = x1; o[2] = z0; o[3] = z1;
+  }
+}
+// Stage 2 (one workgroup): the partial boxes -> the key record of spatial_order_sort_f32, 65536 cells over the extent of each
+// axis (scale 0 for an axis without extent, and for both when no position is finite)
+__global__ void __launch_bounds__(256) box_final_f32(const float* part, long long nblk, OrderBox* box) {
+  const float inf = __builtin_inff();
+  float x0 = inf, x1 = -inf, z0 = inf, z1 = -inf;
+  for (long long i = threadIdx.x; i < nblk; i += 256) box_merge(x0, x1, z0, z1, part[4 * i], part[4 * i + 1], part[4 * i + 2], part[4 * i + 3]);
+  box_reduce_block(x0, x1, z0, z1);
+  if (threadIdx.x == 0) {
+    const bool any = x1 >= x0;
+    const double ex = any ? (double)x1 - (double)x0 : 0.0, ez = any ? (double)z1 - (double)z0 : 0.0;
+    box->x0 = any ? (double)x0 : 0.0;
+    box->z0 = any ? (double)z0 : 0.0;
+    box->sx = ex > 0.0 ? 65536.0 / ex : 0.0;
+    box->sz = ez > 0.0 ? 65536.0 / ez : 0.0;
+  }
+}
+
+// the three fp32 arrays of a self-interaction launch in the order `order`
+__global__ void __launch_bounds__(kBlock)
+gather_f32(const float* x, const float* z, const float* g, const unsigned* order, long long n, float* xo, float* zo, float* go) {
+  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= n) return;
+  const long long p = (long long)order[k];
+  xo[k] = x[p];
+  zo[k] = z[p];
+  go[k] = g[p];
 }
 
 // dst[a][k] = src[a][order[k]] for up to three arrays of n doubles (order == nullptr: a copy)

@@ -26,4 +26,11 @@ size_t spatial_order_temp_bytes(size_t n);
 hipError_t spatial_order_sort(const double* d_x, const double* d_z, size_t n, OrderBox box, void* d_tmp, size_t tmp_bytes,
                               unsigned* d_order, hipStream_t stream);
 
+// The same for plain fp32 positions with the box in DEVICE memory (x0, z0 the low corner of the finite positions, sx, sz
+// cells per unit of length of each axis; a scale of 0 -- no extent along that axis -- puts every point in cell 0): nothing
+// comes back to the host.  A non-finite position takes the largest key; equal keys keep the caller's order (a set without
+// extent in either axis: the identity).
+hipError_t spatial_order_sort_f32(const float* d_x, const float* d_z, size_t n, const OrderBox* d_box, void* d_tmp,
+                                  size_t tmp_bytes, unsigned* d_order, hipStream_t stream);
+
 }  // namespace ludvm

@@ -263,10 +263,22 @@ constexpr long long kSymT8MinN = 36864;
 constexpr long long kSymMinNMarch = 11264;
 // The quad variant takes launches of at least this many 512-vortex tiles whose items the size rule gives one wave each.
 constexpr long long kSymQuadMinTiles = 640;
+// A symmetric launch on plain fp32 device arrays (ludvm_induce_dev_f32, the self path of ludvm_advect_dev_f32) of at least
+// this many vortices is evaluated in Morton order: one O(N) pre-pass (bounding box, keys, stable sort, gather), the pair
+// kernel on the ordered copies, the way back fused into the finisher.  The pair kernel has no data-dependent path; what
+// the order changes is its operands' statistics -- a tile is then a small box, the high bits of every dx, dz, r^2 and rsq
+// of a tile pair nearly constant -- and with them the power per operation and the clock the chip holds under this
+// energy-limited kernel.  Measured [MI355X] on the uniform cloud of bench.py, same box, the two modes alternating, medians
+// of 6 blocks of 10 whole calls, pre-pass included (profiles/self_order_ab.txt): 327 680 vortices +1.2 % (unordered arm's own
+// block-to-block spread 0.8 %), 524 288 +2.2 % (0.1 %), 1e6 +3.0 % (0.5 %); the pre-pass itself 0.14 / 0.16 / 0.22 ms.  The
+// threshold is the smallest of these sizes whose gain exceeds max(1.5 %, 3 x that spread).  A shed wake is coherent as
+// stored and gains nothing; the resident wake and the march do not come this way.
+constexpr long long kSelfOrderMin = 524288;
 
 // What a context can override; the defaults are the library's.
 struct SymKnobs {
   int sym_mode = 1;                             // 0: never symmetric; 1: from kSymMinN / kSymMinNMarch; > 1: from this size
+  int self_order = 1;                           // device-pointer self launches in Morton order: 0 never, 1 from kSelfOrderMin, 2 always
   int tile_t = 0;                               // 4 or 8: that many vortices per lane at every size (0: by size)
   int tune_split = 0;                           // > 0: this many d-chunks
   int tune_rsplit = 0;                          // 1, 2, 4: waves per item; -1: mixed everywhere; -2: nowhere; -4: quad (0: by size)
@@ -282,6 +294,10 @@ inline long long sym_min_n(const SymKnobs& k, bool march) {
 // core: (float)v_core^4 > 0
 inline bool sym_use(const SymKnobs& k, long long n, bool core, bool march) {
   return k.sym_mode != 0 && core && n >= sym_min_n(k, march);
+}
+// (asked only of launches that sym_use gave to the symmetric kernel)
+inline bool sym_self_order(const SymKnobs& k, long long n) {
+  return k.self_order == 2 || (k.self_order == 1 && n >= kSelfOrderMin);
 }
 inline int sym_tile(const SymKnobs& k, long long n, bool hilo) {
   if (hilo) return 4;                 // hi+lo positions: 256-vortex tile only

@@ -110,6 +110,12 @@ class Engine:
         pair once, 64-bit fixed-point accumulation: also bitwise reproducible); n >= 2: the same from n vortices."""
         self._check(self._lib.ludvm_set_symmetric(self._ctx, int(mode)))
 
+    def set_self_order(self, mode=1):
+        """Symmetric launches on device arrays (induce_dev on one array, advect_dev over the whole array) in Morton order:
+        0 never; 1 from the size the library's rule states (kSelfOrderMin); 2 whenever the symmetric kernel runs.  Results
+        come back at the caller's indices either way."""
+        self._check(self._lib.ludvm_set_self_order(self._ctx, int(mode)))
+
     def set_shard(self, rank, world, allreduce=None, d_acc=0, acc_bytes=0, min_vortices=0):
         """Evaluate only tile block `rank` of `world` of every symmetric roll-up of at least `min_vortices` vortices;
         `allreduce(count, stream)` must enqueue, on the hipStream_t `stream` (an int handle; 0 = the default stream), an

@@ -18,7 +18,7 @@ int main(int, char** argv) {
   SymKnobs k;
   const bool march = std::atoi(argv[1]), first_quad = std::atoi(argv[3]);
   if (std::atoll(argv[2]) > 0) k.t8_min_n = std::atoll(argv[2]);
-  std::printf("%lld %lld %lld %lld\n", kSymMinN, kSymMinNMarch, kSymT8MinN, kSymQuadMinTiles);
+  std::printf("%lld %lld %lld %lld %lld\n", kSymMinN, kSymMinNMarch, kSymT8MinN, kSymQuadMinTiles, kSelfOrderMin);
   for (long long lo, hi, step; std::scanf("%lld %lld %lld", &lo, &hi, &step) == 3;)
     for (long long n = lo; n <= hi; n += step) {
       const bool sym = sym_use(k, n, true, march);
@@ -53,7 +53,7 @@ def _ask(ranges, *flags):
 
 
 def constants():
-    return dict(zip(("kSymMinN", "kSymMinNMarch", "kSymT8MinN", "kSymQuadMinTiles"), map(int, _ask([], 0, 0, 0)[0].split())))
+    return dict(zip(("kSymMinN", "kSymMinNMarch", "kSymT8MinN", "kSymQuadMinTiles", "kSelfOrderMin"), map(int, _ask([], 0, 0, 0)[0].split())))
 
 
 def rule(sizes, march=False, t8_switch=None, first_quad=False):
