@@ -743,6 +743,31 @@ int ludvm_vorticity_f32(ludvm_ctx* ctx, const float* u, const float* w, size_t n
 int ludvm_vorticity_dev_f32(ludvm_ctx* ctx, const float* d_u, const float* d_w, size_t nx, size_t nz, float dr,
                             float* d_ome);
 
+/* ---- stream function and analytic vorticity (an addition to ABI 7: detect it by symbol) --------------------------
+ * Two scalar pair sums over the sources of the velocity sum (LUDVM.py:565-566), in float64 throughout.  For a target p and a
+ * source j of circulation G_j: dx = xp - xj, dz = zp - zj, r2 = dx^2 + dz^2, s = sqrt(r2^2 + vcore^4) (the velocity sum's
+ * denominator), a = (r2 + s) / 2, and
+ *     LUDVM_FIELD_PSI:    psi(p)   = sum_j G_j / (4 pi) * ln(a_pj)
+ *     LUDVM_FIELD_OMEGA:  omega(p) = -sum_j G_j * vcore^4 / (pi * s_pj^3)
+ * d psi / dz = u and -d psi / dx = w of LUDVM.py:565-568 exactly; omega = dw/dx - du/dz of that field in closed form, with the
+ * sign of the finite-difference ome_ff (LUDVM.py:1224-1292: a positive circulation turns clockwise, hence the minus), but
+ * needing no grid.  vcore = 0 (inviscid): psi is the point
+ * vortex's G / (2 pi) ln r in the same gauge and omega is 0.  A target on top of a source is finite when vcore > 0 (the term
+ * is ln(vcore^2 / 2)); with vcore = 0 that pair gives what IEEE arithmetic gives (psi: -/+ inf or NaN, omega: NaN).
+ * The sources are walked in the given order, in splits planned like the float64 velocity sum's and added in split order: the
+ * results do not depend on how many workgroups ran.  Host arrays in and out; out has nt values.  nt = 0 is a no-op, ns = 0
+ * writes zeros; an unknown kind or a null array with a non-zero count is LUDVM_E_ARG. */
+enum { LUDVM_FIELD_PSI = 0, LUDVM_FIELD_OMEGA = 1 };
+int ludvm_scalar_f64(ludvm_ctx* ctx, int kind, const double* xs, const double* zs, const double* gs, size_t ns,
+                     const double* xt, const double* zt, size_t nt, double vcore, double* out);
+/* The same sum on rows [row_first, row_first + row_count) of the grid of LUDVM.flowfield (LUDVM.py:1186-1298; the mesh of
+ * ludvm_flowfield_rows_f64: point (i, j) = (xmin + i dr, zmin + j dr), index i nz + j), generated on the device, each coordinate by one fused multiply-add (one rounding).  out is a
+ * host array of row_count * nz.  A block of rows is planned from the whole grid and carries the whole-grid call's bits.
+ * row_count = 0 or nz = 0 is a no-op; rows outside the grid are LUDVM_E_ARG. */
+int ludvm_flowfield_scalar_rows_f64(ludvm_ctx* ctx, int kind, double xmin, double zmin, double dr, size_t nx, size_t nz,
+                                    size_t row_first, size_t row_count, const double* xs, const double* zs,
+                                    const double* gs, size_t ns, double vcore, double* out);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Probe of the symmetric kernel's fixed-point accumulation (the order-independent sums behind the roll-up of

@@ -43,6 +43,7 @@ TRACER_PRECISIONS = {"f64": 0, "f32x2": 2}   # ludvm_march_set_tracer_precision 
 TRACER_F32X2_PER_LANE = 4  # kTracerF32PerLane (csrc/march_kernels.hpp): the hi+lo fp32 tracer kernel's tile is 256 lanes x this
 SURVEY_F32_PER_LANE = 4  # kSurveyF32PerLane (csrc/march_kernels.hpp): the fp32 survey kernel's point tile is 256 lanes x this
 SYM_SCALE_BYTES = 32
+FIELD_KINDS = {"psi": 0, "omega": 1}   # LUDVM_FIELD_PSI, LUDVM_FIELD_OMEGA (ludvm_scalar_f64, ludvm_flowfield_scalar_rows_f64)
 
 _pd, _pf = POINTER(c_double), POINTER(c_float)
 
@@ -137,6 +138,9 @@ SIGNATURES = {
                                 c_void_p, c_size_t, c_float, c_void_p, c_void_p],
     "ludvm_vorticity_f32": [c_void_p, _pf, _pf, c_size_t, c_size_t, c_double, _pf],
     "ludvm_vorticity_dev_f32": [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_float, c_void_p],
+    "ludvm_scalar_f64": [c_void_p, c_int, _pd, _pd, _pd, c_size_t, _pd, _pd, c_size_t, c_double, _pd],
+    "ludvm_flowfield_scalar_rows_f64": [c_void_p, c_int, c_double, c_double, c_double, c_size_t, c_size_t, c_size_t, c_size_t,
+                                        _pd, _pd, _pd, c_size_t, c_double, _pd],
     "ludvm_fixed_point_probe": [c_void_p, _pf, c_size_t, c_int, POINTER(c_longlong)],
     "ludvm_kernel_timing": [c_void_p, c_int],
     "ludvm_kernel_time_ms": [c_void_p, c_int, POINTER(c_double), POINTER(c_longlong)],
@@ -146,7 +150,7 @@ SIGNATURES = {
 ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm_march_read_tracers", "ludvm_march_tracer_state",
                   "ludvm_ensemble_run_traced", "ludvm_march_set_survey", "ludvm_march_read_survey", "ludvm_ensemble_run_surveyed",
                   "ludvm_march_set_survey_precision", "ludvm_march_set_tracer_precision", "ludvm_march_set_survey_bins",
-                  "ludvm_march_read_survey_bins")
+                  "ludvm_march_read_survey_bins", "ludvm_scalar_f64", "ludvm_flowfield_scalar_rows_f64")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -1,5 +1,6 @@
-// O(N) kernels of the flow field (flowfield.hip): source staging conversions and the vorticity stencil of LUDVM.flowfield
-// (LUDVM.py:1224-1292).  Non-template kernels: this header belongs to ONE translation unit (flowfield.hip).
+// Kernels of the flow field (flowfield.hip): source staging conversions, the vorticity stencil of LUDVM.flowfield
+// (LUDVM.py:1224-1292), and the scalar pair sums (stream function, analytic vorticity).  Non-template kernels: this header
+// belongs to ONE translation unit (flowfield.hip).
 #pragma once
 #include "pair_kernels.hpp"
 #include "pair_sym_kernels.hpp"
@@ -73,6 +74,123 @@ vorticity_f64(const double* u, const double* w, long long nx, long long nz, long
   const double dw = w[ip * nz + j] - w[im * nz + j];
   const double du = u[i * nz + jp] - u[i * nz + jm];
   ome[p] = dw / dxm - du / dzm;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Scalar pair sums over the sources of the velocity sum (LUDVM.py:565-566), float64 throughout: with r2 = dx^2 + dz^2,
+// q = r2^2 + vc^4 (pair_f64's q), s = sqrt(q) and a = (r2 + s) / 2,
+//     PSI:    psi(p)   = sum_j G_j / (4 pi) ln(a_pj)        (d psi / dz = u, -d psi / dx = w of pair_f64)
+//     OMEGA:  omega(p) = -sum_j G_j vc^4 / (pi s_pj^3)      (dw/dx - du/dz of that field in closed form: a positive circulation
+//                                                            turns clockwise, LUDVM.py:565-566)
+// The shape of pair_f64: sources in LDS tiles, one target per lane (arrays, or grid points generated in registers), source
+// splits over blockIdx.y into a ONE-column slab [split][nt_pad] that finish_scalar sums in split order.
+// Ragged tiles are NOT padded: pair_f64's far-away source of zero circulation would give 0 * ln(inf) = NaN here, and no pad
+// position is safe for every target when vc = 0 (a target on the pad has a = 0).  The inner loop is bounded by the tile's
+// source count instead (uniform over the workgroup): a slot past the end is neither staged nor read.
+// Per pair: PSI 2 sub, mul, 2 fma, rsq + 2 Newton steps (rsqrt_f64), mul, add, mul, the logarithm (log_f64 below: an fp32
+// logarithm misses the test bound by 4e4), fma; OMEGA the same up to rsqrt_f64, then 2 mul, fma.
+// ---------------------------------------------------------------------------------------------
+enum ScalarKind { kScalarPsi = 0, kScalarOmega = 1 };      // (= LUDVM_FIELD_*, flowfield.hip asserts it)
+constexpr double kInv4PiD = 0.07957747154594766788444;
+constexpr double kInvPiD = 0.31830988618379067153777;
+
+// ln(a) in float64 to < 1 ulp for a >= 0 (-inf at 0; +inf and NaN pass through), in about 40 instructions where OCML's log
+// takes about 90 -- and the logarithm is most of a PSI pair.  The classical form (fdlibm's e_log.c, whose minimax coefficients
+// Lg1 .. Lg7 these are): a = 2^k m with m in [sqrt(1/2), sqrt(2)), f = m - 1, s = f / (2 + f), and
+//   ln m = f - f^2 / 2 + s (f^2 / 2 + R(s^2)),  R(z) = Lg1 z + ... + Lg7 z^7,   ln a = k ln2_hi + (ln m + k ln2_lo).
+// The quotient is v_rcp_f64 refined by two Newton steps and one residual correction, not a division (its scale / fixup
+// steps guard ranges f and 2 + f never leave).  v_frexp_* normalise subnormals themselves.
+__device__ __forceinline__ double log_f64(double a) {
+  double m = __builtin_amdgcn_frexp_mant(a);                // [1/2, 1)
+  int k = __builtin_amdgcn_frexp_exp(a);
+  const bool low = m < 0.70710678118654752440;
+  m = low ? m + m : m;
+  k = low ? k - 1 : k;
+  const double f = m - 1.0, d = 2.0 + f;                    // f in [-0.293, 0.414], d in [1.707, 2.414]
+  double y = __builtin_amdgcn_rcp(d);
+  y = __builtin_fma(y, __builtin_fma(-d, y, 1.0), y);
+  y = __builtin_fma(y, __builtin_fma(-d, y, 1.0), y);
+  double s = f * y;
+  s = __builtin_fma(__builtin_fma(-d, s, f), y, s);
+  const double z = s * s, w = z * z;
+  const double t1 = w * __builtin_fma(w, __builtin_fma(w, 1.531383769920937332e-01, 2.222219843214978396e-01), 3.999999999940941908e-01);
+  const double t2 = z * __builtin_fma(w, __builtin_fma(w, __builtin_fma(w, 1.479819860511658591e-01, 1.818357216161805012e-01),
+                                                       2.857142874366239149e-01), 6.666666666666735130e-01);
+  const double hfsq = 0.5 * f * f, dk = (double)k;
+  const double r = dk * 6.93147180369123816490e-01 -
+                   ((hfsq - __builtin_fma(s, hfsq + (t2 + t1), dk * 1.90821492927058770002e-10)) - f);
+  // (a = 0 leaves a finite r: the -inf is ADDED, so that the compiler keeps one straight line of code for every lane)
+  return (a < __builtin_inf() ? r : a) + (a == 0.0 ? -__builtin_inf() : 0.0);
+}
+
+template <int KIND>
+__device__ __forceinline__ double scalar_term(double dx, double dz, double vc4) {
+  const double r2 = __builtin_fma(dz, dz, dx * dx);
+  const double q = __builtin_fma(r2, r2, vc4);
+  const double y = rsqrt_f64(q);
+  if (KIND == kScalarOmega) return y * y * y;               // s^-3 (the factor -vc^4 / pi: once per target)
+  const double s = q > 0.0 ? q * y : q;                     // sqrt(q); q = 0 (inviscid, coincident): 0, not 0 * inf
+  return log_f64(0.5 * (r2 + s));
+}
+
+template <int KIND, int TILE>
+__global__ void __launch_bounds__(kBlock)
+pair_scalar_f64(PairArgs a) {
+  __shared__ __attribute__((aligned(16))) double lx[TILE];
+  __shared__ __attribute__((aligned(16))) double lz[TILE];
+  __shared__ __attribute__((aligned(16))) double lg[TILE];
+
+  const double* __restrict__ xs = static_cast<const double*>(a.xs);
+  const double* __restrict__ zs = static_cast<const double*>(a.zs);
+  const double* __restrict__ gs = static_cast<const double*>(a.gs);
+
+  const int tid = threadIdx.x;
+  const long long ti = (long long)blockIdx.x * kBlock + tid;
+  const long long s_begin = (long long)blockIdx.y * a.chunk;
+  long long s_end = s_begin + a.chunk;
+  if (s_end > a.ns) s_end = a.ns;
+
+  double xp = 0.0, zp = 0.0;
+  if (ti < a.nt) {
+    if (a.grid_nz > 0) {
+      grid_point(a, ti, xp, zp);
+    } else {
+      xp = static_cast<const double*>(a.xt)[ti];
+      zp = static_cast<const double*>(a.zt)[ti];
+    }
+  }
+  double acc = 0.0;
+  const double vc4 = a.vc4;
+
+  for (long long base = s_begin; base < s_end; base += TILE) {
+    const int cnt = s_end - base < TILE ? (int)(s_end - base) : TILE;      // sources of this tile (uniform)
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < (TILE + kBlock - 1) / kBlock; ++k) {
+      const int l = tid + k * kBlock;
+      if (l < cnt) {
+        lx[l] = xs[base + l];
+        lz[l] = zs[base + l];
+        lg[l] = gs[base + l];
+      }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < cnt; ++j) acc = __builtin_fma(lg[j], scalar_term<KIND>(xp - lx[j], zp - lz[j], vc4), acc);
+  }
+
+  if (ti < a.nt) {
+    const double v = acc * (KIND == kScalarOmega ? -vc4 * kInvPiD : kInv4PiD);
+    if (gridDim.y == 1) static_cast<double*>(a.u)[ti] = v;
+    else static_cast<double*>(a.part)[(long long)blockIdx.y * a.nt_pad + ti] = v;
+  }
+}
+
+// the splits of one target, added in split order in sum_column's fixed association
+__global__ void __launch_bounds__(kBlock)
+finish_scalar(const double* part, long long nt, long long nt_pad, int nsplit, double* out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i < nt) out[i] = sum_column(part + i, nt_pad, nsplit);
 }
 
 }  // namespace ludvm

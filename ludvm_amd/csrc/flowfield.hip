@@ -1,7 +1,8 @@
 // libludvm_hip.so -- C-ABI implementation (see include/ludvm_hip.h for the contract and the reference file:line each entry point
 // replaces; ctx.hpp for how the library is divided into translation units).  gfx950 only; no CPU path: every entry point either
 // runs the HIP kernels or returns an error code.
-// This unit: flow-field grids (LUDVM.flowfield, LUDVM.py:1186-1298) and the vorticity stencil.
+// This unit: flow-field grids (LUDVM.flowfield, LUDVM.py:1186-1298), the vorticity stencil, and the scalar pair sums (stream
+// function, analytic vorticity) at points and on grids.
 #include "ctx.hpp"
 #include "field_kernels.hpp"
 
@@ -215,6 +216,107 @@ int ludvm_vorticity_f32(ludvm_ctx* c, const float* u, const float* w, size_t nx,
   HIPCHK(c, hipMemcpyAsync(ome, dome, nt * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LUDVM_OK;
+}
+
+}  // extern "C"
+
+/* ---- stream function and analytic vorticity -------------------------------------------------- */
+
+static_assert(kScalarPsi == LUDVM_FIELD_PSI && kScalarOmega == LUDVM_FIELD_OMEGA, "the kernels take the ABI's kind codes");
+
+// pair_scalar_f64 + finish_scalar into the device array `out` [a.nt]; a: device sources, targets (arrays or a grid) and
+// vc4 filled in by the caller.  The sources are split as the float64 velocity sum splits them (make_plan: a few targets
+// still fill the device), from plan_nt targets when the launch is a block of rows of a larger grid; the one-column slab
+// [split][nt_pad] lives in c->part.
+static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, double* out) {
+  const Plan p = make_plan(c, a.nt, a.ns, LUDVM_PREC_F64, true, plan_nt);
+  a.chunk = p.chunk;
+  a.nt_pad = p.nt_pad;
+  a.nsplit = p.nsplit;
+  a.u = out;
+  if (p.nsplit > 1) {
+    CHK(ensure(c, c->part, (size_t)p.nsplit * (size_t)p.nt_pad * sizeof(double)));
+    a.part = c->part.p;
+  }
+  void (*kernel)(PairArgs) = nullptr;
+  if (kind == LUDVM_FIELD_PSI) {
+    kernel = p.tile == kTileF64Few ? pair_scalar_f64<kScalarPsi, kTileF64Few> : pair_scalar_f64<kScalarPsi, kTileF64>;
+  } else {
+    kernel = p.tile == kTileF64Few ? pair_scalar_f64<kScalarOmega, kTileF64Few> : pair_scalar_f64<kScalarOmega, kTileF64>;
+  }
+  TimedLaunch t{};
+  bool active = false;
+  CHK(timed_begin(c, t, active));
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(a.nt), (unsigned)p.nsplit), dim3(kBlock), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  CHK(timed_end(c, t, active));
+  if (p.nsplit > 1) {
+    hipLaunchKernelGGL(finish_scalar, dim3(blocks_for(a.nt)), dim3(kBlock), 0, c->stream, static_cast<const double*>(c->part.p),
+                       a.nt, p.nt_pad, p.nsplit, out);
+    HIPCHK(c, hipGetLastError());
+  }
+  return LUDVM_OK;
+}
+
+// Host sources up, the sum over targets `a` describes (array targets are uploaded here), nt results down.
+static int scalar_host(ludvm_ctx* c, int kind, PairArgs a, const double* xs, const double* zs, const double* gs, size_t ns,
+                       const double* xt, const double* zt, size_t nt, size_t plan_nt, double vcore, double* out) {
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->arena, 3 * Arena::need(ns, 8) + 3 * Arena::need(nt, 8)));
+  Arena ar(c->arena.p);
+  double* dout = ar.take<double>(nt);
+  if (ns == 0) {
+    HIPCHK(c, hipMemsetAsync(dout, 0, nt * 8, c->stream));
+  } else {
+    double* dxs = ar.take<double>(ns);
+    double* dzs = ar.take<double>(ns);
+    double* dgs = ar.take<double>(ns);
+    HIPCHK(c, hipMemcpyAsync(dxs, xs, ns * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dzs, zs, ns * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dgs, gs, ns * 8, hipMemcpyHostToDevice, c->stream));
+    if (xt) {
+      double* dxt = ar.take<double>(nt);
+      double* dzt = ar.take<double>(nt);
+      HIPCHK(c, hipMemcpyAsync(dxt, xt, nt * 8, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(dzt, zt, nt * 8, hipMemcpyHostToDevice, c->stream));
+      a.xt = dxt; a.zt = dzt;
+    }
+    a.xs = dxs; a.zs = dzs; a.gs = dgs; a.ns = (long long)ns;
+    a.nt = (long long)nt;
+    const double v2 = vcore * vcore;
+    a.vc4 = v2 * v2;
+    CHK(scalar_device(c, kind, a, (long long)plan_nt, dout));
+  }
+  HIPCHK(c, hipMemcpyAsync(out, dout, nt * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LUDVM_OK;
+}
+
+extern "C" {
+
+int ludvm_scalar_f64(ludvm_ctx* c, int kind, const double* xs, const double* zs, const double* gs, size_t ns, const double* xt,
+                     const double* zt, size_t nt, double vcore, double* out) {
+  if (!c) return LUDVM_E_ARG;
+  if (kind != LUDVM_FIELD_PSI && kind != LUDVM_FIELD_OMEGA) return fail(c, LUDVM_E_ARG, "unknown field kind");
+  if (nt == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !xt || !zt || !out) return fail(c, LUDVM_E_ARG, "null array");
+  return scalar_host(c, kind, PairArgs{}, xs, zs, gs, ns, xt, zt, nt, nt, vcore, out);
+}
+
+int ludvm_flowfield_scalar_rows_f64(ludvm_ctx* c, int kind, double xmin, double zmin, double dr, size_t nx, size_t nz,
+                                    size_t row_first, size_t row_count, const double* xs, const double* zs, const double* gs,
+                                    size_t ns, double vcore, double* out) {
+  if (!c) return LUDVM_E_ARG;
+  if (kind != LUDVM_FIELD_PSI && kind != LUDVM_FIELD_OMEGA) return fail(c, LUDVM_E_ARG, "unknown field kind");
+  if (row_first > nx || row_count > nx - row_first) return fail(c, LUDVM_E_ARG, "rows outside the grid");
+  if (row_count == 0 || nz == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !out) return fail(c, LUDVM_E_ARG, "null array");
+  PairArgs a{};
+  a.grid_nz = (long long)nz;
+  a.grid_row0 = (long long)row_first;
+  a.xmin = xmin; a.zmin = zmin; a.dr = dr;
+  // (planned for the whole grid: a block of rows is then bit for bit what the whole-grid call computes for them)
+  return scalar_host(c, kind, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, out);
 }
 
 }  // extern "C"

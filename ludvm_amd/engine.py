@@ -742,6 +742,47 @@ class Engine:
     def vorticity_dev(self, d_u, d_w, nx, nz, dr, d_ome):
         self._check(self._lib.ludvm_vorticity_dev_f32(self._ctx, d_u, d_w, int(nx), int(nz), float(dr), d_ome))
 
+    # -- stream function and analytic vorticity ---------------------------------------------------
+    def _field_kind(self, kind, fn):
+        if not hasattr(self._lib, fn):
+            raise LudvmHipError(_ffi.E_STATE, f"this build of the library has no {fn}")
+        code = _ffi.FIELD_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+        if isinstance(code, bool) or not isinstance(code, int):
+            raise ValueError("kind: 'psi' or 'omega' (or the library's code)")
+        return code
+
+    def scalar_field(self, kind, circulation, xw, zw, xp, zp, v_core):
+        """float64 [Np]: the stream function (kind 'psi': sum G / (4 pi) ln((r^2 + s) / 2), s = sqrt(r^4 + v_core^4), whose z and
+        -x derivatives are `induce`'s u and w) or the core model's vorticity (kind 'omega': dw/dx - du/dz of that
+        velocity in closed form, -sum G v_core^4 / (pi s^3)) of the
+        vortices at the points, in float64 throughout (ludvm_scalar_f64)."""
+        code = self._field_kind(kind, "ludvm_scalar_f64")
+        g, xs, zs, xt, zt = _f64(circulation), _f64(xw), _f64(zw), _f64(xp), _f64(zp)
+        if not (len(g) == len(xs) == len(zs)) or len(xt) != len(zt):
+            raise ValueError("scalar_field: source arrays (and target arrays) must have equal lengths")
+        out = np.empty(len(xt))
+        self._check(self._lib.ludvm_scalar_f64(self._ctx, code, _pd(xs), _pd(zs), _pd(g), len(xs), _pd(xt), _pd(zt), len(xt),
+                                               float(v_core), _pd(out)))
+        return out
+
+    def flowfield_scalar(self, kind, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core, row_first=0, row_count=None):
+        """float64 [row_count, nz]: `scalar_field` on rows [row_first, row_first + row_count) of the flow-field grid
+        (xmin + i*dr, zmin + j*dr), generated on the device; every row by default.  A block of rows carries the whole-grid
+        call's bits (ludvm_flowfield_scalar_rows_f64)."""
+        code = self._field_kind(kind, "ludvm_flowfield_scalar_rows_f64")
+        g, xs, zs = _f64(circulation), _f64(xw), _f64(zw)
+        if not (len(g) == len(xs) == len(zs)):
+            raise ValueError("flowfield_scalar: source arrays must have equal lengths")
+        nx, nz, row_first = int(nx), int(nz), int(row_first)
+        row_count = nx - row_first if row_count is None else int(row_count)
+        if nx < 0 or nz < 0 or row_first < 0 or row_count < 0:
+            raise ValueError("flowfield_scalar: nx, nz, row_first and row_count must not be negative")
+        out = np.empty(max(row_count, 0) * nz)
+        self._check(self._lib.ludvm_flowfield_scalar_rows_f64(self._ctx, code, float(xmin), float(zmin), float(dr), nx, nz,
+                                                              row_first, row_count, _pd(xs), _pd(zs), _pd(g), len(xs),
+                                                              float(v_core), _pd(out)))
+        return out.reshape(row_count, nz)
+
     def fixed_point_probe(self, values, scale_log2):
         """int64 units the symmetric kernel adds to an accumulator for fp32 partial sums `values` at scale
         2**scale_log2 (ludvm_fixed_point_probe): trunc(value * scale), exact below 2**63."""

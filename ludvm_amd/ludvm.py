@@ -686,6 +686,29 @@ class LUDVM:
             return np.ascontiguousarray(uw[:, 0]), np.ascontiguousarray(uw[:, 1])
         return self.engine.induce(circulation, xw, zw, xp, zp, v_core, precision=self.precision)
 
+    def _scalar_field(self, kind, what, circulation, xw, zw, xp, zp, viscous):
+        if self._shard is not None and self._shard.world > 1:
+            raise ValueError(f"{what} runs on one GPU: not with `distributed` or more than one device in `devices`")
+        if not hasattr(self.engine, 'scalar_field'):
+            raise RuntimeError(f"{what}: this engine has no scalar_field")
+        v_core = self.v_core if viscous == True else 0  # noqa: E712  (as induced_velocity)
+        return self.engine.scalar_field(kind, circulation, xw, zw, xp, zp, v_core)
+
+    def stream_function(self, circulation, xw, zw, xp, zp, viscous=True):
+        """Stream function psi at points (xp, zp) of vortices (circulation, xw, zw), the arguments of `induced_velocity`:
+        psi = sum G / (4 pi) ln((r^2 + s) / 2) with s = sqrt(r^4 + v_core^4), so that d psi / dz = u and -d psi / dx = w of
+        `induced_velocity` exactly (LUDVM.py:565-568); with `viscous=False` the point vortex's G / (2 pi) ln r in the same
+        gauge.  One new float64 array, evaluated on the GPU in float64 whatever the run's `precision`.  A point on top of a
+        vortex is finite with a core (that term is ln(v_core^2 / 2)) and IEEE's -/+ inf or NaN without one."""
+        return self._scalar_field('psi', 'the stream function', circulation, xw, zw, xp, zp, viscous)
+
+    def vorticity(self, circulation, xw, zw, xp, zp, viscous=True):
+        """Vorticity omega = dw/dx - du/dz at points (xp, zp) of the velocity field `induced_velocity` gives for vortices
+        (circulation, xw, zw), in closed form: -sum G v_core^4 / (pi s^3), s = sqrt(r^4 + v_core^4) -- the sign convention of
+        `ome_ff`, no grid and no differences.  One new float64 array, float64 on the GPU whatever the run's `precision`; 0
+        with `viscous=False` (NaN at a point on top of a vortex)."""
+        return self._scalar_field('omega', 'the analytic vorticity', circulation, xw, zw, xp, zp, viscous)
+
     def _chord_frame(self, u1, w1, i):
         a = self.alpha[i]
         return u1 * np.cos(a) - w1 * np.sin(a), u1 * np.sin(a) + w1 * np.cos(a)
@@ -1651,7 +1674,7 @@ class LUDVM:
         LUDVM(..., snapshot_steps=LUDVM.flowfield_rows_needed(tsteps))."""
         return sorted({r for s in tsteps for r in ((int(s) - 1, int(s)) if int(s) > 0 else (0,))})
 
-    def flowfield(self, xmin=-10, xmax=0, zmin=-4, zmax=4, dr=0.02, tsteps=[0, 1, 2]):
+    def flowfield(self, xmin=-10, xmax=0, zmin=-4, zmax=4, dr=0.02, tsteps=[0, 1, 2], psi=False, omega=False):
         """Velocity and vorticity on the uniform mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr)
         at the requested time steps (LUDVM.py:1186-1298).  The mesh points are generated on the
         device (x-major, as meshgrid(indexing='ij') ravels, :1194-1195); wake and bound vortices go in
@@ -1659,7 +1682,18 @@ class LUDVM:
         are, and the three fields come back together.  A run in precision 'f64' (what 'auto' picks for every case whose
         dense history the reference itself could hold) evaluates the field in float64 throughout, as the reference does
         (:1206, :1216-1217): u_ff, w_ff and ome_ff then equal the reference's to rounding; 'f32' / 'f32x2' runs evaluate
-        it in fp32 on local-origin sources (~1e-6 of max|u|; the stencil amplifies that by 1 / (2 dr) in ome_ff)."""
+        it in fp32 on local-origin sources (~1e-6 of max|u|; the stencil amplifies that by 1 / (2 dr) in ome_ff).
+        `psi=True` / `omega=True` add `psi_ff` / `omega_ff` [nsteps, nx, nz] from the same sources on the same mesh: the stream
+        function whose contours are the streamlines (of the induced velocity, the fluid far away at rest; `psi_ff + Uinf * z_ff`
+        in the frame that translates with the foil, a wind tunnel's) and the core model's vorticity in closed form
+        (`stream_function`, `vorticity`) -- float64 whatever the run's precision, and, unlike the stencil's ome_ff, resolved at
+        any dr.  One GPU only; u_ff, w_ff and ome_ff are what they are without the flags."""
+        scalars = [kind for kind, on in (('psi', psi), ('omega', omega)) if on]
+        if scalars:
+            if self._shard is not None and self._shard.world > 1:
+                raise ValueError("psi / omega fields run on one GPU: not with `distributed` or more than one device in `devices`")
+            if not hasattr(self.engine, 'flowfield_scalar'):
+                raise RuntimeError("flowfield(psi=..., omega=...): this engine has no flowfield_scalar")
         x1, z1 = np.arange(xmin, xmax, dr), np.arange(zmin, zmax, dr)
         nx, nz = len(x1), len(z1)
         x, z = np.meshgrid(x1, z1, indexing='ij')
@@ -1667,6 +1701,7 @@ class LUDVM:
         u = np.zeros([nsteps, nx, nz])
         w = np.zeros([nsteps, nx, nz])
         ome = np.zeros([nsteps, nx, nz])
+        extra = {kind: np.zeros([nsteps, nx, nz]) for kind in scalars}
         fused = hasattr(self.engine, 'flowfield_vorticity')
         sh = self._shard if (self._shard is not None and self._shard.world > 1) else None
         ffp = 'f64' if self.precision == 'f64' else 'f32'
@@ -1700,7 +1735,13 @@ class LUDVM:
                 uf, wf = self.engine.flowfield(xmin, zmin, dr, nx, nz, g, xw, zw, self.v_core)
                 u[ii], w[ii] = uf, wf
                 ome[ii] = self.engine.vorticity(uf, wf, dr)
+            for kind in scalars:
+                extra[kind][ii] = self.engine.flowfield_scalar(kind, xmin, zmin, dr, nx, nz, g, xw, zw, self.v_core)
         self.x_ff, self.z_ff = x, z
         self.u_ff, self.w_ff = u, w
         self.ome_ff = ome
+        if psi:
+            self.psi_ff = extra['psi']
+        if omega:
+            self.omega_ff = extra['omega']
         return None
