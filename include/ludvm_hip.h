@@ -459,6 +459,31 @@ int ludvm_march_tracer_state(ludvm_ctx* ctx, double* x, double* z);
  *   precision is 0 enqueues exactly what it enqueued before this entry existed. */
 int ludvm_march_set_tracer_precision(ludvm_ctx* ctx, int precision);
 
+/* ---- the tracers' deformation gradient (an addition to ABI 7: detect it by symbol) -------------------------------
+ *
+ * The sources of a step do not depend on a tracer, so the exact derivative of a released tracer's discrete map
+ * start -> start + dt (u, w)_i(start) (LUDVM.py:1120-1127's forward-Euler step) with respect to its seed (X, Z) is one 2 x 2
+ * product per step,  F <- (I + dt G_i(start)) F,  G_i = grad (u, w)_i in the closed form of ludvm_gradient_f64 (below) over the
+ * step's sources.  F = [[dx/dX, dx/dZ], [dz/dX, dz/dZ]] is carried as four arrays F11 | F12 | F21 | F22; it is the identity while
+ * a tracer is held and is reset to the identity at its release step.  The finite-time Lyapunov exponent of the flow map is
+ * ln sigma_max(F) / T with T = dt (step - release + 1).
+ *
+ * ludvm_march_set_tracer_gradient: on = 1 makes the marched steps carry F (float64 tracers only: LUDVM_E_STATE while the
+ *   tracer precision is 2, and ludvm_march_set_tracer_precision then refuses 2); F is [4][count], or NULL for the identity (a run
+ *   that is continued gives what ludvm_march_tracer_gradient_state returned).  on = 0 stops it.  Valid only while tracers are set
+ *   (LUDVM_E_STATE otherwise); a flag other than 0 and 1 or an F that is not finite is LUDVM_E_ARG and changes nothing.
+ *   ludvm_march_set_tracers and ludvm_march_setup reset it to off.
+ * ludvm_march_read_tracer_gradient: the F rows of the steps ludvm_march_read_tracers returns for the last ludvm_march_run call,
+ *   F [rows][4][count]; rows_cap, steps_out, nrows_out and the error codes as there (LUDVM_E_STATE also when the gradient is
+ *   off or was switched on after that call).
+ * ludvm_march_tracer_gradient_state: the current F [4][count].
+ * Guarantee: the tracer positions and every other result of ludvm_march_run keep their bits (the gradient kernels run under the
+ *   plain float64 tracers' launch plan and do their arithmetic for u and w operation for operation); F repeats bit for bit
+ *   however a run is cut into calls; a context without the flag enqueues exactly what it enqueued before this entry existed. */
+int ludvm_march_set_tracer_gradient(ludvm_ctx* ctx, int on, const double* F);
+int ludvm_march_read_tracer_gradient(ludvm_ctx* ctx, double* F, size_t rows_cap, long long* steps_out, size_t* nrows_out);
+int ludvm_march_tracer_gradient_state(ludvm_ctx* ctx, double* F);
+
 /* ---- wake survey: running field moments inside the march (an addition to ABI 7: detect it by symbol) -----------
  *
  * The time-averaged wake on a survey grid without a time series: for survey point p, (u, w)_i(p) is EXACTLY the probes'
@@ -767,6 +792,28 @@ int ludvm_scalar_f64(ludvm_ctx* ctx, int kind, const double* xs, const double* z
 int ludvm_flowfield_scalar_rows_f64(ludvm_ctx* ctx, int kind, double xmin, double zmin, double dr, size_t nx, size_t nz,
                                     size_t row_first, size_t row_count, const double* xs, const double* zs,
                                     const double* gs, size_t ns, double vcore, double* out);
+
+/* ---- velocity gradient (an addition to ABI 7: detect it by symbol) -------------------------------------------------
+ * The gradient of the velocity sum (LUDVM.py:565-568) in closed form, in float64 throughout.  With dx, dz, r2 and s as above and
+ * y = 1 / s, three raw sums per target
+ *     A = sum_j G_j r2 dx dz y^3,    B = sum_j G_j r2 (dx^2 - dz^2) y^3,    C = sum_j G_j y^3
+ * give
+ *     ux = du/dx = -A / pi                  (dw/dz = -ux: the field is divergence free)
+ *     uz = du/dz = (B + vcore^4 C) / (2 pi)
+ *     wx = dw/dx = (B - vcore^4 C) / (2 pi)
+ * so that wx - uz is LUDVM_FIELD_OMEGA exactly, and Q = det grad u = -ux^2 - uz wx = omega^2 / 4 - (strain rate)^2 is positive in
+ * a vortex core and negative in a shear layer.  One walk over the sources serves the three sums.  A target on top of a source
+ * gives ux = 0, uz = -wx = G / (2 pi vcore^2) from that pair when vcore > 0, and IEEE's NaN when vcore = 0.  Splits, order and
+ * reproducibility as ludvm_scalar_f64; host arrays in and out, ux, uz, wx of nt values each.  nt = 0 is a no-op, ns = 0 writes
+ * zeros; a null array with a non-zero count is LUDVM_E_ARG. */
+int ludvm_gradient_f64(ludvm_ctx* ctx, const double* xs, const double* zs, const double* gs, size_t ns, const double* xt,
+                       const double* zt, size_t nt, double vcore, double* ux, double* uz, double* wx);
+/* The same sums on rows [row_first, row_first + row_count) of the grid of LUDVM.flowfield (LUDVM.py:1186-1298), the mesh and
+ * the rules of ludvm_flowfield_scalar_rows_f64: ux, uz, wx are host arrays of row_count * nz; a block of rows is planned from the
+ * whole grid and carries the whole-grid call's bits. */
+int ludvm_flowfield_gradient_rows_f64(ludvm_ctx* ctx, double xmin, double zmin, double dr, size_t nx, size_t nz,
+                                      size_t row_first, size_t row_count, const double* xs, const double* zs,
+                                      const double* gs, size_t ns, double vcore, double* ux, double* uz, double* wx);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

@@ -110,6 +110,9 @@ SIGNATURES = {
     "ludvm_march_set_survey_bins": [c_void_p, POINTER(c_int), c_size_t, c_int, _pd, POINTER(c_longlong)],
     "ludvm_march_read_survey_bins": [c_void_p, _pd, POINTER(c_longlong)],
     "ludvm_march_set_tracer_precision": [c_void_p, c_int],
+    "ludvm_march_set_tracer_gradient": [c_void_p, c_int, _pd],
+    "ludvm_march_read_tracer_gradient": [c_void_p, _pd, c_size_t, POINTER(c_longlong), POINTER(c_size_t)],
+    "ludvm_march_tracer_gradient_state": [c_void_p, _pd],
     "ludvm_ensemble_limits": [c_void_p, POINTER(c_longlong)],
     "ludvm_ensemble_run": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
                            POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
@@ -141,6 +144,9 @@ SIGNATURES = {
     "ludvm_scalar_f64": [c_void_p, c_int, _pd, _pd, _pd, c_size_t, _pd, _pd, c_size_t, c_double, _pd],
     "ludvm_flowfield_scalar_rows_f64": [c_void_p, c_int, c_double, c_double, c_double, c_size_t, c_size_t, c_size_t, c_size_t,
                                         _pd, _pd, _pd, c_size_t, c_double, _pd],
+    "ludvm_gradient_f64": [c_void_p, _pd, _pd, _pd, c_size_t, _pd, _pd, c_size_t, c_double, _pd, _pd, _pd],
+    "ludvm_flowfield_gradient_rows_f64": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, c_size_t, c_size_t,
+                                          _pd, _pd, _pd, c_size_t, c_double, _pd, _pd, _pd],
     "ludvm_fixed_point_probe": [c_void_p, _pf, c_size_t, c_int, POINTER(c_longlong)],
     "ludvm_kernel_timing": [c_void_p, c_int],
     "ludvm_kernel_time_ms": [c_void_p, c_int, POINTER(c_double), POINTER(c_longlong)],
@@ -150,7 +156,9 @@ SIGNATURES = {
 ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm_march_read_tracers", "ludvm_march_tracer_state",
                   "ludvm_ensemble_run_traced", "ludvm_march_set_survey", "ludvm_march_read_survey", "ludvm_ensemble_run_surveyed",
                   "ludvm_march_set_survey_precision", "ludvm_march_set_tracer_precision", "ludvm_march_set_survey_bins",
-                  "ludvm_march_read_survey_bins", "ludvm_scalar_f64", "ludvm_flowfield_scalar_rows_f64")
+                  "ludvm_march_read_survey_bins", "ludvm_scalar_f64", "ludvm_flowfield_scalar_rows_f64",
+                  "ludvm_gradient_f64", "ludvm_flowfield_gradient_rows_f64", "ludvm_march_set_tracer_gradient",
+                  "ludvm_march_read_tracer_gradient", "ludvm_march_tracer_gradient_state")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -121,7 +121,8 @@ int ludvm_destroy(ludvm_ctx* c) {
   void* bufs[] = {c->part.p, c->acc.p, c->symsc.p, c->arena.p, c->orderws.p, c->x64, c->z64, c->g64, c->xh, c->xl, c->zh, c->zl, c->g32,
                   c->xr, c->zr, c->cx, c->cz, c->march_tab.p, c->march_kin.p, c->march_rows.p, c->march_state.p, c->march_hist.p,
                   c->probe_xz.p, c->probe_shift.p, c->probe_part.p, c->probe_out.p, c->tracer_seed.p, c->tracer_release.p,
-                  c->tracer_shift.p, c->tracer_cur.p, c->tracer_part.p, c->tracer_out.p, c->survey_xz.p, c->survey_shift.p, c->survey_sums.p,
+                  c->tracer_shift.p, c->tracer_cur.p, c->tracer_part.p, c->tracer_out.p, c->tracer_F.p, c->tracer_grad_part.p,
+                  c->tracer_F_out.p, c->survey_xz.p, c->survey_shift.p, c->survey_sums.p,
                   c->survey_part.p, c->survey_bin_sums.p, c->ens_in.p, c->ens_work.p, c->ens_out.p};
   for (void* p : bufs)
     if (p) (void)hipFree(p);

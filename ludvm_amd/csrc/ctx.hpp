@@ -125,6 +125,11 @@ struct ludvm_ctx {
   std::vector<long long> tracer_record;        // steps whose rows are recorded, ascending
   std::vector<long long> tracer_rows;          // the recorded steps of the last ludvm_march_run call
   int tracer_precision = 0;                    // 0: float64 pair sums; 2: hi+lo fp32 (ludvm_march_set_tracer_precision)
+  // the tracers' deformation gradient (ludvm_march_set_tracer_gradient): resident F11 | F12 | F21 | F22 [M], the five-column
+  // slab of the gradient kernels, and the F rows of the last ludvm_march_run call [rows][4][M]
+  Buf tracer_F, tracer_grad_part, tracer_F_out;
+  bool tracer_gradient = false;
+  bool tracer_grad_ran = false;                // the last ludvm_march_run call succeeded with the gradient on
   // wake survey of the march (ludvm_march_set_survey): points x[K] | z[K], the per-step x offsets, the five raw sums
   // [5][K], the partial slabs of one sampled step -- buffers of the survey's own, like the probes' and the tracers'
   Buf survey_xz, survey_shift, survey_sums, survey_part;

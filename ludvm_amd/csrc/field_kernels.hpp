@@ -1,5 +1,5 @@
 // Kernels of the flow field (flowfield.hip): source staging conversions, the vorticity stencil of LUDVM.flowfield
-// (LUDVM.py:1224-1292), and the scalar pair sums (stream function, analytic vorticity).  Non-template kernels: this header
+// (LUDVM.py:1224-1292), the scalar pair sums (stream function, analytic vorticity) and the velocity gradient.  Non-template kernels: this header
 // belongs to ONE translation unit (flowfield.hip).
 #pragma once
 #include "pair_kernels.hpp"
@@ -91,8 +91,7 @@ vorticity_f64(const double* u, const double* w, long long nx, long long nz, long
 // logarithm misses the test bound by 4e4), fma; OMEGA the same up to rsqrt_f64, then 2 mul, fma.
 // ---------------------------------------------------------------------------------------------
 enum ScalarKind { kScalarPsi = 0, kScalarOmega = 1 };      // (= LUDVM_FIELD_*, flowfield.hip asserts it)
-constexpr double kInv4PiD = 0.07957747154594766788444;
-constexpr double kInvPiD = 0.31830988618379067153777;
+constexpr double kInv4PiD = 0.07957747154594766788444;      // (kInvPiD: pair_kernels.hpp)
 
 // ln(a) in float64 to < 1 ulp for a >= 0 (-inf at 0; +inf and NaN pass through), in about 40 instructions where OCML's log
 // takes about 90 -- and the logarithm is most of a PSI pair.  The classical form (fdlibm's e_log.c, whose minimax coefficients
@@ -191,6 +190,104 @@ __global__ void __launch_bounds__(kBlock)
 finish_scalar(const double* part, long long nt, long long nt_pad, int nsplit, double* out) {
   const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (i < nt) out[i] = sum_column(part + i, nt_pad, nsplit);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Velocity gradient of the same field, float64 throughout: with y = 1 / s, three raw sums per target
+//     A = sum G r2 dx dz y^3,   B = sum G r2 (dx^2 - dz^2) y^3,   C = sum G y^3
+// give  du/dx = -A / pi (= -dw/dz: the field is divergence free),  du/dz = (B + vc^4 C) / (2 pi),
+//       dw/dx = (B - vc^4 C) / (2 pi),  so that dw/dx - du/dz = -vc^4 C / pi is OMEGA above exactly.
+// pair_scalar_f64's shape: one walk over the sources with three accumulators per target (one reciprocal square root per
+// pair serves all three), the ragged tile bounded by its count (with vc = 0 no pad position is safe for every target), source
+// splits into a THREE-column slab [split][3][nt_pad] of the raw sums that finish_grad adds in split order.  The outputs are
+// formed once per target, by grad_outputs in both routes; `out` is [3][nt]: du/dx, du/dz, dw/dx.
+// Per pair: 2 sub, mul, 2 fma, rsqrt_f64, 2 mul (y^3), mul (G y^3), add, mul (r2), mul (dx dz), fma (dx^2 - dz^2), 2 fma.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void grad_outputs(double A, double B, double C, double vc4, long long stride, double* out) {
+  const double vC = vc4 * C;
+  out[0] = -A * kInvPiD;
+  out[stride] = (B + vC) * kInv2PiD;
+  out[2 * stride] = (B - vC) * kInv2PiD;
+}
+
+template <int TILE>
+__global__ void __launch_bounds__(kBlock)
+pair_grad_f64(PairArgs a) {
+  __shared__ __attribute__((aligned(16))) double lx[TILE];
+  __shared__ __attribute__((aligned(16))) double lz[TILE];
+  __shared__ __attribute__((aligned(16))) double lg[TILE];
+
+  const double* __restrict__ xs = static_cast<const double*>(a.xs);
+  const double* __restrict__ zs = static_cast<const double*>(a.zs);
+  const double* __restrict__ gs = static_cast<const double*>(a.gs);
+
+  const int tid = threadIdx.x;
+  const long long ti = (long long)blockIdx.x * kBlock + tid;
+  const long long s_begin = (long long)blockIdx.y * a.chunk;
+  long long s_end = s_begin + a.chunk;
+  if (s_end > a.ns) s_end = a.ns;
+
+  double xp = 0.0, zp = 0.0;
+  if (ti < a.nt) {
+    if (a.grid_nz > 0) {
+      grid_point(a, ti, xp, zp);
+    } else {
+      xp = static_cast<const double*>(a.xt)[ti];
+      zp = static_cast<const double*>(a.zt)[ti];
+    }
+  }
+  double sa = 0.0, sb = 0.0, sc = 0.0;
+  const double vc4 = a.vc4;
+
+  for (long long base = s_begin; base < s_end; base += TILE) {
+    const int cnt = s_end - base < TILE ? (int)(s_end - base) : TILE;      // sources of this tile (uniform)
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < (TILE + kBlock - 1) / kBlock; ++k) {
+      const int l = tid + k * kBlock;
+      if (l < cnt) {
+        lx[l] = xs[base + l];
+        lz[l] = zs[base + l];
+        lg[l] = gs[base + l];
+      }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < cnt; ++j) {
+      const double dx = xp - lx[j];
+      const double dz = zp - lz[j];
+      const double dxx = dx * dx;
+      const double r2 = __builtin_fma(dz, dz, dxx);
+      const double q = __builtin_fma(r2, r2, vc4);
+      const double y = rsqrt_f64(q);
+      const double c = lg[j] * (y * y * y);                 // G / s^3
+      const double e = c * r2;
+      sc += c;
+      sa = __builtin_fma(e, dx * dz, sa);
+      sb = __builtin_fma(e, __builtin_fma(-dz, dz, dxx), sb);
+    }
+  }
+
+  if (ti < a.nt) {
+    if (gridDim.y == 1) {
+      grad_outputs(sa, sb, sc, vc4, a.nt, static_cast<double*>(a.u) + ti);
+    } else {
+      double* row = static_cast<double*>(a.part) + (long long)blockIdx.y * 3 * a.nt_pad + ti;
+      row[0] = sa;
+      row[a.nt_pad] = sb;
+      row[2 * a.nt_pad] = sc;
+    }
+  }
+}
+
+// the three raw sums of one target, each added in split order in sum_column's fixed association, then the outputs
+__global__ void __launch_bounds__(kBlock)
+finish_grad(const double* part, long long nt, long long nt_pad, int nsplit, double vc4, double* out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= nt) return;
+  const double* col = part + i;
+  grad_outputs(sum_column(col, 3 * nt_pad, nsplit), sum_column(col + nt_pad, 3 * nt_pad, nsplit),
+               sum_column(col + 2 * nt_pad, 3 * nt_pad, nsplit), vc4, nt, out + i);
 }
 
 }  // namespace ludvm

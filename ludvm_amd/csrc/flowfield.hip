@@ -2,7 +2,7 @@
 // replaces; ctx.hpp for how the library is divided into translation units).  gfx950 only; no CPU path: every entry point either
 // runs the HIP kernels or returns an error code.
 // This unit: flow-field grids (LUDVM.flowfield, LUDVM.py:1186-1298), the vorticity stencil, and the scalar pair sums (stream
-// function, analytic vorticity) at points and on grids.
+// function, analytic vorticity) and the velocity gradient at points and on grids.
 #include "ctx.hpp"
 #include "field_kernels.hpp"
 
@@ -220,14 +220,17 @@ int ludvm_vorticity_f32(ludvm_ctx* c, const float* u, const float* w, size_t nx,
 
 }  // extern "C"
 
-/* ---- stream function and analytic vorticity -------------------------------------------------- */
+/* ---- stream function, analytic vorticity and velocity gradient ----------------------------- */
 
 static_assert(kScalarPsi == LUDVM_FIELD_PSI && kScalarOmega == LUDVM_FIELD_OMEGA, "the kernels take the ABI's kind codes");
+// (inside this unit only: the three-column gradient sum takes the scalar sums' path under a kind of its own)
+constexpr int kFieldGrad = 2;
+static int field_columns(int kind) { return kind == kFieldGrad ? 3 : 1; }
 
-// pair_scalar_f64 + finish_scalar into the device array `out` [a.nt]; a: device sources, targets (arrays or a grid) and
-// vc4 filled in by the caller.  The sources are split as the float64 velocity sum splits them (make_plan: a few targets
-// still fill the device), from plan_nt targets when the launch is a block of rows of a larger grid; the one-column slab
-// [split][nt_pad] lives in c->part.
+// pair_scalar_f64 + finish_scalar (kFieldGrad: pair_grad_f64 + finish_grad) into the device array `out` [columns][a.nt]; a:
+// device sources, targets (arrays or a grid) and vc4 filled in by the caller.  The sources are split as the float64 velocity
+// sum splits them (make_plan: a few targets still fill the device), from plan_nt targets when the launch is a block of rows
+// of a larger grid; the slab [split][columns][nt_pad] lives in c->part.
 static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, double* out) {
   const Plan p = make_plan(c, a.nt, a.ns, LUDVM_PREC_F64, true, plan_nt);
   a.chunk = p.chunk;
@@ -235,11 +238,13 @@ static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, 
   a.nsplit = p.nsplit;
   a.u = out;
   if (p.nsplit > 1) {
-    CHK(ensure(c, c->part, (size_t)p.nsplit * (size_t)p.nt_pad * sizeof(double)));
+    CHK(ensure(c, c->part, (size_t)p.nsplit * (size_t)field_columns(kind) * (size_t)p.nt_pad * sizeof(double)));
     a.part = c->part.p;
   }
   void (*kernel)(PairArgs) = nullptr;
-  if (kind == LUDVM_FIELD_PSI) {
+  if (kind == kFieldGrad) {
+    kernel = p.tile == kTileF64Few ? pair_grad_f64<kTileF64Few> : pair_grad_f64<kTileF64>;
+  } else if (kind == LUDVM_FIELD_PSI) {
     kernel = p.tile == kTileF64Few ? pair_scalar_f64<kScalarPsi, kTileF64Few> : pair_scalar_f64<kScalarPsi, kTileF64>;
   } else {
     kernel = p.tile == kTileF64Few ? pair_scalar_f64<kScalarOmega, kTileF64Few> : pair_scalar_f64<kScalarOmega, kTileF64>;
@@ -251,22 +256,29 @@ static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, 
   HIPCHK(c, hipGetLastError());
   CHK(timed_end(c, t, active));
   if (p.nsplit > 1) {
-    hipLaunchKernelGGL(finish_scalar, dim3(blocks_for(a.nt)), dim3(kBlock), 0, c->stream, static_cast<const double*>(c->part.p),
-                       a.nt, p.nt_pad, p.nsplit, out);
+    if (kind == kFieldGrad) {
+      hipLaunchKernelGGL(finish_grad, dim3(blocks_for(a.nt)), dim3(kBlock), 0, c->stream, static_cast<const double*>(c->part.p),
+                         a.nt, p.nt_pad, p.nsplit, a.vc4, out);
+    } else {
+      hipLaunchKernelGGL(finish_scalar, dim3(blocks_for(a.nt)), dim3(kBlock), 0, c->stream, static_cast<const double*>(c->part.p),
+                         a.nt, p.nt_pad, p.nsplit, out);
+    }
     HIPCHK(c, hipGetLastError());
   }
   return LUDVM_OK;
 }
 
-// Host sources up, the sum over targets `a` describes (array targets are uploaded here), nt results down.
+// Host sources up, the sum over targets `a` describes (array targets are uploaded here), nt results per column down: out[k]
+// takes column k (one column, or the gradient's three).
 static int scalar_host(ludvm_ctx* c, int kind, PairArgs a, const double* xs, const double* zs, const double* gs, size_t ns,
-                       const double* xt, const double* zt, size_t nt, size_t plan_nt, double vcore, double* out) {
+                       const double* xt, const double* zt, size_t nt, size_t plan_nt, double vcore, double* const* out) {
+  const size_t ncol = (size_t)field_columns(kind);
   HIPCHK(c, hipSetDevice(c->device));
-  CHK(ensure(c, c->arena, 3 * Arena::need(ns, 8) + 3 * Arena::need(nt, 8)));
+  CHK(ensure(c, c->arena, 3 * Arena::need(ns, 8) + 2 * Arena::need(nt, 8) + Arena::need(ncol * nt, 8)));
   Arena ar(c->arena.p);
-  double* dout = ar.take<double>(nt);
+  double* dout = ar.take<double>(ncol * nt);
   if (ns == 0) {
-    HIPCHK(c, hipMemsetAsync(dout, 0, nt * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(dout, 0, ncol * nt * 8, c->stream));
   } else {
     double* dxs = ar.take<double>(ns);
     double* dzs = ar.take<double>(ns);
@@ -287,7 +299,7 @@ static int scalar_host(ludvm_ctx* c, int kind, PairArgs a, const double* xs, con
     a.vc4 = v2 * v2;
     CHK(scalar_device(c, kind, a, (long long)plan_nt, dout));
   }
-  HIPCHK(c, hipMemcpyAsync(out, dout, nt * 8, hipMemcpyDeviceToHost, c->stream));
+  for (size_t k = 0; k < ncol; ++k) HIPCHK(c, hipMemcpyAsync(out[k], dout + k * nt, nt * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LUDVM_OK;
 }
@@ -300,7 +312,7 @@ int ludvm_scalar_f64(ludvm_ctx* c, int kind, const double* xs, const double* zs,
   if (kind != LUDVM_FIELD_PSI && kind != LUDVM_FIELD_OMEGA) return fail(c, LUDVM_E_ARG, "unknown field kind");
   if (nt == 0) return LUDVM_OK;
   if ((ns && (!xs || !zs || !gs)) || !xt || !zt || !out) return fail(c, LUDVM_E_ARG, "null array");
-  return scalar_host(c, kind, PairArgs{}, xs, zs, gs, ns, xt, zt, nt, nt, vcore, out);
+  return scalar_host(c, kind, PairArgs{}, xs, zs, gs, ns, xt, zt, nt, nt, vcore, &out);
 }
 
 int ludvm_flowfield_scalar_rows_f64(ludvm_ctx* c, int kind, double xmin, double zmin, double dr, size_t nx, size_t nz,
@@ -316,7 +328,32 @@ int ludvm_flowfield_scalar_rows_f64(ludvm_ctx* c, int kind, double xmin, double 
   a.grid_row0 = (long long)row_first;
   a.xmin = xmin; a.zmin = zmin; a.dr = dr;
   // (planned for the whole grid: a block of rows is then bit for bit what the whole-grid call computes for them)
-  return scalar_host(c, kind, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, out);
+  return scalar_host(c, kind, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, &out);
+}
+
+int ludvm_gradient_f64(ludvm_ctx* c, const double* xs, const double* zs, const double* gs, size_t ns, const double* xt,
+                       const double* zt, size_t nt, double vcore, double* ux, double* uz, double* wx) {
+  if (!c) return LUDVM_E_ARG;
+  if (nt == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !xt || !zt || !ux || !uz || !wx) return fail(c, LUDVM_E_ARG, "null array");
+  double* const out[3] = {ux, uz, wx};
+  return scalar_host(c, kFieldGrad, PairArgs{}, xs, zs, gs, ns, xt, zt, nt, nt, vcore, out);
+}
+
+int ludvm_flowfield_gradient_rows_f64(ludvm_ctx* c, double xmin, double zmin, double dr, size_t nx, size_t nz, size_t row_first,
+                                      size_t row_count, const double* xs, const double* zs, const double* gs, size_t ns,
+                                      double vcore, double* ux, double* uz, double* wx) {
+  if (!c) return LUDVM_E_ARG;
+  if (row_first > nx || row_count > nx - row_first) return fail(c, LUDVM_E_ARG, "rows outside the grid");
+  if (row_count == 0 || nz == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !ux || !uz || !wx) return fail(c, LUDVM_E_ARG, "null array");
+  PairArgs a{};
+  a.grid_nz = (long long)nz;
+  a.grid_row0 = (long long)row_first;
+  a.xmin = xmin; a.zmin = zmin; a.dr = dr;
+  // (planned for the whole grid: a block of rows is then bit for bit what the whole-grid call computes for them)
+  double* const out[3] = {ux, uz, wx};
+  return scalar_host(c, kFieldGrad, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, out);
 }
 
 }  // extern "C"

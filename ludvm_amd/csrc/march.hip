@@ -24,6 +24,8 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->tracer_record.clear();
   c->tracer_rows.clear();
   c->tracer_precision = 0;
+  c->tracer_gradient = false;
+  c->tracer_grad_ran = false;
   c->survey_count = 0;      // ... and its survey (ludvm_march_set_survey)
   c->survey_samples = 0;
   c->survey_precision = 0;
@@ -160,7 +162,9 @@ int march_probe_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s
 // are, behind march_solve of step s on the stream that ran it and behind the probe kernels when both are set, so before the
 // roll-up's finisher moves anything.  The slab, the positions and the record are the tracers' own buffers, touched only by
 // these two kernels in stream order.  Reads the wake, writes nothing of it: rows, state, hist, the resident wake and the
-// probe rows keep their bits.
+// probe rows keep their bits.  With the deformation gradient on (ludvm_march_set_tracer_gradient) the gradient pair of kernels
+// takes the place of the plain pair under the same plan: the positions keep their bits, F and its record are further buffers
+// of the tracers' own.
 int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s, long long rec_row, size_t rec_rows) {
   const MarchSetup& m = c->msetup;
   const size_t M = c->tracer_count;
@@ -170,8 +174,24 @@ int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   const long long* release = static_cast<const long long*>(c->tracer_release.p);
   const double* shift = step_shift(c->tracer_shift, c->tracer_shifted, s);
   double* cur = static_cast<double*>(c->tracer_cur.p);
-  double* slab = static_cast<double*>(c->tracer_part.p);
   double* out = static_cast<double*>(c->tracer_out.p);
+  if (c->tracer_gradient) {
+    double* gslab = static_cast<double*>(c->tracer_grad_part.p);
+    hipLaunchKernelGGL(march_grad_tracer_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M,
+                       release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.pad,
+                       (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, gslab);
+    HIPCHK(c, hipGetLastError());
+    const bool rec = rec_row >= 0;
+    hipLaunchKernelGGL(march_grad_tracer_finish, dim3(blocks_for((long long)M)), dim3(kBlock), 0, st, (const double*)gslab, p.pad,
+                       p.nsplit, seed, seed + M, release, shift, s, (long long)M, m.dt, m.vc4, cur, cur + M,
+                       static_cast<double*>(c->tracer_F.p), rec ? out + (size_t)rec_row * M : nullptr,
+                       rec ? out + (rec_rows + (size_t)rec_row) * M : nullptr,
+                       rec ? static_cast<double*>(c->tracer_F_out.p) + (size_t)rec_row * 4 * M : nullptr);
+    HIPCHK(c, hipGetLastError());
+    return LUDVM_OK;
+  }
+  double* slab = static_cast<double*>(c->tracer_part.p);
   hipLaunchKernelGGL(f32x2 ? march_f32x2_tracer_partial : march_tracer_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock),
                      0, st, seed, seed + M, release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M,
                      p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
@@ -383,6 +403,8 @@ int ludvm_march_set_tracers(ludvm_ctx* c, const double* seed_x, const double* se
   c->tracer_record.clear();
   c->tracer_rows.clear();
   c->tracer_precision = 0;         // float64 until ludvm_march_set_tracer_precision says otherwise
+  c->tracer_gradient = false;      // no deformation gradient until ludvm_march_set_tracer_gradient says otherwise
+  c->tracer_grad_ran = false;
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const long long ttiles = observer_tiles(kObserverRules[kObsTracers], (long long)count);
@@ -414,7 +436,66 @@ int ludvm_march_set_tracer_precision(ludvm_ctx* c, int precision) {
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
   if (precision != 0 && precision != 2) return fail(c, LUDVM_E_ARG, "march: tracer precision is 0 (float64) or 2 (hi+lo fp32)");
+  if (precision == 2 && c->tracer_gradient) return fail(c, LUDVM_E_STATE, "march: the tracers' deformation gradient needs float64 tracers");
   c->tracer_precision = precision;
+  return LUDVM_OK;
+}
+
+int ludvm_march_set_tracer_gradient(ludvm_ctx* c, int on, const double* F) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (on != 0 && on != 1) return fail(c, LUDVM_E_ARG, "march: the tracer gradient flag is 0 or 1");
+  const size_t M = c->tracer_count;
+  if (on && c->tracer_precision != 0) return fail(c, LUDVM_E_STATE, "march: the tracers' deformation gradient needs float64 tracers");
+  if (on && F)
+    for (size_t k = 0; k < 4 * M; ++k)
+      if (!std::isfinite(F[k])) return fail(c, LUDVM_E_ARG, "march: the tracers' deformation gradient must be finite");
+  if (!on) {
+    c->tracer_gradient = false;
+    c->tracer_grad_ran = false;
+    return LUDVM_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> f(4 * M, 0.0);
+  if (F) std::copy(F, F + 4 * M, f.begin());
+  else std::fill(f.begin(), f.begin() + M, 1.0), std::fill(f.begin() + 3 * M, f.end(), 1.0);
+  // (the five-column slab [split][5][m_pad] of kObsTracers' plan: 5 / 2 of the plain one)
+  CHK(ensure(c, c->tracer_F, 4 * M * 8));
+  CHK(ensure(c, c->tracer_grad_part, observer_slab_bytes(kObserverRules[kObsTracers], (long long)M) / 2 * 5));
+  HIPCHK(c, hipMemcpyAsync(c->tracer_F.p, f.data(), 4 * M * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (f lives on this frame)
+  c->tracer_gradient = true;
+  c->tracer_grad_ran = false;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_tracer_gradient(ludvm_ctx* c, double* F, size_t rows_cap, long long* steps_out, size_t* nrows_out) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (!c->tracer_gradient) return fail(c, LUDVM_E_STATE, "march: the tracers' deformation gradient is not on");
+  if (!c->tracer_ran || !c->tracer_grad_ran)
+    return fail(c, LUDVM_E_STATE, "march: no ludvm_march_run call has succeeded since the tracers' deformation gradient was set");
+  if (!nrows_out) return fail(c, LUDVM_E_ARG, "null array");
+  const size_t rows = c->tracer_rows.size();
+  *nrows_out = rows;
+  if (rows_cap < rows) return fail(c, LUDVM_E_ARG, "march: the last ludvm_march_run call recorded " + std::to_string(rows) + " tracer rows");
+  if (rows == 0) return LUDVM_OK;
+  if (!F || !steps_out) return fail(c, LUDVM_E_ARG, "null array");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(F, c->tracer_F_out.p, rows * 4 * c->tracer_count * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < rows; ++k) steps_out[k] = c->tracer_rows[k];
+  return LUDVM_OK;
+}
+
+int ludvm_march_tracer_gradient_state(ludvm_ctx* c, double* F) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (!c->tracer_gradient) return fail(c, LUDVM_E_STATE, "march: the tracers' deformation gradient is not on");
+  if (!F) return fail(c, LUDVM_E_ARG, "null array");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(F, c->tracer_F.p, 4 * c->tracer_count * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return LUDVM_OK;
 }
 
@@ -488,6 +569,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
   c->probe_rows = 0;
   c->tracer_ran = false;
+  c->tracer_grad_ran = false;
   c->tracer_rows.clear();
   if (!valid_precision(precision)) return fail(c, LUDVM_E_ARG, "unknown precision");
   if (!state || !rows) return fail(c, LUDVM_E_ARG, "null array");
@@ -522,6 +604,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
     for (long long r : c->tracer_record)
       if (r >= first_step && r < first_step + count) trec.push_back(r);
     if (!trec.empty()) CHK(ensure(c, c->tracer_out, trec.size() * 2 * c->tracer_count * 8));
+    if (!trec.empty() && c->tracer_gradient) CHK(ensure(c, c->tracer_F_out, trec.size() * 4 * c->tracer_count * 8));
   }
   size_t trec_at = 0;               // the next recorded step
   const bool survey = c->survey_count != 0;
@@ -766,7 +849,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   for (int k = 0; k < m.ncoef; ++k) state[16 + k] = hs.prevA[k];
   if (c->timing) CHK(drain_timing(c));
   if (probes) c->probe_rows = (size_t)count;
-  if (tracers) { c->tracer_rows = trec; c->tracer_ran = true; }
+  if (tracers) { c->tracer_rows = trec; c->tracer_ran = true; c->tracer_grad_ran = c->tracer_gradient; }
   c->survey_samples += surveyed;
   for (size_t b = 0; b < binned.size(); ++b) c->survey_bin_samples[b] += binned[b];
   return LUDVM_OK;

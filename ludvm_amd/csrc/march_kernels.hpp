@@ -753,6 +753,149 @@ march_tracer_finish(const double* slab, long long m_pad, int nsplit, const doubl
   }
 }
 
+// ---- deformation gradient of the tracers (ludvm_march_set_tracer_gradient) -----------------------------------------------------
+// The sources of a step do not depend on a tracer, so the exact derivative of the discrete map start -> start + dt (u, w)_i(start)
+// with respect to the seed is one 2 x 2 product per step: F <- (I + dt G_i(start)) F, G_i = grad (u, w)_i in closed form
+// (field_kernels.hpp: du/dx = -A / pi, du/dz = (B + vc^4 C) / (2 pi), dw/dx = (B - vc^4 C) / (2 pi), dw/dz = -du/dx, from the raw
+// sums A = sum G r2 dx dz y^3, B = sum G r2 (dx^2 - dz^2) y^3, C = sum G y^3, y = 1 / sqrt(r2^2 + vc^4)).  F = [[dx/dX, dx/dZ],
+// [dz/dX, dz/dZ]] lives in four resident arrays F11 | F12 | F21 | F22 [M]: the identity while a tracer is held and at its release.
+//
+// field_grad_f64              field_f64 with three more accumulators per point: per pair pair_acc_f64's arithmetic for au, aw,
+//                             operation for operation (the positions keep their bits), then the A, B, C updates from that pair's
+//                             dx, dz, r2 and reciprocal square root.  A pad slot (G = 0 at kPadPosD) adds exact zeros: y = 0
+//                             there and G y^3 is multiplied in BEFORE r2 and dx dz (both finite at the pad)
+// march_grad_tracer_partial   march_tracer_partial's loader and launch geometry (kObsTracers: the same tiles, splits and chunk, so
+//                             the same summation order for u and w), the body above, five columns u | w | A | B | C to a slab
+//                             [split][5][m_pad] of its own
+// march_grad_tracer_finish    march_tracer_finish's position update with the same operations, then the product above (held: F
+//                             untouched; the release step starts from the identity) and -- recorded -- the step's F row
+template <int PPL, int LANES, int UNROLL>
+__device__ __forceinline__ void field_grad_f64(const double (&xp)[PPL], const double (&zp)[PPL], const double* __restrict__ xs,
+                                               const double* __restrict__ zs, const double* __restrict__ gs, long long s_begin,
+                                               long long s_end, double vc4, double (&au)[PPL], double (&aw)[PPL], double (&ga)[PPL],
+                                               double (&gb)[PPL], double (&gc)[PPL]) {
+  static_assert(kFieldTile % LANES == 0, "whole source slots per lane");
+  __shared__ __attribute__((aligned(16))) double lx[kFieldTile];
+  __shared__ __attribute__((aligned(16))) double lz[kFieldTile];
+  __shared__ __attribute__((aligned(16))) double lg[kFieldTile];
+  const int tid = threadIdx.x;
+  for (long long base = s_begin; base < s_end; base += kFieldTile) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kFieldTile / LANES; ++k) {
+      const int l = tid + k * LANES;
+      const long long si = base + l;
+      const bool ok = si < s_end;
+      lx[l] = ok ? xs[si] : kPadPosD;
+      lz[l] = ok ? zs[si] : kPadPosD;
+      lg[l] = ok ? gs[si] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll UNROLL
+    for (int j = 0; j < kFieldTile; ++j) {
+      const double sx = lx[j], sz = lz[j], sg = lg[j];
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) {
+        // (pair_acc_f64, operation for operation)
+        const double dx = xp[k] - sx;
+        const double dz = zp[k] - sz;
+        const double dxx = dx * dx;
+        const double r2 = __builtin_fma(dz, dz, dxx);
+        const double q = __builtin_fma(r2, r2, vc4);
+        const double y = rsqrt_f64(q);
+        const double s = sg * y;
+        au[k] = __builtin_fma(dz, s, au[k]);
+        aw[k] = __builtin_fma(dx, s, aw[k]);
+        // the gradient's raw sums
+        const double c = s * (y * y);                       // G y^3
+        const double e = c * r2;
+        gc[k] += c;
+        ga[k] = __builtin_fma(e, dx * dz, ga[k]);
+        gb[k] = __builtin_fma(e, __builtin_fma(-dz, dz, dxx), gb[k]);
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_grad_tracer_partial(const double* __restrict__ seed_x, const double* __restrict__ seed_z, const long long* __restrict__ release,
+                          const long long* __restrict__ tile_min, const double* cur_x, const double* cur_z, const double* shift,
+                          long long step, long long count, long long m_pad, const double* __restrict__ xs,
+                          const double* __restrict__ zs, const double* __restrict__ gs, const MarchState* S, int nfoil,
+                          long long chunk, double vc4, double* slab) {
+  if (tiles_held<1>(tile_min, step, count)) return;         // (uniform: before any barrier)
+  __builtin_amdgcn_s_setprio(3);
+  const SplitRange src = split_range(S, nfoil, chunk);
+  double xp[kTracerPerLane], zp[kTracerPerLane], au[kTracerPerLane], aw[kTracerPerLane];
+  double ga[kTracerPerLane], gb[kTracerPerLane], gc[kTracerPerLane];
+  bool free_[kTracerPerLane];
+  load_tracers<kTracerPerLane>(seed_x, seed_z, release, cur_x, cur_z, shift, step, count, kPadPosD, xp, zp, au, aw, free_);
+#pragma unroll
+  for (int k = 0; k < kTracerPerLane; ++k) { ga[k] = 0.0; gb[k] = 0.0; gc[k] = 0.0; }
+  field_grad_f64<kTracerPerLane, kBlock, 2>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw, ga, gb, gc);
+  double* row = slab + (long long)blockIdx.y * 5 * m_pad;
+#pragma unroll
+  for (int k = 0; k < kTracerPerLane; ++k) {
+    const long long m = observer_point<kTracerPerLane, kBlock>(k);
+    if (free_[k]) {
+      row[m] = au[k] * kInv2PiD;
+      row[m_pad + m] = -aw[k] * kInv2PiD;
+      row[2 * m_pad + m] = ga[k];
+      row[3 * m_pad + m] = gb[k];
+      row[4 * m_pad + m] = gc[k];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_grad_tracer_finish(const double* slab, long long m_pad, int nsplit, const double* __restrict__ seed_x,
+                         const double* __restrict__ seed_z, const long long* __restrict__ release, const double* shift,
+                         long long step, long long count, double dt, double vc4, double* cur_x, double* cur_z, double* F,
+                         double* rec_x, double* rec_z, double* rec_F) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (m >= count) return;
+  const double sh = shift ? *shift : 0.0;
+  const long long rel = release[m];
+  double x, z;
+  double f11 = F[m], f12 = F[count + m], f21 = F[2 * count + m], f22 = F[3 * count + m];
+  if (rel > step) {
+    x = seed_x[m] + sh;
+    z = seed_z[m];
+  } else {
+    tracer_start(seed_x, seed_z, cur_x, cur_z, m, rel, step, sh, x, z);
+    // (march_tracer_finish's sums and update: splits 0, 1, 2, ... in that order)
+    double u = 0.0, w = 0.0, A = 0.0, B = 0.0, C = 0.0;
+    const double* c0 = slab + m;
+    for (int sidx = 0; sidx < nsplit; ++sidx) {
+      const double* cs = c0 + (long long)sidx * 5 * m_pad;
+      u += cs[0];
+      w += cs[m_pad];
+      A += cs[2 * m_pad];
+      B += cs[3 * m_pad];
+      C += cs[4 * m_pad];
+    }
+    x = __builtin_fma(dt, u, x);
+    z = __builtin_fma(dt, w, z);
+    const double vC = vc4 * C;
+    const double ux = -A * kInvPiD, uz = (B + vC) * kInv2PiD, wx = (B - vC) * kInv2PiD, wz = -ux;
+    if (rel == step) { f11 = 1.0; f12 = 0.0; f21 = 0.0; f22 = 1.0; }
+    const double n11 = __builtin_fma(dt, __builtin_fma(ux, f11, uz * f21), f11);
+    const double n12 = __builtin_fma(dt, __builtin_fma(ux, f12, uz * f22), f12);
+    const double n21 = __builtin_fma(dt, __builtin_fma(wx, f11, wz * f21), f21);
+    const double n22 = __builtin_fma(dt, __builtin_fma(wx, f12, wz * f22), f22);
+    f11 = n11; f12 = n12; f21 = n21; f22 = n22;
+    F[m] = f11; F[count + m] = f12; F[2 * count + m] = f21; F[3 * count + m] = f22;
+  }
+  cur_x[m] = x;
+  cur_z[m] = z;
+  if (rec_x) {
+    rec_x[m] = x;
+    rec_z[m] = z;
+    rec_F[m] = f11; rec_F[count + m] = f12; rec_F[2 * count + m] = f21; rec_F[3 * count + m] = f22;
+  }
+}
+
 // ---- wake survey: running field moments (ludvm_march_set_survey) ------------------------------------------------------------------
 // Survey point k sits at (x[k] + shift[i], z[k]) in step i (shift[i] = 0 in the lab frame).  In every SAMPLED step i -- the
 // host knows the window first <= i < stop, (i - first) % every == 0 and launches nothing outside it -- the probes' field

@@ -51,6 +51,7 @@ constexpr int kFinBlock = kOriginBlock;           // Euler finishers: one workgr
 // the end
 inline __host__ __device__ long long origin_slots(long long n) { return 2 * (n / kOriginBlock + 2); }
 constexpr double kInv2PiD = 0.15915494309189533576888;
+constexpr double kInvPiD = 0.31830988618379067153777;
 // Padding for source slots past the end of the range: far enough that r^4 overflows to +inf, so
 // rsq() returns exactly 0 and the (zero-circulation) slot contributes exactly 0 even when vc = 0
 // (inviscid), yet small enough that dx^2 + dz^2 itself stays finite.

@@ -536,6 +536,41 @@ class Engine:
             raise ValueError("march_set_tracer_precision: 'f64' or 'f32x2' (or the library's code)")
         self._check(self._lib.ludvm_march_set_tracer_precision(self._ctx, code))
 
+    def march_set_tracer_gradient(self, on=True, F=None):
+        """Carry the tracers' deformation gradient through the marched steps (ludvm_march_set_tracer_gradient): F <- (I + dt
+        grad(u, w)) F per step of a released tracer, the identity while it is held and at its release.  F: None (the identity),
+        or [4, M] (F11, F12, F21, F22) of a run that is continued.  Valid while float64 tracers are set."""
+        if not hasattr(self._lib, "ludvm_march_set_tracer_gradient"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_tracer_gradient")
+        code = int(on) if isinstance(on, (bool, int, np.integer)) else None
+        if code is None:
+            raise ValueError("march_set_tracer_gradient: on is a flag (or the library's code)")
+        f = None
+        if F is not None:
+            f = np.ascontiguousarray(F, dtype=np.float64)
+            if f.shape != (4, getattr(self, "_march_ntracers", 0)):
+                raise ValueError("march_set_tracer_gradient: F must be [4, M]")
+        self._check(self._lib.ludvm_march_set_tracer_gradient(self._ctx, code, _pd(f)))
+
+    def march_tracer_gradient(self):
+        """(steps int64 [R], F float64 [R, 4, M]): the deformation-gradient rows the last `march_run` call recorded, the steps of
+        `march_tracers` (ludvm_march_read_tracer_gradient)."""
+        first, count = self._march_last
+        rec = self._march_tracer_record
+        M, cap = self._march_ntracers, int(np.count_nonzero((rec >= first) & (rec < first + count)))
+        F = np.empty([cap, 4, M])
+        steps, n = np.zeros(max(cap, 1), dtype=np.int64), c_size_t(0)
+        self._check(self._lib.ludvm_march_read_tracer_gradient(self._ctx, _pd(F), cap, steps.ctypes.data_as(POINTER(c_longlong)),
+                                                               byref(n)))
+        r = int(n.value)
+        return steps[:r].copy(), F[:r].copy()
+
+    def march_tracer_gradient_state(self):
+        """float64 [4, M]: the tracers' current deformation gradient (ludvm_march_tracer_gradient_state)."""
+        F = np.empty([4, self._march_ntracers])
+        self._check(self._lib.ludvm_march_tracer_gradient_state(self._ctx, _pd(F)))
+        return F
+
     def march_set_survey_precision(self, precision):
         """How the marched steps evaluate the survey's field (ludvm_march_set_survey_precision): 'f64' (what `march_set_survey`
         leaves) or 'f32' -- fp32 pair arithmetic on local origins, float64 class sums, splits and moments -- or the library's
@@ -782,6 +817,41 @@ class Engine:
                                                               row_first, row_count, _pd(xs), _pd(zs), _pd(g), len(xs),
                                                               float(v_core), _pd(out)))
         return out.reshape(row_count, nz)
+
+    # -- velocity gradient ------------------------------------------------------------------------
+    def _need(self, fn):
+        if not hasattr(self._lib, fn):
+            raise LudvmHipError(_ffi.E_STATE, f"this build of the library has no {fn}")
+
+    def gradient_field(self, circulation, xw, zw, xp, zp, v_core):
+        """(ux, uz, wx), float64 [Np] each: du/dx, du/dz and dw/dx of `induce`'s velocity at the points, in closed form and in
+        float64 throughout (ludvm_gradient_f64); dw/dz = -ux, wx - uz is `scalar_field('omega', ...)`."""
+        self._need("ludvm_gradient_f64")
+        g, xs, zs, xt, zt = _f64(circulation), _f64(xw), _f64(zw), _f64(xp), _f64(zp)
+        if not (len(g) == len(xs) == len(zs)) or len(xt) != len(zt):
+            raise ValueError("gradient_field: source arrays (and target arrays) must have equal lengths")
+        ux, uz, wx = np.empty(len(xt)), np.empty(len(xt)), np.empty(len(xt))
+        self._check(self._lib.ludvm_gradient_f64(self._ctx, _pd(xs), _pd(zs), _pd(g), len(xs), _pd(xt), _pd(zt), len(xt),
+                                                 float(v_core), _pd(ux), _pd(uz), _pd(wx)))
+        return ux, uz, wx
+
+    def flowfield_gradient(self, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core, row_first=0, row_count=None):
+        """(ux, uz, wx), float64 [row_count, nz] each: `gradient_field` on rows [row_first, row_first + row_count) of the
+        flow-field grid (xmin + i*dr, zmin + j*dr), generated on the device; every row by default.  A block of rows carries
+        the whole-grid call's bits (ludvm_flowfield_gradient_rows_f64)."""
+        self._need("ludvm_flowfield_gradient_rows_f64")
+        g, xs, zs = _f64(circulation), _f64(xw), _f64(zw)
+        if not (len(g) == len(xs) == len(zs)):
+            raise ValueError("flowfield_gradient: source arrays must have equal lengths")
+        nx, nz, row_first = int(nx), int(nz), int(row_first)
+        row_count = nx - row_first if row_count is None else int(row_count)
+        if nx < 0 or nz < 0 or row_first < 0 or row_count < 0:
+            raise ValueError("flowfield_gradient: nx, nz, row_first and row_count must not be negative")
+        ux, uz, wx = (np.empty(max(row_count, 0) * nz) for _ in range(3))
+        self._check(self._lib.ludvm_flowfield_gradient_rows_f64(self._ctx, float(xmin), float(zmin), float(dr), nx, nz,
+                                                                row_first, row_count, _pd(xs), _pd(zs), _pd(g), len(xs),
+                                                                float(v_core), _pd(ux), _pd(uz), _pd(wx)))
+        return ux.reshape(row_count, nz), uz.reshape(row_count, nz), wx.reshape(row_count, nz)
 
     def fixed_point_probe(self, values, scale_log2):
         """int64 units the symmetric kernel adds to an accumulator for fp32 partial sums `values` at scale

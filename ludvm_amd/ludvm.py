@@ -135,6 +135,19 @@ class LUDVM:
                  other result keeps its bits, and the paths repeat bit for bit however the run is cut, checkpoints included
                  (they carry the value).  Refused: without `tracers`, with march=False, in a sweep; a run that cannot take the
                  march raises instead of falling back to float64.  The object carries `tracer_precision` as used
+      tracer_gradient  False (default).  True: every tracer carries the deformation gradient of its own path with respect to
+                 its seed, F = [[dx/dX, dx/dZ], [dz/dX, dz/dZ]].  The sources of a step do not depend on a tracer, so the exact
+                 derivative of the discrete forward-Euler map is one 2 x 2 product per step, F <- (I + dt G_i(start)) F with G_i
+                 the gradient of (u, w)_i in closed form (`velocity_gradient`) at the step's start position; F is the identity
+                 while a tracer is held and at its release.  Evaluated inside the device-resident march by a gradient version of
+                 the float64 tracer kernels under the same launch plan.  Results: `tracer_F_path`, a SparseHistory step ->
+                 [4, M] in the order F11, F12, F21, F22 (row 0: the identity; the steps of `tracer_path`), `tracer_F_last`
+                 [4, M], `tracer_ftle(step=None)` -> [M], the finite-time Lyapunov exponent ln sigma_max(F) / T with T = dt (step
+                 - release + 1), NaN for a tracer not yet released (`ftle_from_F(F, T)` for any F).  The tracer positions and
+                 every other result keep their bits; F repeats bit for bit however the run is cut, checkpoints included (they
+                 carry it).  Refused: without `tracers`, with march=False, with tracer_precision='f32x2', in a sweep, with
+                 `distributed` or more than one device; a run that cannot take the march raises.  Out of scope: backward-time
+                 FTLE, the gradient on the per-step path
       survey     None (default), or the points of a wake survey: a [2, K] array (x row, z row), or a dict(xmin, xmax, zmin, zmax,
                  dr) meaning the mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr), x-major as `flowfield` builds it
                  (1 <= K <= 1048576).  In every sampled step the field of `probes` is evaluated at the points and added to
@@ -204,6 +217,10 @@ class LUDVM:
                 if kwargs.get('probes') is not None:
                     cls._check_probes(kwargs['probes'], kwargs.get('probe_frame', 'lab'))
                     raise ValueError("probes run on one GPU: not with more than one device in `devices`")
+                if kwargs.get('tracer_gradient', False) is not False:
+                    cls._check_tracer_gradient(kwargs['tracer_gradient'], kwargs.get('tracers') is not None,
+                                               kwargs.get('march', True), kwargs.get('tracer_precision', 'f64'))
+                    raise ValueError("tracer_gradient runs on one GPU: not with more than one device in `devices`")
                 if kwargs.get('tracers') is not None:
                     cls._check_tracers(kwargs['tracers'], kwargs.get('tracer_release'), kwargs.get('tracer_frame', 'lab'))
                     raise ValueError("tracers run on one GPU: not with more than one device in `devices`")
@@ -360,6 +377,41 @@ class LUDVM:
             raise ValueError("tracer_precision='f32x2' is evaluated inside the device-resident march: not with march=False")
 
     @staticmethod
+    def _check_tracer_gradient(tracer_gradient, traced, march=True, tracer_precision='f64'):
+        """ValueError from the keywords alone (nothing else has been created yet)."""
+        if not isinstance(tracer_gradient, (bool, np.bool_)):
+            raise ValueError(f"tracer_gradient must be True or False (got {tracer_gradient!r})")
+        if not tracer_gradient:
+            return
+        if not traced:
+            raise ValueError("tracer_gradient needs `tracers`")
+        if not march:
+            raise ValueError("tracer_gradient is evaluated inside the device-resident march: not with march=False")
+        if tracer_precision != 'f64':
+            raise ValueError(f"tracer_gradient needs float64 tracers: not with tracer_precision={tracer_precision!r}")
+
+    @staticmethod
+    def ftle_from_F(F, T):
+        """Finite-time Lyapunov exponent ln sigma_max(F) / T of deformation gradients F [4, ...] (F11, F12, F21, F22) over the
+        times T (a number or an array of the trailing shape): sigma_max^2 = (|F|^2 + sqrt(|F|^4 - 4 det^2)) / 2 with |F| the
+        Frobenius norm -- the radicand formed as its factors ((F11 - F22)^2 + (F12 + F21)^2) ((F11 + F22)^2 + (F12 - F21)^2), which
+        do not cancel where the two singular values are close (F near the identity or a rotation).  Plain numpy; NaN where
+        T <= 0."""
+        F = np.asarray(F, dtype=np.float64)
+        if F.shape[0] != 4:
+            raise ValueError(f"ftle_from_F: F must be [4, ...] (F11, F12, F21, F22); got shape {F.shape}")
+        f11, f12, f21, f22 = F
+        n2 = f11 * f11 + f12 * f12 + f21 * f21 + f22 * f22
+        rad = ((f11 - f22)**2 + (f12 + f21)**2) * ((f11 + f22)**2 + (f12 - f21)**2)       # = |F|^4 - 4 det^2
+        s2 = 0.5 * (n2 + np.sqrt(rad))
+        T = np.broadcast_to(np.asarray(T, dtype=np.float64), s2.shape)
+        out = np.full(s2.shape, np.nan)
+        ok = T > 0
+        with np.errstate(divide='ignore', invalid='ignore'):
+            out[ok] = 0.5 * np.log(s2[ok]) / T[ok]
+        return out
+
+    @staticmethod
     def _check_tracers(tracers, tracer_release, tracer_frame, tracer_steps=None, nt=None):
         """-> (float64 [2, M], int64 [M], sorted steps or None), or ValueError (nothing else has been created yet)."""
         if tracer_frame not in ('lab', 'tunnel'):
@@ -410,7 +462,7 @@ class LUDVM:
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
                  probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
                  survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64', tracer_precision='f64',
-                 survey_bins=None, survey_period=None, survey_phase0=None):
+                 survey_bins=None, survey_period=None, survey_phase0=None, tracer_gradient=False):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -429,6 +481,9 @@ class LUDVM:
         elif tracer_release is not None or tracer_steps is not None:
             raise ValueError("tracer_release / tracer_steps need `tracers`")
         self._check_tracer_precision(tracer_precision, tracers is not None, march)
+        self._check_tracer_gradient(tracer_gradient, tracers is not None, march, tracer_precision)
+        if tracer_gradient and distributed is not None and distributed is not False:
+            raise ValueError("tracer_gradient runs on one GPU: not with `distributed`")
         if survey is not None:
             # refused before any engine, thread or communicator exists
             survey_xz, survey_shape, survey_win = self._check_survey(survey, survey_frame, survey_steps,
@@ -470,6 +525,9 @@ class LUDVM:
             self.tracer_precision = tracer_precision
             if self.tracer_precision != 'f64':      # (float64 tracers keep the checkpoints they had)
                 self._ctor.update(tracer_precision=self.tracer_precision)
+            self.tracer_gradient = bool(tracer_gradient)
+            if self.tracer_gradient:                # (tracers without it likewise)
+                self._ctor.update(tracer_gradient=True)
         if survey is not None:              # (likewise; a mesh travels as its five numbers)
             self._ctor.update(survey={k: float(v) for k, v in survey.items()} if isinstance(survey, dict) else survey_xz.tolist(),
                               survey_frame=survey_frame, survey_steps=list(survey_win))
@@ -709,6 +767,19 @@ class LUDVM:
         with `viscous=False` (NaN at a point on top of a vortex)."""
         return self._scalar_field('omega', 'the analytic vorticity', circulation, xw, zw, xp, zp, viscous)
 
+    def velocity_gradient(self, circulation, xw, zw, xp, zp, viscous=True):
+        """Velocity gradient (ux, uz, wx) = (du/dx, du/dz, dw/dx) at points (xp, zp) of the velocity field `induced_velocity`
+        gives for vortices (circulation, xw, zw), in closed form: no grid and no differences.  dw/dz = -ux (the field is
+        divergence free), wx - uz is `vorticity`, and Q = -ux^2 - uz wx is positive in a vortex core and negative in a
+        shear layer.  Three new float64 arrays, float64 on the GPU whatever the run's `precision`; with `viscous=False` the
+        point vortex's gradient (NaN at a point on top of a vortex)."""
+        if self._shard is not None and self._shard.world > 1:
+            raise ValueError("the velocity gradient runs on one GPU: not with `distributed` or more than one device in `devices`")
+        if not hasattr(self.engine, 'gradient_field'):
+            raise RuntimeError("the velocity gradient: this engine has no gradient_field")
+        v_core = self.v_core if viscous == True else 0  # noqa: E712  (as induced_velocity)
+        return self.engine.gradient_field(circulation, xw, zw, xp, zp, v_core)
+
     def _chord_frame(self, u1, w1, i):
         a = self.alpha[i]
         return u1 * np.cos(a) - w1 * np.sin(a), u1 * np.sin(a) + w1 * np.cos(a)
@@ -782,6 +853,8 @@ class LUDVM:
                 i += 1
             if S.tracers is not None:
                 self.tracer_last = eng.march_tracer_state() if S.can_march else S.tcur
+                if self.tracer_gradient:
+                    self.tracer_F_last = eng.march_tracer_gradient_state()
             if S.survey is not None:
                 self._survey_results(*(eng.march_survey() if S.can_march else (S.ssums, S.scount)))
             if S.sbins is not None:
@@ -799,7 +872,7 @@ class LUDVM:
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
             'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
-            'tracers', 'trec', 'tcur', 'survey', 'ssums', 'scount', 'sbins', 'sbsums', 'sbcounts',
+            'tracers', 'trec', 'tcur', 'tF', 'survey', 'ssums', 'scount', 'sbins', 'sbsums', 'sbcounts',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
@@ -906,6 +979,11 @@ class LUDVM:
             self.tracer_path = SparseHistory(nt)
             S.tcur = self._tracer_seeds(0)
             self.tracer_path.store(0, S.tcur.copy())
+            S.tF = None
+            if self.tracer_gradient:
+                # the deformation gradient the march carries: the identity at the seeds (row 0)
+                self.tracer_F_path = SparseHistory(nt)
+                self.tracer_F_path.store(0, self._identity_F())
         S.survey = getattr(self, '_survey_xz', None)
         S.ssums, S.scount = None, 0
         if S.survey is not None:
@@ -976,6 +1054,24 @@ class LUDVM:
         """bool [M]: the tracers that move in time step `step` (released at or before it)."""
         return self.tracer_release <= int(step)
 
+    def _identity_F(self):
+        F = np.zeros([4, self.tracer_xz.shape[1]])
+        F[0], F[3] = 1.0, 1.0
+        return F
+
+    def tracer_ftle(self, step=None):
+        """float64 [M]: the finite-time Lyapunov exponent ln sigma_max(F) / T of every tracer after time step `step` (None: the
+        last step), T = dt (step - release + 1) -- NaN for a tracer not yet released at that step.  Needs tracer_gradient=True
+        and, for a step other than the last, a step `tracer_F_path` holds."""
+        if not getattr(self, 'tracer_gradient', False):
+            raise ValueError("tracer_ftle needs a run with tracer_gradient=True")
+        if step is None:
+            step, F = self.nt - 1, self.tracer_F_last
+        else:
+            step = int(step) + (self.nt if int(step) < 0 else 0)
+            F = self.tracer_F_path[step]
+        return self.ftle_from_F(F, self.dt * (step - self.tracer_release + 1.0))
+
     def probe_positions(self, step):
         """Lab coordinates [2, P] of the probes at time step `step` ('tunnel' frame: x + xpiv[step])."""
         xz = self.probe_xz.copy()
@@ -1001,6 +1097,10 @@ class LUDVM:
             S.tcur = R['tracer_cur'].copy()
             for srow, row in zip(R['tracer_rows_steps'], R['tracer_rows']):
                 self.tracer_path.store(int(srow), row.copy())
+            if self.tracer_gradient:
+                S.tF = R['tracer_F_cur'].copy()
+                for srow, row in zip(R['tracer_rows_steps'], R['tracer_F_rows']):
+                    self.tracer_F_path.store(int(srow), row.copy())
         if S.survey is not None:
             S.ssums, S.scount = R['survey_sums'].copy(), int(R['survey_samples'])
         if S.sbins is not None:
@@ -1030,6 +1130,9 @@ class LUDVM:
         f32_tracers = S.tracers is not None and self.tracer_precision == 'f32x2'
         if f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_precision'):
             raise RuntimeError("tracer_precision='f32x2': this engine marches but has no march_set_tracer_precision")
+        grad_tracers = S.tracers is not None and self.tracer_gradient
+        if grad_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_gradient'):
+            raise RuntimeError("tracer_gradient: this engine marches but has no march_set_tracer_gradient")
         f32_survey = S.survey is not None and self.survey_precision == 'f32'
         if f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_precision'):
             raise RuntimeError("survey_precision='f32': this engine marches but has no march_set_survey_precision")
@@ -1051,6 +1154,8 @@ class LUDVM:
                                       shift_x=self.xpiv if self.tracer_frame == 'tunnel' else None, cur=S.tcur, record_steps=S.trec)
                 if f32_tracers:
                     eng.march_set_tracer_precision('f32x2')
+                if grad_tracers:
+                    eng.march_set_tracer_gradient(True, F=S.tF)
             if S.survey is not None:
                 eng.march_set_survey(S.survey[0], S.survey[1], shift_x=self.xpiv if self.survey_frame == 'tunnel' else None,
                                      steps=self.survey_steps, sums=S.ssums if S.scount else None, samples=S.scount)
@@ -1063,6 +1168,10 @@ class LUDVM:
         if f32_tracers and not S.can_march:
             # (no float64 in its place: the per-step path has no fp32 tracer sums)
             raise RuntimeError("tracer_precision='f32x2' is evaluated inside the device-resident march, which this run cannot take "
+                               "(an engine without march_run, method, Npoints or Ncoeffs outside its limits)")
+        if grad_tracers and not S.can_march:
+            # (the per-step path carries no deformation gradient)
+            raise RuntimeError("tracer_gradient is evaluated inside the device-resident march, which this run cannot take "
                                "(an engine without march_run, method, Npoints or Ncoeffs outside its limits)")
         if f32_survey and not S.can_march:
             # (no float64 in its place: the per-step path has no fp32 survey sums)
@@ -1126,8 +1235,10 @@ class LUDVM:
             # one call's probe rows ([steps, 2, P] doubles) stay at or under 256 MB, like the history rows
             j = min(j, i + max(1, int(getattr(self, '_probe_call_bytes', 256e6) // (16 * S.probes.shape[1]))))
         if S.tracers is not None:
-            # one call's recorded tracer rows ([rows, 2, M] doubles) stay at or under 256 MB as well
-            most = max(1, int(getattr(self, '_tracer_call_bytes', 256e6) // (16 * S.tracers.shape[1])))
+            # one call's recorded tracer rows ([rows, 2, M] doubles; with the deformation gradient [rows, 4, M] more) stay at or
+            # under 256 MB as well
+            row_bytes = 48 if self.tracer_gradient else 16
+            most = max(1, int(getattr(self, '_tracer_call_bytes', 256e6) // (row_bytes * S.tracers.shape[1])))
             lo = int(np.searchsorted(S.trec, i))
             if int(np.searchsorted(S.trec, j)) - lo > most:
                 j = int(S.trec[lo + most])      # (the call ends before its `most + 1`-th recorded step)
@@ -1173,6 +1284,9 @@ class LUDVM:
         if S.tracers is not None:
             for srow, row in zip(*self.engine.march_tracers()):
                 self.tracer_path.store(int(srow), row)
+            if self.tracer_gradient:
+                for srow, row in zip(*self.engine.march_tracer_gradient()):
+                    self.tracer_F_path.store(int(srow), row)
         self._store_march_results(S, i, j, st, R, hist)
 
     def _store_march_results(self, S, i, j, st, R, hist=None):
@@ -1527,6 +1641,9 @@ class LUDVM:
             steps_t = self.tracer_path.steps()
             d['tracer_rows_steps'] = np.array(steps_t, dtype=np.int64)
             d['tracer_rows'] = np.stack([self.tracer_path[q] for q in steps_t])
+            if self.tracer_gradient:    # (the current deformation gradient and its rows, the steps of tracer_rows)
+                d['tracer_F_cur'] = self.engine.march_tracer_gradient_state()
+                d['tracer_F_rows'] = np.stack([self.tracer_F_path[q] for q in steps_t])
         if S.survey is not None:        # (likewise; the sums and the count of sampled steps so far)
             d['survey_sums'], d['survey_samples'] = self.engine.march_survey() if S.can_march else (S.ssums, S.scount)
         if S.sbins is not None:         # (likewise; the sums and the samples of every bin so far)
@@ -1674,7 +1791,7 @@ class LUDVM:
         LUDVM(..., snapshot_steps=LUDVM.flowfield_rows_needed(tsteps))."""
         return sorted({r for s in tsteps for r in ((int(s) - 1, int(s)) if int(s) > 0 else (0,))})
 
-    def flowfield(self, xmin=-10, xmax=0, zmin=-4, zmax=4, dr=0.02, tsteps=[0, 1, 2], psi=False, omega=False):
+    def flowfield(self, xmin=-10, xmax=0, zmin=-4, zmax=4, dr=0.02, tsteps=[0, 1, 2], psi=False, omega=False, grad=False):
         """Velocity and vorticity on the uniform mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr)
         at the requested time steps (LUDVM.py:1186-1298).  The mesh points are generated on the
         device (x-major, as meshgrid(indexing='ij') ravels, :1194-1195); wake and bound vortices go in
@@ -1687,13 +1804,21 @@ class LUDVM:
         function whose contours are the streamlines (of the induced velocity, the fluid far away at rest; `psi_ff + Uinf * z_ff`
         in the frame that translates with the foil, a wind tunnel's) and the core model's vorticity in closed form
         (`stream_function`, `vorticity`) -- float64 whatever the run's precision, and, unlike the stencil's ome_ff, resolved at
-        any dr.  One GPU only; u_ff, w_ff and ome_ff are what they are without the flags."""
+        any dr.  `grad=True` adds the velocity gradient in closed form from the same sources on the same mesh
+        (`velocity_gradient`): `ux_ff`, `uz_ff`, `wx_ff` and `q_ff` = -ux^2 - uz wx (the Q / Okubo-Weiss criterion: positive in a
+        vortex core, negative in a shear layer), [nsteps, nx, nz] each.  One GPU only; u_ff, w_ff and ome_ff (and psi_ff,
+        omega_ff) are what they are without the flags."""
         scalars = [kind for kind, on in (('psi', psi), ('omega', omega)) if on]
         if scalars:
             if self._shard is not None and self._shard.world > 1:
                 raise ValueError("psi / omega fields run on one GPU: not with `distributed` or more than one device in `devices`")
             if not hasattr(self.engine, 'flowfield_scalar'):
                 raise RuntimeError("flowfield(psi=..., omega=...): this engine has no flowfield_scalar")
+        if grad:
+            if self._shard is not None and self._shard.world > 1:
+                raise ValueError("gradient fields run on one GPU: not with `distributed` or more than one device in `devices`")
+            if not hasattr(self.engine, 'flowfield_gradient'):
+                raise RuntimeError("flowfield(grad=True): this engine has no flowfield_gradient")
         x1, z1 = np.arange(xmin, xmax, dr), np.arange(zmin, zmax, dr)
         nx, nz = len(x1), len(z1)
         x, z = np.meshgrid(x1, z1, indexing='ij')
@@ -1702,6 +1827,7 @@ class LUDVM:
         w = np.zeros([nsteps, nx, nz])
         ome = np.zeros([nsteps, nx, nz])
         extra = {kind: np.zeros([nsteps, nx, nz]) for kind in scalars}
+        gradient = np.zeros([3, nsteps, nx, nz]) if grad else None
         fused = hasattr(self.engine, 'flowfield_vorticity')
         sh = self._shard if (self._shard is not None and self._shard.world > 1) else None
         ffp = 'f64' if self.precision == 'f64' else 'f32'
@@ -1737,6 +1863,9 @@ class LUDVM:
                 ome[ii] = self.engine.vorticity(uf, wf, dr)
             for kind in scalars:
                 extra[kind][ii] = self.engine.flowfield_scalar(kind, xmin, zmin, dr, nx, nz, g, xw, zw, self.v_core)
+            if grad:
+                gradient[0, ii], gradient[1, ii], gradient[2, ii] = self.engine.flowfield_gradient(xmin, zmin, dr, nx, nz, g, xw, zw,
+                                                                                                    self.v_core)
         self.x_ff, self.z_ff = x, z
         self.u_ff, self.w_ff = u, w
         self.ome_ff = ome
@@ -1744,4 +1873,7 @@ class LUDVM:
             self.psi_ff = extra['psi']
         if omega:
             self.omega_ff = extra['omega']
+        if grad:
+            self.ux_ff, self.uz_ff, self.wx_ff = gradient
+            self.q_ff = -self.ux_ff * self.ux_ff - self.uz_ff * self.wx_ff
         return None
