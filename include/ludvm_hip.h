@@ -569,6 +569,36 @@ int ludvm_march_set_survey_bins(ludvm_ctx* ctx, const int* bin_of_row, size_t ro
                                 const long long* counts);
 int ludvm_march_read_survey_bins(ludvm_ctx* ctx, double* sums, long long* counts);
 
+/* ---- gradient sums of the survey: mean vorticity, strain and Q inside the march (an addition to ABI 7: detect it by symbol) ----
+ *
+ * In a sampled step i the closed-form gradient of the same field (u, w)_i at the same survey points -- the raw sums A, B, C of
+ * ludvm_gradient_f64 (below) over the step's own sources [0, n + nfoil), added over the source splits in split order -- gives
+ *   ux = -A / pi,  e = B / (2 pi) (= (du/dz + dw/dx) / 2),  om = -v_core^4 C / pi (= dw/dx - du/dz),
+ *   Q = om^2 / 4 - ux^2 - e^2 (= -ux^2 - du/dz dw/dx)
+ * and five more raw float64 sums per point grow in step order: gsums[0..4][k] = sum ux, sum e, sum om, sum om^2, sum Q.  om is
+ * never formed as a difference of the two shear terms.  With bins, the sampled step's bin block bin_gsums[b][5][count] grows by
+ * the same five terms formed the same way.  The sample count and the bin counts are the velocity sums' own: no second counter.
+ * The gradient pair of kernels takes the place of the plain float64 pair under the same launch plan and does its arithmetic for
+ * u and w operation for operation; a sampled step still runs one partial kernel and ONE finisher.
+ *
+ * ludvm_march_set_survey_gradient: on = 1 makes the sampled steps carry the gradient sums.  Valid while a survey is set in
+ *   float64 precision: LUDVM_E_STATE when there is no survey, when the survey precision is 1, or when gsums is NULL although
+ *   the survey or one of its bins already has samples (one count has to serve both).  gsums is [5][count], or NULL (start from
+ *   zero); bin_gsums is [nbins][5][count], or NULL (start from zero) -- it is LUDVM_E_ARG when given without bins or without
+ *   gsums.  A flag other than 0 and 1 is LUDVM_E_ARG.  Every value is checked finite (LUDVM_E_ARG) before anything changes: a
+ *   refused call leaves the context as it was.  on = 0 removes the gradient sums (the other arguments are not looked at).
+ *   ludvm_march_set_survey, ludvm_march_set_survey_bins and ludvm_march_setup reset it to off: the call order is survey, bins,
+ *   gradient.  While it is on, ludvm_march_set_survey_precision(ctx, 1) is LUDVM_E_STATE and changes nothing.
+ * ludvm_march_read_survey_gradient: gsums[5][count] and -- bin_gsums not NULL -- bin_gsums[nbins][5][count] as they stand, at any
+ *   time after the set call.  LUDVM_E_STATE when the gradient sums are off; bin_gsums without bins is LUDVM_E_ARG.
+ * Guarantees: with the gradient sums on, everything ludvm_march_run produced before keeps its bits, the plain and the binned
+ *   velocity sums and their counts included; a context without the flag enqueues exactly what it enqueued before this entry
+ *   existed.  Bin b's gradient block equals, bit for bit, the plain gradient sums of a survey that samples exactly bin b's steps.
+ *   All sums repeat bit for bit however a run is cut into ludvm_march_run calls (carried over where the context is set up
+ *   again). */
+int ludvm_march_set_survey_gradient(ludvm_ctx* ctx, int on, const double* gsums, const double* bin_gsums);
+int ludvm_march_read_survey_gradient(ludvm_ctx* ctx, double* gsums, double* bin_gsums);
+
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *
  * A parameter sweep (LESPcrit, k, alpha_max, dt, a gust vortex, 'Faure' / 'Ramesh') is `members` independent simulations,

@@ -123,7 +123,8 @@ int ludvm_destroy(ludvm_ctx* c) {
                   c->probe_xz.p, c->probe_shift.p, c->probe_part.p, c->probe_out.p, c->tracer_seed.p, c->tracer_release.p,
                   c->tracer_shift.p, c->tracer_cur.p, c->tracer_part.p, c->tracer_out.p, c->tracer_F.p, c->tracer_grad_part.p,
                   c->tracer_F_out.p, c->survey_xz.p, c->survey_shift.p, c->survey_sums.p,
-                  c->survey_part.p, c->survey_bin_sums.p, c->ens_in.p, c->ens_work.p, c->ens_out.p};
+                  c->survey_part.p, c->survey_bin_sums.p, c->survey_gsums.p, c->survey_bin_gsums.p, c->survey_grad_part.p,
+                  c->ens_in.p, c->ens_work.p, c->ens_out.p};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   for (auto& e : c->march_ev)

@@ -144,6 +144,10 @@ struct ludvm_ctx {
   int survey_nbins = 0;                        // B (0: no bins)
   std::vector<int> survey_bin_of_row;          // [kinematics rows]
   std::vector<long long> survey_bin_samples;   // [B]
+  // gradient sums of the survey (ludvm_march_set_survey_gradient): five more raw sums per point [5][K], the bins' blocks
+  // [nbins][5][K] and the five-column partial slab of one sampled step; the sample counts are the velocity sums' own
+  Buf survey_gsums, survey_bin_gsums, survey_grad_part;
+  bool survey_gradient = false;
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

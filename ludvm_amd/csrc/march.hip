@@ -30,6 +30,7 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->survey_samples = 0;
   c->survey_precision = 0;
   c->survey_nbins = 0;      // ... and its bins (ludvm_march_set_survey_bins)
+  c->survey_gradient = false;
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -221,6 +222,28 @@ int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   const ObserverPlan p = observer_plan(kObserverRules[f32 ? kObsSurveyF32 : kObsSurvey], (long long)K, n_ub + (long long)m.npan);
   const double* pxz = static_cast<const double*>(c->survey_xz.p);
   const double* shift = step_shift(c->survey_shift, c->survey_shifted, s);
+  const int bin = c->survey_nbins ? c->survey_bin_of_row[(size_t)s] : -1;
+  if (c->survey_gradient) {
+    // the gradient pair takes the place of the plain pair under the same plan (float64: the setters see to it): the velocity
+    // sums keep their bits, the gradient sums and the five-column slab are further buffers of the survey's own
+    double* gslab = static_cast<double*>(c->survey_grad_part.p);
+    double* sums = static_cast<double*>(c->survey_sums.p);
+    double* gsums = static_cast<double*>(c->survey_gsums.p);
+    hipLaunchKernelGGL(march_grad_survey_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
+                       (long long)K, p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+                       static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, gslab);
+    HIPCHK(c, hipGetLastError());
+    if (bin >= 0)
+      hipLaunchKernelGGL(march_binned_grad_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)gslab,
+                         p.pad, p.nsplit, (long long)K, m.vc4, sums, gsums,
+                         static_cast<double*>(c->survey_bin_sums.p) + (size_t)bin * kSurveySums * K,
+                         static_cast<double*>(c->survey_bin_gsums.p) + (size_t)bin * kSurveySums * K);
+    else
+      hipLaunchKernelGGL(march_grad_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)gslab, p.pad,
+                         p.nsplit, (long long)K, m.vc4, sums, gsums);
+    HIPCHK(c, hipGetLastError());
+    return LUDVM_OK;
+  }
   double* slab = static_cast<double*>(c->survey_part.p);
   // (the two precisions' argument lists differ: the fp32 kernel's guard is in units of v_core)
   if (f32)
@@ -233,7 +256,6 @@ int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
                        static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, slab);
   HIPCHK(c, hipGetLastError());
   // a step with a bin: one finisher, as without bins, that also updates the bin's block (the host knows the step's bin)
-  const int bin = c->survey_nbins ? c->survey_bin_of_row[(size_t)s] : -1;
   if (bin >= 0)
     hipLaunchKernelGGL(march_binned_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.pad,
                        p.nsplit, (long long)K, static_cast<double*>(c->survey_sums.p),
@@ -297,6 +319,7 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
   c->survey_samples = 0;
   c->survey_precision = 0;         // float64 until ludvm_march_set_survey_precision says otherwise
   c->survey_nbins = 0;             // (and no bins until ludvm_march_set_survey_bins)
+  c->survey_gradient = false;      // (and no gradient sums until ludvm_march_set_survey_gradient)
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_sums, kSurveySums * count * 8));
@@ -317,7 +340,61 @@ int ludvm_march_set_survey_precision(ludvm_ctx* c, int precision) {
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
   if (precision != 0 && precision != 1) return fail(c, LUDVM_E_ARG, "march: survey precision is 0 (float64) or 1 (fp32)");
+  if (precision == 1 && c->survey_gradient) return fail(c, LUDVM_E_STATE, "march: the survey's gradient sums need a float64 survey");
   c->survey_precision = precision;
+  return LUDVM_OK;
+}
+
+int ludvm_march_set_survey_gradient(ludvm_ctx* c, int on, const double* gsums, const double* bin_gsums) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  if (on != 0 && on != 1) return fail(c, LUDVM_E_ARG, "march: the survey gradient flag is 0 or 1");
+  if (!on) {
+    c->survey_gradient = false;
+    return LUDVM_OK;
+  }
+  if (c->survey_precision != 0) return fail(c, LUDVM_E_STATE, "march: the survey's gradient sums need a float64 survey");
+  const size_t K = c->survey_count, B = (size_t)c->survey_nbins;
+  if (bin_gsums && B == 0) return fail(c, LUDVM_E_ARG, "march: survey bin gradient sums without survey bins");
+  if (bin_gsums && !gsums) return fail(c, LUDVM_E_ARG, "march: survey bin gradient sums come with the gradient sums");
+  if (!gsums) {
+    // one count serves the velocity and the gradient sums: sums that start from zero start with the survey
+    bool sampled = c->survey_samples != 0;
+    for (size_t b = 0; b < B; ++b) sampled = sampled || c->survey_bin_samples[b] != 0;
+    if (sampled) return fail(c, LUDVM_E_STATE, "march: the survey already has samples; its gradient sums must be given");
+  }
+  for (size_t k = 0; gsums && k < kSurveySums * K; ++k)
+    if (!std::isfinite(gsums[k])) return fail(c, LUDVM_E_ARG, "march: survey gradient sums must be finite");
+  for (size_t k = 0; bin_gsums && k < B * kSurveySums * K; ++k)
+    if (!std::isfinite(bin_gsums[k])) return fail(c, LUDVM_E_ARG, "march: survey bin gradient sums must be finite");
+  c->survey_gradient = false;      // (a failure from here on leaves the context without gradient sums)
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(ensure(c, c->survey_gsums, kSurveySums * K * 8));
+  if (B) CHK(ensure(c, c->survey_bin_gsums, B * kSurveySums * K * 8));
+  // (the five-column slab [split][5][k_pad] of kObsSurvey's plan: 5 / 2 of the plain one)
+  CHK(ensure(c, c->survey_grad_part, observer_slab_bytes(kObserverRules[kObsSurvey], (long long)K) / 2 * 5));
+  if (gsums) HIPCHK(c, hipMemcpyAsync(c->survey_gsums.p, gsums, kSurveySums * K * 8, hipMemcpyHostToDevice, c->stream));
+  else HIPCHK(c, hipMemsetAsync(c->survey_gsums.p, 0, kSurveySums * K * 8, c->stream));
+  if (B && bin_gsums)
+    HIPCHK(c, hipMemcpyAsync(c->survey_bin_gsums.p, bin_gsums, B * kSurveySums * K * 8, hipMemcpyHostToDevice, c->stream));
+  else if (B) HIPCHK(c, hipMemsetAsync(c->survey_bin_gsums.p, 0, B * kSurveySums * K * 8, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->survey_gradient = true;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_survey_gradient(ludvm_ctx* c, double* gsums, double* bin_gsums) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  if (!c->survey_gradient) return fail(c, LUDVM_E_STATE, "march: the survey's gradient sums are not on");
+  if (!gsums) return fail(c, LUDVM_E_ARG, "null array");
+  if (bin_gsums && c->survey_nbins == 0) return fail(c, LUDVM_E_ARG, "march: survey bin gradient sums without survey bins");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(gsums, c->survey_gsums.p, kSurveySums * c->survey_count * 8, hipMemcpyDeviceToHost, c->stream));
+  if (bin_gsums)
+    HIPCHK(c, hipMemcpyAsync(bin_gsums, c->survey_bin_gsums.p, (size_t)c->survey_nbins * kSurveySums * c->survey_count * 8,
+                             hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return LUDVM_OK;
 }
 
@@ -341,6 +418,7 @@ int ludvm_march_set_survey_bins(ludvm_ctx* c, const int* bin_of_row, size_t rows
     return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_SURVEY_BINS) + " survey bins");
   if (nbins == 0) {
     c->survey_nbins = 0;
+    c->survey_gradient = false;    // (the gradient sums are set after the bins)
     return LUDVM_OK;
   }
   if ((size_t)nbins * K > (size_t)LUDVM_MARCH_MAX_SURVEY_BIN_POINTS)
@@ -358,6 +436,7 @@ int ludvm_march_set_survey_bins(ludvm_ctx* c, const int* bin_of_row, size_t rows
   for (int b = 0; counts && b < nbins; ++b)
     if (counts[b] < 0) return fail(c, LUDVM_E_ARG, "march: survey bin counts must be >= 0");
   c->survey_nbins = 0;             // (a failure from here on leaves the context without bins)
+  c->survey_gradient = false;      // (the gradient sums are set after the bins)
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_bin_sums, doubles * 8));
   if (sums) HIPCHK(c, hipMemcpyAsync(c->survey_bin_sums.p, sums, doubles * 8, hipMemcpyHostToDevice, c->stream));

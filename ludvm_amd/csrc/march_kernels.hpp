@@ -1101,6 +1101,100 @@ march_binned_survey_finish(const double* slab, long long k_pad, int nsplit, long
   survey_add(bin_sums + m, count, u, w);
 }
 
+// ---- gradient sums of the survey (ludvm_march_set_survey_gradient) ----------------------------------------------------------------
+// In every sampled step the closed-form gradient of the same field at the same points (field_kernels.hpp; the raw sums A, B, C
+// of the tracers' deformation gradient above) gives
+//   ux = -A / pi     e = B / (2 pi) = (du/dz + dw/dx) / 2     om = -vc^4 C / pi     Q = om^2 / 4 - ux^2 - e^2 (= -ux^2 - uz wx)
+// and five more raw sums per point, gsums[0..4][k] = sum ux, sum e, sum om, sum om^2, sum Q: the mean vorticity, the mean strain,
+// the enstrophy and the vortex cores (Q > 0) of a run without a stored wake.  om is never formed as wx - uz: outside the cores
+// |B| >> vc^4 |C| and the difference would lose its digits.
+//
+// march_grad_survey_partial   march_survey_partial's loader and launch geometry (kObsSurvey: the same tiles, splits and chunk, so
+//                             the same summation order for u and w), field_grad_f64 as the body, five columns u | w | A | B | C
+//                             to a slab [split][5][k_pad] of its own.  A pad source (G = 0 at kPadPosD) adds exact zeros to all
+//                             five (field_grad_f64); a lane without a point walks along at kPadPosD and stores nothing
+// march_grad_survey_finish    one lane per point: splits 0, 1, 2, ... in that order for all five columns, survey_add on `sums` with
+//                             the (u, w) that march_survey_finish forms (the velocity sums keep their bits), then the five terms
+//                             above into gsums with plain loads and stores
+// march_binned_grad_survey_finish  the same for a sampled step that has a bin, launched in its place: `sums` and `gsums`, then the
+//                             same terms into the bin's two blocks: a bin's gradient block is, bit for bit, the plain gradient
+//                             sums of a survey that samples that bin's steps alone
+// Still one partial kernel and ONE finisher per sampled step; the sample count and the bin counts are the velocity sums' own.
+__global__ void __launch_bounds__(kBlock)
+march_grad_survey_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, long long count,
+                          long long k_pad, const double* __restrict__ xs, const double* __restrict__ zs,
+                          const double* __restrict__ gs, const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
+  __builtin_amdgcn_s_setprio(3);
+  const SplitRange src = split_range(S, nfoil, chunk);
+  double xp[kSurveyPerLane], zp[kSurveyPerLane], au[kSurveyPerLane], aw[kSurveyPerLane];
+  double ga[kSurveyPerLane], gb[kSurveyPerLane], gc[kSurveyPerLane];
+  load_fixed_points<kSurveyPerLane, kBlock>(px, pz, shift, count, kPadPosD, xp, zp, au, aw);
+#pragma unroll
+  for (int k = 0; k < kSurveyPerLane; ++k) { ga[k] = 0.0; gb[k] = 0.0; gc[k] = 0.0; }
+  field_grad_f64<kSurveyPerLane, kBlock, 2>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw, ga, gb, gc);
+  double* row = slab + (long long)blockIdx.y * 5 * k_pad;
+#pragma unroll
+  for (int k = 0; k < kSurveyPerLane; ++k) {
+    const long long m = observer_point<kSurveyPerLane, kBlock>(k);
+    if (m < count) {
+      row[m] = au[k] * kInv2PiD;
+      row[k_pad + m] = -aw[k] * kInv2PiD;
+      row[2 * k_pad + m] = ga[k];
+      row[3 * k_pad + m] = gb[k];
+      row[4 * k_pad + m] = gc[k];
+    }
+  }
+}
+
+// point m's sample of a five-column slab: (u, w) as split_sums forms them and the gradient's terms, splits 0, 1, 2, ... in order
+struct GradSample { double u, w, ux, e, om; };
+__device__ __forceinline__ GradSample grad_split_sums(const double* slab, long long pad, int nsplit, long long m, double vc4) {
+  double u = 0.0, w = 0.0, A = 0.0, B = 0.0, C = 0.0;
+  const double* c0 = slab + m;
+  for (int sidx = 0; sidx < nsplit; ++sidx) {
+    const double* cs = c0 + (long long)sidx * 5 * pad;
+    u += cs[0];
+    w += cs[pad];
+    A += cs[2 * pad];
+    B += cs[3 * pad];
+    C += cs[4 * pad];
+  }
+  return {u, w, -A * kInvPiD, B * kInv2PiD, -(vc4 * C) * kInvPiD};
+}
+
+// one sample (ux, e, om) of a point into its five gradient sums g[0..4][count] (g: at the point's column), in survey_add's style
+__device__ __forceinline__ void survey_grad_add(double* g, long long count, double ux, double e, double om) {
+  const double q = __builtin_fma(-e, e, __builtin_fma(-ux, ux, 0.25 * (om * om)));
+  g[0] += ux;
+  g[count] += e;
+  g[2 * count] += om;
+  g[3 * count] = __builtin_fma(om, om, g[3 * count]);
+  g[4 * count] += q;
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_grad_survey_finish(const double* slab, long long k_pad, int nsplit, long long count, double vc4, double* sums, double* gsums) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (m >= count) return;
+  const GradSample s = grad_split_sums(slab, k_pad, nsplit, m, vc4);
+  survey_add(sums + m, count, s.u, s.w);
+  survey_grad_add(gsums + m, count, s.ux, s.e, s.om);
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_binned_grad_survey_finish(const double* slab, long long k_pad, int nsplit, long long count, double vc4, double* sums,
+                                double* gsums, double* bin_sums, double* bin_gsums) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long m = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (m >= count) return;
+  const GradSample s = grad_split_sums(slab, k_pad, nsplit, m, vc4);
+  survey_add(sums + m, count, s.u, s.w);
+  survey_grad_add(gsums + m, count, s.ux, s.e, s.om);
+  survey_add(bin_sums + m, count, s.u, s.w);
+  survey_grad_add(bin_gsums + m, count, s.ux, s.e, s.om);
+}
+
 // ---- the tracers' field in hi+lo fp32 (ludvm_march_set_tracer_precision) ---------------------------------------------------------
 // The same quantity as march_tracer_partial into the same slab, with the pair arithmetic in fp32 on hi+lo positions (pair_f32<...,
 // HILO = true>'s inner loop) and everything around it in float64.  It reads the float64 master arrays and splits them itself

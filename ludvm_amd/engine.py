@@ -591,6 +591,41 @@ class Engine:
         self._check(self._lib.ludvm_march_read_survey(self._ctx, _pd(sums), byref(n)))
         return sums, int(n.value)
 
+    def march_set_survey_gradient(self, on=True, gsums=None, bin_gsums=None):
+        """Gradient sums of the survey (ludvm_march_set_survey_gradient): every sampled step also adds ux, e = (uz + wx) / 2,
+        omega, omega^2 and Q = omega^2 / 4 - ux^2 - e^2 of the closed-form gradient at the survey points to five more raw
+        float64 sums per point -- and, with bins, to the step's bin block.  gsums [5, K] and bin_gsums [nbins, 5, K] continue a
+        run (what `march_survey_gradient` returned); None starts from zero.  Valid while a float64 survey is set, after
+        `march_set_survey` and `march_set_survey_bins`, which forget it."""
+        if not hasattr(self._lib, "ludvm_march_set_survey_gradient"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_survey_gradient")
+        code = int(on) if isinstance(on, (bool, int, np.integer)) else None
+        if code is None:
+            raise ValueError("march_set_survey_gradient: on is a flag (or the library's code)")
+        K, B = getattr(self, "_march_nsurvey", 0), getattr(self, "_march_nbins", 0)
+        g = bg = None
+        if gsums is not None:
+            g = np.ascontiguousarray(gsums, dtype=np.float64)
+            if g.shape != (5, K):
+                raise ValueError("march_set_survey_gradient: gsums must be [5, K]")
+        if bin_gsums is not None:
+            bg = np.ascontiguousarray(bin_gsums, dtype=np.float64)
+            if bg.ndim != 3 or bg.shape[1:] != (5, K) or (B and bg.shape[0] != B):
+                raise ValueError("march_set_survey_gradient: bin_gsums must be [nbins, 5, K]")
+        self._check(self._lib.ludvm_march_set_survey_gradient(self._ctx, code, _pd(g), _pd(bg)))
+
+    def march_survey_gradient(self):
+        """(gsums float64 [5, K], bin_gsums float64 [B, 5, K] or None without bins): the survey's gradient sums -- ux, e, omega,
+        omega^2, Q per point -- as they stand (ludvm_march_read_survey_gradient); their counts are `march_survey`'s and
+        `march_survey_bins`'s."""
+        if not hasattr(self._lib, "ludvm_march_read_survey_gradient"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_read_survey_gradient")
+        K, B = getattr(self, "_march_nsurvey", 0), getattr(self, "_march_nbins", 0)
+        g = np.empty([5, K])
+        bg = np.empty([B, 5, K]) if B else None
+        self._check(self._lib.ludvm_march_read_survey_gradient(self._ctx, _pd(g), _pd(bg)))
+        return g, bg
+
     @staticmethod
     def march_anchor_steps(first_step):
         """The four steps whose wake sizes ludvm_march_run wants in `anchors` for a call that begins at first_step."""

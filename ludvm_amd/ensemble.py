@@ -72,6 +72,9 @@ def _check_case(idx, kw, first):
     if "tracer_gradient" in kw:
         raise ValueError(who + f"tracer_gradient={kw['tracer_gradient']!r}: the tracers of a sweep carry no deformation gradient (run "
                          "the member on its own, LUDVM(..., tracers=..., tracer_gradient=True))")
+    if "survey_gradient" in kw:
+        raise ValueError(who + f"survey_gradient={kw['survey_gradient']!r}: the survey of a sweep carries no gradient sums (run the "
+                         "member on its own, LUDVM(..., survey=..., survey_gradient=True))")
     for key, (fine, why) in _REFUSED.items():
         if key in kw and not (kw[key] is fine or (fine is not None and kw[key] == fine)):
             raise ValueError(who + f"{key}={kw[key]!r}: {why}")
@@ -234,7 +237,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     ensemble_run_traced, and tracer records (16 bytes x members x (recorded steps + 1) x M) over 1 GiB; `survey` / `survey_steps` /
     survey_frame='tunnel' inside a member's dict (they belong to the sweep), more than 4096 survey points, points that are not
     finite, a survey_frame other than 'lab' / 'tunnel', survey_steps that are not three integers with first >= 1 and every >= 1
-    or that hold no step of some member (named), survey_steps without `survey`, `survey_precision`, `tracer_precision` or `tracer_gradient` anywhere (the sweep's or a member's), an engine without
+    or that hold no step of some member (named), survey_steps without `survey`, `survey_precision`, `tracer_precision`, `tracer_gradient` or `survey_gradient` anywhere (the sweep's or a member's), an engine without
     ensemble_run_surveyed, and
     survey sums (40 bytes x members x K) over 1 GiB: split the case list.
 
@@ -249,6 +252,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     if "tracer_gradient" in common:
         raise ValueError(f"sweep: tracer_gradient={common['tracer_gradient']!r}: the tracers of a sweep carry no deformation gradient "
                          "(run a member on its own, LUDVM(..., tracers=..., tracer_gradient=True))")
+    if "survey_gradient" in common:
+        raise ValueError(f"sweep: survey_gradient={common['survey_gradient']!r}: the survey of a sweep carries no gradient sums "
+                         "(run a member on its own, LUDVM(..., survey=..., survey_gradient=True))")
     for key in ("survey_bins", "survey_period", "survey_phase0"):
         if common.get(key) is not None:
             raise ValueError(f"sweep: {key}={common[key]!r}: binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)")

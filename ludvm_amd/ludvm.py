@@ -194,6 +194,20 @@ class LUDVM:
       survey_period  the period, a time, of the int form of `survey_bins`; default 1 / self.f, the period of the motion (refused
                  when that is infinite, and when not finite and positive)
       survey_phase0  the time of phase 0 of the int form of `survey_bins`; default t0
+      survey_gradient  False (default).  True: every sampled step also adds the closed-form gradient of the survey's field at the
+                 survey points to five more raw float64 sums per point, ux = du/dx, e = (du/dz + dw/dx) / 2, omega = dw/dx - du/dz,
+                 omega^2 and Q = omega^2 / 4 - ux^2 - e^2 (= -ux^2 - uz wx; Q > 0 marks a vortex core) -- inside the device-resident
+                 march, under the plain survey's launch plan, so every velocity sum keeps its bits -- and, with `survey_bins`, to
+                 the step's bin block.  Results, shaped like `survey_x`: `survey_grad_sums` [5, ...], `survey_mean_ux`,
+                 `survey_mean_strain` (mean e), `survey_mean_omega`, `survey_mean_uz` = mean e - mean omega / 2, `survey_mean_wx`
+                 = mean e + mean omega / 2, `survey_omega2` (sum omega^2 / n: twice the mean enstrophy), `survey_omega_var`,
+                 `survey_mean_q`, and `survey_production` = -(uu ux + uw 2 e - ww ux), the production of fluctuation energy from
+                 the survey's own Reynolds stresses and these means (dw/dz = -du/dx).  With bins: `survey_bin_grad_sums`
+                 [B, 5, ...], `survey_bin_mean_ux`, `_strain`, `_omega`, `_q`, `survey_bin_omega2`, and `survey_coherent_omega2` /
+                 `survey_random_omega2`, the variance of omega split as the velocity moments are.  The counts are the velocity
+                 sums' own.  The sums are bit-identical however the run is cut, checkpoints included.  The
+                 per-step path (march=False) adds the same terms from `Engine.gradient_field`.  Refused: not a bool, without
+                 `survey`, with survey_precision='f32', in a sweep, with `devices` > 1 or `distributed`
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -224,6 +238,10 @@ class LUDVM:
                 if kwargs.get('tracers') is not None:
                     cls._check_tracers(kwargs['tracers'], kwargs.get('tracer_release'), kwargs.get('tracer_frame', 'lab'))
                     raise ValueError("tracers run on one GPU: not with more than one device in `devices`")
+                if kwargs.get('survey_gradient', False) is not False:
+                    cls._check_survey_gradient(kwargs['survey_gradient'], kwargs.get('survey') is not None,
+                                               kwargs.get('survey_precision', 'f64'))
+                    raise ValueError("survey_gradient runs on one GPU: not with more than one device in `devices`")
                 if kwargs.get('survey') is not None:
                     cls._check_survey(kwargs['survey'], kwargs.get('survey_frame', 'lab'), kwargs.get('survey_steps'))
                     raise ValueError("a survey runs on one GPU: not with more than one device in `devices`")
@@ -391,6 +409,18 @@ class LUDVM:
             raise ValueError(f"tracer_gradient needs float64 tracers: not with tracer_precision={tracer_precision!r}")
 
     @staticmethod
+    def _check_survey_gradient(survey_gradient, surveyed, survey_precision='f64'):
+        """ValueError from the keywords alone (nothing else has been created yet)."""
+        if not isinstance(survey_gradient, (bool, np.bool_)):
+            raise ValueError(f"survey_gradient must be True or False (got {survey_gradient!r})")
+        if not survey_gradient:
+            return
+        if not surveyed:
+            raise ValueError("survey_gradient needs `survey`")
+        if survey_precision != 'f64':
+            raise ValueError(f"survey_gradient needs a float64 survey: not with survey_precision={survey_precision!r}")
+
+    @staticmethod
     def ftle_from_F(F, T):
         """Finite-time Lyapunov exponent ln sigma_max(F) / T of deformation gradients F [4, ...] (F11, F12, F21, F22) over the
         times T (a number or an array of the trailing shape): sigma_max^2 = (|F|^2 + sqrt(|F|^4 - 4 det^2)) / 2 with |F| the
@@ -462,7 +492,7 @@ class LUDVM:
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
                  probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
                  survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64', tracer_precision='f64',
-                 survey_bins=None, survey_period=None, survey_phase0=None, tracer_gradient=False):
+                 survey_bins=None, survey_period=None, survey_phase0=None, tracer_gradient=False, survey_gradient=False):
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -494,6 +524,9 @@ class LUDVM:
             raise ValueError("survey_frame must be 'lab' or 'tunnel'")
         elif survey_steps is not None:
             raise ValueError("survey_steps needs `survey`")
+        self._check_survey_gradient(survey_gradient, survey is not None, survey_precision)
+        if survey_gradient and distributed is not None and distributed is not False:
+            raise ValueError("survey_gradient runs on one GPU: not with `distributed`")
         self._check_survey_precision(survey_precision, survey is not None, march)
         binned = survey_bins is not None or survey_period is not None or survey_phase0 is not None
         if binned:
@@ -542,6 +575,9 @@ class LUDVM:
                                   survey_period=None if survey_period is None else float(survey_period),
                                   survey_phase0=None if survey_phase0 is None else float(survey_phase0))
                 self.survey_nbins, self.survey_bin_of_step, self.survey_phase = bin_count, bin_table, bin_phase
+            self.survey_gradient = bool(survey_gradient)
+            if self.survey_gradient:                # (a survey without it likewise)
+                self._ctor.update(survey_gradient=True)
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -859,6 +895,8 @@ class LUDVM:
                 self._survey_results(*(eng.march_survey() if S.can_march else (S.ssums, S.scount)))
             if S.sbins is not None:
                 self._survey_bin_results(*(eng.march_survey_bins() if S.can_march else (S.sbsums, S.sbcounts)))
+            if S.sgsums is not None:        # (after the velocity results: the counts and the Reynolds stresses are theirs)
+                self._survey_gradient_results(*(eng.march_survey_gradient() if S.can_march else (S.sgsums, S.sbgsums)))
         finally:
             if self._shard is not None:
                 self._shard.detach(eng)
@@ -872,7 +910,7 @@ class LUDVM:
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
             'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
-            'tracers', 'trec', 'tcur', 'tF', 'survey', 'ssums', 'scount', 'sbins', 'sbsums', 'sbcounts',
+            'tracers', 'trec', 'tcur', 'tF', 'survey', 'ssums', 'scount', 'sbins', 'sbsums', 'sbcounts', 'sgsums', 'sbgsums',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
 
@@ -995,6 +1033,12 @@ class LUDVM:
             # likewise for the bins: [B][5][K] and the samples of every bin
             S.sbsums = np.zeros([self.survey_nbins, 5, S.survey.shape[1]])
             S.sbcounts = np.zeros(self.survey_nbins, dtype=np.int64)
+        S.sgsums = S.sbgsums = None
+        if S.survey is not None and self.survey_gradient:
+            # likewise for the gradient sums [5][K] and their bin blocks [B][5][K] (the counts are the velocity sums' own)
+            S.sgsums = np.zeros([5, S.survey.shape[1]])
+            if S.sbins is not None:
+                S.sbgsums = np.zeros([self.survey_nbins, 5, S.survey.shape[1]])
         return S
 
     def _survey_sampled(self, step):
@@ -1042,6 +1086,39 @@ class LUDVM:
             self.survey_random_uu = (nb * self.survey_bin_uu[full]).sum(axis=0) / N
             self.survey_random_ww = (nb * self.survey_bin_ww[full]).sum(axis=0) / N
             self.survey_random_uw = (nb * self.survey_bin_uw[full]).sum(axis=0) / N
+
+    def _survey_gradient_results(self, gsums, bin_gsums):
+        """The gradient survey's attributes from the raw sums [5, K] and -- with bins -- [B, 5, K]; the counts, the Reynolds
+        stresses and the bins' decomposition weights are the velocity survey's (`_survey_results`, `_survey_bin_results`)."""
+        shape, n = self._survey_shape, self.survey_count
+        self.survey_grad_sums = np.array(gsums, dtype=np.float64).reshape((5,) + shape)
+        sux, se, som, som2, sq = self.survey_grad_sums
+        with np.errstate(divide='ignore', invalid='ignore'):       # (n = 0: a run that stopped before its window)
+            ux, e, om = sux / n, se / n, som / n
+            self.survey_mean_ux, self.survey_mean_strain, self.survey_mean_omega = ux, e, om
+            self.survey_mean_uz, self.survey_mean_wx = e - 0.5 * om, e + 0.5 * om
+            self.survey_omega2, self.survey_mean_q = som2 / n, sq / n
+            self.survey_omega_var = self.survey_omega2 - om * om
+            # -<u_i' u_j'> dU_i/dx_j with dw/dz = -du/dx and du/dz + dw/dx = 2 e
+            self.survey_production = -(self.survey_uu * ux + self.survey_uw * (2.0 * e) - self.survey_ww * ux)
+        if bin_gsums is None:
+            return
+        B = self.survey_nbins
+        self.survey_bin_grad_sums = np.array(bin_gsums, dtype=np.float64).reshape((B, 5) + shape)
+        nb_all = self.survey_bin_count.reshape((B,) + (1,) * len(shape)).astype(np.float64)
+        bux, be, bom, bom2, bq = (self.survey_bin_grad_sums[:, c] for c in range(5))
+        with np.errstate(divide='ignore', invalid='ignore'):       # (an empty bin: nan)
+            self.survey_bin_mean_ux, self.survey_bin_mean_strain = bux / nb_all, be / nb_all
+            self.survey_bin_mean_omega, self.survey_bin_mean_q = bom / nb_all, bq / nb_all
+            self.survey_bin_omega2 = bom2 / nb_all
+        N = float(self.survey_bin_count.sum())
+        full = self.survey_bin_count > 0
+        nb = nb_all[full]
+        with np.errstate(divide='ignore', invalid='ignore'):       # (N = 0: a run that stopped before its first binned step)
+            to = bom[full].sum(axis=0) / N                         # the mean of the binned samples
+            mo = self.survey_bin_mean_omega[full]
+            self.survey_coherent_omega2 = (nb * (mo - to) * (mo - to)).sum(axis=0) / N
+            self.survey_random_omega2 = (nb * (self.survey_bin_omega2[full] - mo * mo)).sum(axis=0) / N
 
     def _tracer_seeds(self, step):
         """Lab coordinates [2, M] of the seeds at time step `step` ('tunnel' frame: x + xpiv[step])."""
@@ -1105,6 +1182,10 @@ class LUDVM:
             S.ssums, S.scount = R['survey_sums'].copy(), int(R['survey_samples'])
         if S.sbins is not None:
             S.sbsums, S.sbcounts = R['survey_bin_sums'].copy(), R['survey_bin_counts'].astype(np.int64)
+        if S.sgsums is not None:
+            S.sgsums = R['survey_grad_sums'].copy()
+            if S.sbgsums is not None:
+                S.sbgsums = R['survey_bin_grad_sums'].copy()
         for key in ('TEV', 'LEV', 'FREE'):
             if self.history == 'full':
                 P[key][:S.first_step] = R['path_' + key]
@@ -1136,6 +1217,10 @@ class LUDVM:
         f32_survey = S.survey is not None and self.survey_precision == 'f32'
         if f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_precision'):
             raise RuntimeError("survey_precision='f32': this engine marches but has no march_set_survey_precision")
+        grad_survey = S.sgsums is not None
+        if grad_survey and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_gradient'):
+            raise RuntimeError("survey_gradient: this engine marches but has no march_set_survey_gradient (pass march=False for the "
+                               "per-step path)")
         # preallocated host buffers for the two device calls of a step (engines that offer them)
         S.sb = eng.step_buffers(npan) if hasattr(eng, 'step_buffers') else None
         S.prec_code = {'f32': 0, 'f32x2': 1, 'f64': 2}[self.precision]
@@ -1165,6 +1250,13 @@ class LUDVM:
                     carried = bool(S.sbcounts.any())
                     eng.march_set_survey_bins(S.sbins, self.survey_nbins, sums=S.sbsums if carried else None,
                                               counts=S.sbcounts if carried else None)
+                if grad_survey:
+                    # (after the survey and its bins, which forget it; sums that are carried go together with their counts)
+                    carried = bool(S.scount) or (S.sbins is not None and bool(S.sbcounts.any()))
+                    eng.march_set_survey_gradient(True, gsums=S.sgsums if carried else None,
+                                                  bin_gsums=S.sbgsums if carried else None)
+        if grad_survey and not S.can_march and not hasattr(eng, 'gradient_field'):
+            raise RuntimeError("survey_gradient: the per-step path needs an engine with gradient_field")
         if f32_tracers and not S.can_march:
             # (no float64 in its place: the per-step path has no fp32 tracer sums)
             raise RuntimeError("tracer_precision='f32x2' is evaluated inside the device-resident march, which this run cannot take "
@@ -1541,6 +1633,20 @@ class LUDVM:
                 for acc, term in zip(S.sbsums[S.sbins[i]], (u, w, u * u, w * w, u * w)):
                     acc += term
                 S.sbcounts[S.sbins[i]] += 1
+            if S.sgsums is not None:
+                # the gradient of that field over the step's sources in their order -- old wake, shed vortices, bound vortices --
+                # in one call, and the five terms ux, e, omega, omega^2, Q.  gradient_field returns the two shear terms, so omega
+                # is their difference here: its absolute error is an ulp of |uz|, far inside what the sums are compared to
+                wx_, wz_, wg_ = eng.wake_read(0, n_wake, gamma=True) if n_wake else (np.empty(0),) * 3
+                ux, uz, wx = eng.gradient_field(np.concatenate([wg_, new_g[:ns], dGamma]), np.concatenate([wx_, new_x[:ns], xg]),
+                                                np.concatenate([wz_, new_z[:ns], zg]), px, pz, vc)
+                e, om = 0.5 * (uz + wx), wx - uz
+                terms = (ux, e, om, om * om, 0.25 * (om * om) - ux * ux - e * e)
+                for acc, term in zip(S.sgsums, terms):
+                    acc += term
+                if S.sbgsums is not None and S.sbins[i] >= 0:
+                    for acc, term in zip(S.sbgsums[S.sbins[i]], terms):
+                        acc += term
         n_after = n_wake + len(new_x)
         one_trip = (not record) and sb is not None and i < nt - 1 and hasattr(eng, 'wake_step_into')
         if not one_trip:
@@ -1648,6 +1754,11 @@ class LUDVM:
             d['survey_sums'], d['survey_samples'] = self.engine.march_survey() if S.can_march else (S.ssums, S.scount)
         if S.sbins is not None:         # (likewise; the sums and the samples of every bin so far)
             d['survey_bin_sums'], d['survey_bin_counts'] = self.engine.march_survey_bins() if S.can_march else (S.sbsums, S.sbcounts)
+        if S.sgsums is not None:        # (likewise; the gradient sums, whose counts are the two above)
+            g, bg = self.engine.march_survey_gradient() if S.can_march else (S.sgsums, S.sbgsums)
+            d['survey_grad_sums'] = g
+            if bg is not None:
+                d['survey_bin_grad_sums'] = bg
         if self.history == 'full':
             for key in ('TEV', 'LEV', 'FREE'):
                 d['path_' + key] = P[key][:next_step]
