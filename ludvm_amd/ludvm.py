@@ -670,8 +670,11 @@ class LUDVM:
             warnings.warn("LUDVM: the mean line of a cambered NACA section / a .dat file is restated from the published "
                           "NACA 4-digit formula (or the averaged surfaces of the file); the reference takes it from the PyPI "
                           "package `airfoils` (LUDVM.py:301-335: mean of the interpolated surfaces), which is not available "
-                          "to this build -- parity with the reference is UNPINNED for this section (symmetric 00xx sections "
-                          "are pinned).", RuntimeWarning, stacklevel=3)
+                          "to this build -- the mean line itself (that package's point distribution and formula) and .dat "
+                          "sections are UNPINNED.  Everything downstream of a NACA 4-digit mean line -- interpolation, slopes, "
+                          "the camber terms of downwash and solve, the bound-vortex positions, the loads, the flow field -- is "
+                          "pinned to the reference on the published mean line (fixture group G10); symmetric 00xx sections "
+                          "are pinned throughout.", RuntimeWarning, stacklevel=3)
         if from_file:
             xa, etaa = self._mean_line_from_dat(filename, Npoints)
         else:

@@ -27,8 +27,14 @@ Fixture groups:
                          every edge of the sweep's and the march's chord-sum lane arithmetic, 4 .. 64 Fourier coefficients,
                          free-vortex counts around the source tiles, and a wake that fills a sweep member's slab exactly.
                              python oracle/gen_golden.py g9    # this group alone
+  G10 off-unit runs   -- the unmodified reference class run on the cases of oracle/g10_cases.py: chord, Uinf and rho pairwise
+                         different and none of them 1, other kinematics, and cambered NACA 4-digit sections; every
+                         airfoil_downwash call of three steps and a flow field of one cambered dimensional case.
+                             python oracle/gen_golden.py g10   # this group alone
 G2-G5 and G9 run the unmodified reference class with oracle/airfoils_standin on sys.path (zero camber,
-valid for the symmetric NACA0012 all BASELINE configs use).
+valid for the symmetric NACA0012 all BASELINE configs use).  G10 alone switches the stand-in's opt-in mean line on
+(airfoils.MEAN_LINE = oracle.ludvm_oracle.naca4_camber, the published NACA 4-digit mean line): this pins everything the
+reference does downstream of the mean line, not the mean line the PyPI package would hand over, and not .dat sections.
 """
 import os
 import sys
@@ -123,11 +129,12 @@ CONFIG1 = dict(t0=0, tf=20, dt=5e-2, chord=1, rho=1.225, Uinf=1, Npoints=81, Nco
 
 
 class Spy:
-    """Records every induced_velocity call of selected time steps (G3)."""
+    """Records every induced_velocity call (G3) and every airfoil_downwash call (G10) of selected time steps."""
 
     def __init__(self, steps):
         self.steps = set(steps)
         self.calls = []
+        self.downwash = []
         self.step = None
 
 
@@ -149,7 +156,10 @@ def run_reference(kwargs, spy=None):
 
     def dw(self, circulation, xw, zw, i):
         spy.step = i
-        return orig_dw(self, circulation, xw, zw, i)
+        W = orig_dw(self, circulation, xw, zw, i)
+        if i in spy.steps:
+            spy.downwash.append(dict(step=i, g=np.array(circulation, dtype=float), xw=np.array(xw), zw=np.array(zw), W=W.copy()))
+        return W
 
     cls.induced_velocity = iv
     cls.airfoil_downwash = dw
@@ -310,7 +320,45 @@ def g9_edge_runs():
     print("G9:", len(G9.CASES), "cases,", os.path.getsize(path), "bytes")
 
 
+def g10_off_unit_runs():
+    """The G10 cases (oracle/g10_cases.py): loads, LESP, circulations, A0 .. A3 and the wake after the last step per case, the
+    section's tables of the cambered ones; every airfoil_downwash call of three steps and the flow field of c4412d."""
+    import time
+    if ROOT not in sys.path:
+        sys.path.append(ROOT)
+    import airfoils
+    from oracle import g10_cases as G10
+    from oracle.ludvm_oracle import naca4_camber
+    t0 = time.time()
+    flat = {}
+    airfoils.MEAN_LINE = naca4_camber
+    try:
+        for c in G10.CASES:
+            spy = Spy(G10.SPY_STEPS) if c["name"] == G10.SPY_CASE else None
+            sim = run_reference(G10.kwargs(c), spy)
+            for k, v in G10.pack(sim, c).items():
+                flat[f"{G10.key(c)}/{k}"] = v
+            if spy is not None:
+                flat["downwash/ncalls"] = np.array(len(spy.downwash))
+                for n, call in enumerate(spy.downwash):
+                    for k, v in call.items():
+                        flat[f"downwash/{n}_{k}"] = v
+            if c["name"] == G10.FIELD_CASE:
+                for s, (xmin, xmax, zmin, zmax, dr) in G10.FIELD_BOXES.items():
+                    quiet(sim.flowfield, xmin=xmin, xmax=xmax, zmin=zmin, zmax=zmax, dr=dr, tsteps=[s])
+                    flat[f"field/{s}"] = np.stack([sim.x_ff, sim.z_ff, sim.u_ff[0], sim.w_ff[0], sim.ome_ff[0]])
+            print(f"G10 {G10.key(c)}: nt {sim.nt} itev {sim.itev} ilev {sim.ilev}  ({time.time() - t0:.0f} s)", flush=True)
+    finally:
+        airfoils.MEAN_LINE = None
+    path = os.path.join(OUT, "g10_off_unit_runs.npz")
+    np.savez_compressed(path, **flat)
+    print("G10:", len(G10.CASES), "cases,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "g10":
+        g10_off_unit_runs()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "g9":
         g9_edge_runs()
         sys.exit(0)
@@ -327,5 +375,6 @@ if __name__ == "__main__":
     g7_config2_regime()
     g8_fp32_routes()
     g9_edge_runs()
+    g10_off_unit_runs()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("total fixture bytes:", tot)

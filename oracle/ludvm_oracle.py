@@ -9,8 +9,12 @@ Pinned against the reference: tests/test_oracle_golden.py checks every function 
 golden vectors under tests/golden/, which oracle/gen_golden.py produced by importing and running
 the unmodified reference in the build container (kernel KATs, the config-1 run, the per-call
 boundary trace, the flow field, and the Ramesh / free-vortex / alpha_m variants).
-Unpinned: cambered NACA digits and .dat sections (the reference takes those from the PyPI package
-`airfoils`, absent here; naca4_camber() below restates the published NACA 4-digit formula).
+Cambered NACA 4-digit sections: everything downstream of the mean line is pinned to the reference by
+fixture group G10 (oracle/g10_cases.py, tests/test_g10_fixture.py), on the published 4-digit mean
+line naca4_camber() below states -- interpolation, slopes, the camber terms of downwash and solve,
+the bound-vortex positions, the loads and the flow field.  Unpinned: the mean line itself (the
+reference takes it from the PyPI package `airfoils`, absent here: that package's point distribution
+and formula) and .dat sections.
 
 Citations are file:line into /root/reference/LUDVM.py.
 """
