@@ -24,6 +24,7 @@ ap.add_argument("--tf", type=float, default=20.0)
 ap.add_argument("--dt", type=float, default=5e-2)
 ap.add_argument("--release-at", type=float, default=0.5, help="fraction of the run after which the mesh is released")
 ap.add_argument("--dr", type=float, default=0.05, help="spacing of the tracer mesh")
+ap.add_argument("--f32x2", action="store_true", help="the Q snapshot's gradient sums in hi+lo fp32 (field_precision='f32x2')")
 ap.add_argument("--plot", default=None, help="write the FTLE field and the Q snapshot to this PNG")
 args = ap.parse_args()
 
@@ -49,7 +50,7 @@ for i in range(0, len(x1), max(1, len(x1) // 20)):
 # the Eulerian reading of the same window at the release step
 x0 = sim.xpiv[release]
 window = dict(xmin=x0 + x1[0], xmax=x0 + x1[-1] + args.dr / 2, zmin=z1[0], zmax=z1[-1] + args.dr / 2)
-sim.flowfield(**window, dr=args.dr, tsteps=[release], grad=True)
+sim.flowfield(**window, dr=args.dr, tsteps=[release], grad=True, field_precision="f32x2" if args.f32x2 else "f64")
 q = sim.q_ff[0]
 print(f"Q at step {release}: in [{q.min():+.2f}, {q.max():+.2f}]; {100 * (q > 0).mean():.1f} % of the window rotation-dominated")
 

@@ -845,6 +845,37 @@ int ludvm_flowfield_gradient_rows_f64(ludvm_ctx* ctx, double xmin, double zmin, 
                                       size_t row_first, size_t row_count, const double* xs, const double* zs,
                                       const double* gs, size_t ns, double vcore, double* ux, double* uz, double* wx);
 
+/* ---- analytic vorticity and velocity gradient in hi+lo fp32 (an addition to ABI 7: detect it by symbol) ------------
+ * LUDVM_FIELD_OMEGA of ludvm_scalar_f64 with the pair arithmetic in fp32: float64 arrays in and out, the same arguments.  Every
+ * float64 coordinate is split into hi = (float)v and lo = (float)(v - hi); a difference is (hi_p - hi_s) + (lo_p - lo_s) and the
+ * pair is fp32 from there (one unrefined reciprocal square root, G and vcore^4 rounded to float).  The sources go in tiles of 256
+ * from the split's first one; within a tile the even sources are added in one fp32 accumulator and the odd ones in another, and
+ * at the tile's end the even sum, then the odd sum, joins the target's float64 total.  No origins and no fall-back: the error is
+ * about 1e-7 of the field's maximum (<= 2e-6, the hi+lo tier) wherever the sources lie.  The splits are a function of the target
+ * and source counts alone and are added in split order: results repeat bit for bit.  nt = 0 is a no-op, ns = 0 writes zeros.
+ * LUDVM_E_ARG: kind = LUDVM_FIELD_PSI ("the stream function has no fp32 route") or unknown, vcore not finite or below 1e-6 (this
+ * is the viscous core's route: with a smaller core 1 / s^3 leaves fp32), a null array with a non-zero count. */
+int ludvm_scalar_f32x2(ludvm_ctx* ctx, int kind, const double* xs, const double* zs, const double* gs, size_t ns,
+                       const double* xt, const double* zt, size_t nt, double vcore, double* out);
+/* The same sum on rows [row_first, row_first + row_count) of the grid, the mesh and the rules of ludvm_flowfield_scalar_rows_f64
+ * (grid points generated in float64, then split): a block of rows is planned from the whole grid and carries the whole-grid
+ * call's bits, and a grid point gets the bits ludvm_scalar_f32x2 gives the same point in an array of as many targets.
+ * LUDVM_E_ARG as above, and for rows outside the grid. */
+int ludvm_flowfield_scalar_rows_f32x2(ludvm_ctx* ctx, int kind, double xmin, double zmin, double dr, size_t nx, size_t nz,
+                                      size_t row_first, size_t row_count, const double* xs, const double* zs,
+                                      const double* gs, size_t ns, double vcore, double* out);
+/* ludvm_gradient_f64 by the same scheme: the raw sums A, B, C in hi+lo fp32 pairs, ordered (G y) (y r2) (y dx dz) so that no
+ * factor leaves fp32's range over |coordinates| <= 1e4 with vcore >= 1e-4; tiles, accumulators, splits and reproducibility as
+ * ludvm_scalar_f32x2, and ux, uz, wx formed from the float64 totals as ludvm_gradient_f64 forms them.
+ * LUDVM_E_ARG: vcore not finite or below 1e-6, a null array with a non-zero count. */
+int ludvm_gradient_f32x2(ludvm_ctx* ctx, const double* xs, const double* zs, const double* gs, size_t ns, const double* xt,
+                         const double* zt, size_t nt, double vcore, double* ux, double* uz, double* wx);
+/* The same sums on rows of the grid, the rules of ludvm_flowfield_gradient_rows_f64 and the scheme of ludvm_gradient_f32x2: a
+ * block of rows carries the whole-grid call's bits.  LUDVM_E_ARG as ludvm_gradient_f32x2, and for rows outside the grid. */
+int ludvm_flowfield_gradient_rows_f32x2(ludvm_ctx* ctx, double xmin, double zmin, double dr, size_t nx, size_t nz,
+                                        size_t row_first, size_t row_count, const double* xs, const double* zs,
+                                        const double* gs, size_t ns, double vcore, double* ux, double* uz, double* wx);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 
 /* Probe of the symmetric kernel's fixed-point accumulation (the order-independent sums behind the roll-up of

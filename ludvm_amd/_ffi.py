@@ -149,6 +149,12 @@ SIGNATURES = {
     "ludvm_gradient_f64": [c_void_p, _pd, _pd, _pd, c_size_t, _pd, _pd, c_size_t, c_double, _pd, _pd, _pd],
     "ludvm_flowfield_gradient_rows_f64": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, c_size_t, c_size_t,
                                           _pd, _pd, _pd, c_size_t, c_double, _pd, _pd, _pd],
+    "ludvm_scalar_f32x2": [c_void_p, c_int, _pd, _pd, _pd, c_size_t, _pd, _pd, c_size_t, c_double, _pd],
+    "ludvm_flowfield_scalar_rows_f32x2": [c_void_p, c_int, c_double, c_double, c_double, c_size_t, c_size_t, c_size_t, c_size_t,
+                                          _pd, _pd, _pd, c_size_t, c_double, _pd],
+    "ludvm_gradient_f32x2": [c_void_p, _pd, _pd, _pd, c_size_t, _pd, _pd, c_size_t, c_double, _pd, _pd, _pd],
+    "ludvm_flowfield_gradient_rows_f32x2": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, c_size_t, c_size_t,
+                                            _pd, _pd, _pd, c_size_t, c_double, _pd, _pd, _pd],
     "ludvm_fixed_point_probe": [c_void_p, _pf, c_size_t, c_int, POINTER(c_longlong)],
     "ludvm_kernel_timing": [c_void_p, c_int],
     "ludvm_kernel_time_ms": [c_void_p, c_int, POINTER(c_double), POINTER(c_longlong)],
@@ -161,7 +167,8 @@ ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm
                   "ludvm_march_read_survey_bins", "ludvm_scalar_f64", "ludvm_flowfield_scalar_rows_f64",
                   "ludvm_gradient_f64", "ludvm_flowfield_gradient_rows_f64", "ludvm_march_set_tracer_gradient",
                   "ludvm_march_read_tracer_gradient", "ludvm_march_tracer_gradient_state", "ludvm_march_set_survey_gradient",
-                  "ludvm_march_read_survey_gradient")
+                  "ludvm_march_read_survey_gradient", "ludvm_scalar_f32x2", "ludvm_flowfield_scalar_rows_f32x2",
+                  "ludvm_gradient_f32x2", "ludvm_flowfield_gradient_rows_f32x2")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -11,7 +11,7 @@
 //   induce.hip     stateless pair sums, the multi-GPU shard step's entry points            (ludvm_induce_*, ludvm_advect_dev_f32, ludvm_sym_*)
 //   wake.hip       the resident wake and its roll-up                                       (ludvm_wake_*)
 //   march.hip      the device-resident time march; the ensemble of small simulations       (ludvm_march_*, ludvm_ensemble_*)
-//   flowfield.hip  flow-field grids, the vorticity stencil, stream function / vorticity    (ludvm_flowfield_*, ludvm_vorticity_*, ludvm_scalar_f64)
+//   flowfield.hip  flow-field grids, the vorticity stencil, stream function / vorticity    (ludvm_flowfield_*, ludvm_vorticity_*, ludvm_scalar_*, ludvm_gradient_*)
 #pragma once
 #pragma GCC visibility push(default)          // the C ABI is what the library exports; everything else is hidden (-fvisibility=hidden)
 #include "../../include/ludvm_hip.h"

@@ -1,5 +1,6 @@
 // Kernels of the flow field (flowfield.hip): source staging conversions, the vorticity stencil of LUDVM.flowfield
-// (LUDVM.py:1224-1292), the scalar pair sums (stream function, analytic vorticity) and the velocity gradient.  Non-template kernels: this header
+// (LUDVM.py:1224-1292), the scalar pair sums (stream function, analytic vorticity) and the velocity gradient in float64, and the
+// latter two in hi+lo fp32 (field_hilo_f32).  Non-template kernels: this header
 // belongs to ONE translation unit (flowfield.hip).
 #pragma once
 #include "pair_kernels.hpp"
@@ -288,6 +289,155 @@ finish_grad(const double* part, long long nt, long long nt_pad, int nsplit, doub
   const double* col = part + i;
   grad_outputs(sum_column(col, 3 * nt_pad, nsplit), sum_column(col + nt_pad, 3 * nt_pad, nsplit),
                sum_column(col + 2 * nt_pad, 3 * nt_pad, nsplit), vc4, nt, out + i);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The analytic vorticity (GRAD = false: C alone) and the velocity gradient (GRAD = true: A, B, C) in hi+lo fp32: the scheme of
+// hilo_field_f32 (march_kernels.hpp) on the float64 device arrays of the float64 route -- no origins, no fall-back.
+//   points   a lane owns kFieldHiloPerLane targets (target b * 1024 + k * 256 + lane in register set k; arrays, or grid_point in
+//            float64), each coordinate split once by split_hilo before the source loop; a lane without a point sits at
+//            -kPadPosF, away from the sources' padding, and stores nothing
+//   tiles    256 consecutive sources from the split's first one (`chunk` is a multiple of 256); each lane splits one source and
+//            stages xh, xl, zh, zl, (float)G: five float planes.  Slots past the end are pair_f32's padding (hi = kPadPosF,
+//            lo = 0, G = 0)
+//   pairs    dx = (xh_p - xh_s) + (xl_p - xl_s), dz likewise, then packed fp32, two sources per v_pk_*_f32, one v_rsq_f32 per
+//            pair, the sources by broadcast ds_read_b128.  With y = rsq(r2^2 + vc^4):
+//                C += (G y) (y y),   e = (G y) (y r2),   A += e (y (dx dz)),   B += e (y (dx^2 - dz^2))
+//            Every factor of e's products is at most about 1 whatever the distance (y r2 <= 1, y |dx dz| <= 1 / 2,
+//            y |dx^2 - dz^2| <= 1) and G y is a velocity-sized number: over |coordinates| <= 1e4 with v_core >= 1e-4 no
+//            intermediate leaves fp32's normal range (y in [1e-9, 1e8], y^2 in [1e-18, 1e16], r2 and |dx dz| <= 8e8); G y^3
+//            formed first would flush for a far source of small circulation while its A and B terms still count.  Only the
+//            C term may flush, and it enters the outputs times vc^4.
+//            A pad pair adds exact zeros: r2 <= 7.2e37 and |dx dz| <= 3.6e37 stay finite (also between a lane and a slot that are
+//            both padding), r2^2 overflows to +inf, y = 0, G y = 0, and every product of y meets a finite partner.
+//            20 (GRAD) or 12 v_pk_*_f32 + 2 v_rsq_f32 per two pairs and point.
+//   sums     two levels: a tile's terms in fp32 packed registers (even sources in the low halves, odd ones in the high halves:
+//            128 terms per accumulator), then low half and high half, in that order, added to the lane's float64 sums
+// Every target sees the same operations on the same operands in the same order, whichever lane, register set, row block or
+// target form it arrives in.  Source splits over blockIdx.y write pair_scalar_f64's / pair_grad_f64's slab ([split][nt_pad]
+// of scaled values, [split][3][nt_pad] of raw sums) for finish_scalar / finish_grad.
+// ---------------------------------------------------------------------------------------------
+template <bool GRAD, int PPL>
+__global__ void __launch_bounds__(kBlock)
+field_hilo_f32(PairArgs a) {
+  static_assert(kFieldHiloTile == kBlock, "one source slot per lane");
+  __shared__ __attribute__((aligned(16))) float lxh[kFieldHiloTile];
+  __shared__ __attribute__((aligned(16))) float lxl[kFieldHiloTile];
+  __shared__ __attribute__((aligned(16))) float lzh[kFieldHiloTile];
+  __shared__ __attribute__((aligned(16))) float lzl[kFieldHiloTile];
+  __shared__ __attribute__((aligned(16))) float lg[kFieldHiloTile];
+
+  const double* __restrict__ xs = static_cast<const double*>(a.xs);
+  const double* __restrict__ zs = static_cast<const double*>(a.zs);
+  const double* __restrict__ gs = static_cast<const double*>(a.gs);
+
+  const int tid = threadIdx.x;
+  const long long t0 = (long long)blockIdx.x * (kBlock * PPL) + tid;
+  const long long s_begin = (long long)blockIdx.y * a.chunk;
+  long long s_end = s_begin + a.chunk;
+  if (s_end > a.ns) s_end = a.ns;
+
+  const float vc4s = (float)a.vc4;
+  const f32x2 vc4p = {vc4s, vc4s};
+  f32x2 xph[PPL], xpl[PPL], zph[PPL], zpl[PPL];
+  double sa[PPL], sb[PPL], sc[PPL];
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long ti = t0 + (long long)k * kBlock;
+    double xd = -(double)kPadPosF, zd = -(double)kPadPosF;
+    if (ti < a.nt) {
+      if (a.grid_nz > 0) {
+        grid_point(a, ti, xd, zd);
+      } else {
+        xd = static_cast<const double*>(a.xt)[ti];
+        zd = static_cast<const double*>(a.zt)[ti];
+      }
+    }
+    float h, l;
+    split_hilo(xd, h, l);
+    xph[k] = (f32x2){h, h}; xpl[k] = (f32x2){l, l};
+    split_hilo(zd, h, l);
+    zph[k] = (f32x2){h, h}; zpl[k] = (f32x2){l, l};
+    sa[k] = 0.0; sb[k] = 0.0; sc[k] = 0.0;
+  }
+
+  for (long long base = s_begin; base < s_end; base += kFieldHiloTile) {
+    __syncthreads();                                // previous tile fully consumed
+    {
+      const long long si = base + tid;
+      float xh = kPadPosF, xl = 0.0f, zh = kPadPosF, zl = 0.0f, g = 0.0f;
+      if (si < s_end) {
+        split_hilo(xs[si], xh, xl);
+        split_hilo(zs[si], zh, zl);
+        g = (float)gs[si];
+      }
+      lxh[tid] = xh; lxl[tid] = xl; lzh[tid] = zh; lzl[tid] = zl; lg[tid] = g;
+    }
+    __syncthreads();
+    f32x2 ta[PPL], tb[PPL], tc[PPL];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) { ta[k] = (f32x2){0.0f, 0.0f}; tb[k] = (f32x2){0.0f, 0.0f}; tc[k] = (f32x2){0.0f, 0.0f}; }
+#pragma unroll 2
+    for (int j = 0; j < kFieldHiloTile; j += 4) {
+      const f32x4 X = *reinterpret_cast<const f32x4*>(&lxh[j]);
+      const f32x4 XL = *reinterpret_cast<const f32x4*>(&lxl[j]);
+      const f32x4 Z = *reinterpret_cast<const f32x4*>(&lzh[j]);
+      const f32x4 ZL = *reinterpret_cast<const f32x4*>(&lzl[j]);
+      const f32x4 G = *reinterpret_cast<const f32x4*>(&lg[j]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x2 xs2 = h ? (f32x2){X.z, X.w} : (f32x2){X.x, X.y};
+        const f32x2 xl2 = h ? (f32x2){XL.z, XL.w} : (f32x2){XL.x, XL.y};
+        const f32x2 zs2 = h ? (f32x2){Z.z, Z.w} : (f32x2){Z.x, Z.y};
+        const f32x2 zl2 = h ? (f32x2){ZL.z, ZL.w} : (f32x2){ZL.x, ZL.y};
+        const f32x2 gs2 = h ? (f32x2){G.z, G.w} : (f32x2){G.x, G.y};
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) {
+          const f32x2 dx = (xph[k] - xs2) + (xpl[k] - xl2);
+          const f32x2 dz = (zph[k] - zs2) + (zpl[k] - zl2);
+          const f32x2 dxx = dx * dx;
+          const f32x2 r2 = __builtin_elementwise_fma(dz, dz, dxx);
+          const f32x2 q = __builtin_elementwise_fma(r2, r2, vc4p);
+          const f32x2 y = {__builtin_amdgcn_rsqf(q.x), __builtin_amdgcn_rsqf(q.y)};
+          const f32x2 gy = gs2 * y;
+          tc[k] = __builtin_elementwise_fma(gy, y * y, tc[k]);
+          if (GRAD) {
+            const f32x2 e = gy * (y * r2);
+            ta[k] = __builtin_elementwise_fma(e, y * (dx * dz), ta[k]);
+            tb[k] = __builtin_elementwise_fma(e, y * __builtin_elementwise_fma(-dz, dz, dxx), tb[k]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      sc[k] += (double)tc[k].x; sc[k] += (double)tc[k].y;
+      if (GRAD) {
+        sa[k] += (double)ta[k].x; sa[k] += (double)ta[k].y;
+        sb[k] += (double)tb[k].x; sb[k] += (double)tb[k].y;
+      }
+    }
+  }
+
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long ti = t0 + (long long)k * kBlock;
+    if (ti >= a.nt) continue;
+    if (GRAD) {
+      if (gridDim.y == 1) {
+        grad_outputs(sa[k], sb[k], sc[k], a.vc4, a.nt, static_cast<double*>(a.u) + ti);
+      } else {
+        double* row = static_cast<double*>(a.part) + (long long)blockIdx.y * 3 * a.nt_pad + ti;
+        row[0] = sa[k];
+        row[a.nt_pad] = sb[k];
+        row[2 * a.nt_pad] = sc[k];
+      }
+    } else {
+      const double v = sc[k] * (-a.vc4 * kInvPiD);
+      if (gridDim.y == 1) static_cast<double*>(a.u)[ti] = v;
+      else static_cast<double*>(a.part)[(long long)blockIdx.y * a.nt_pad + ti] = v;
+    }
+  }
 }
 
 }  // namespace ludvm

@@ -231,8 +231,18 @@ static int field_columns(int kind) { return kind == kFieldGrad ? 3 : 1; }
 // device sources, targets (arrays or a grid) and vc4 filled in by the caller.  The sources are split as the float64 velocity
 // sum splits them (make_plan: a few targets still fill the device), from plan_nt targets when the launch is a block of rows
 // of a larger grid; the slab [split][columns][nt_pad] lives in c->part.
-static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, double* out) {
-  const Plan p = make_plan(c, a.nt, a.ns, LUDVM_PREC_F64, true, plan_nt);
+// hilo: field_hilo_f32 in place of the float64 pair kernel (OMEGA and the gradient), planned by field_hilo_plan from plan_nt and
+// ns alone; the slab and the finishers are the float64 route's.
+static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, double* out, bool hilo = false) {
+  Plan p{};
+  if (hilo) {
+    const FieldHiloPlan h = field_hilo_plan(plan_nt > 0 ? plan_nt : a.nt, a.ns);
+    p.chunk = h.chunk;
+    p.nsplit = h.nsplit;
+    p.nt_pad = field_hilo_pad(a.nt);
+  } else {
+    p = make_plan(c, a.nt, a.ns, LUDVM_PREC_F64, true, plan_nt);
+  }
   a.chunk = p.chunk;
   a.nt_pad = p.nt_pad;
   a.nsplit = p.nsplit;
@@ -242,7 +252,11 @@ static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, 
     a.part = c->part.p;
   }
   void (*kernel)(PairArgs) = nullptr;
-  if (kind == kFieldGrad) {
+  unsigned blocks = blocks_for(a.nt);
+  if (hilo) {
+    kernel = kind == kFieldGrad ? field_hilo_f32<true, kFieldHiloPerLane> : field_hilo_f32<false, kFieldHiloPerLane>;
+    blocks = (unsigned)field_hilo_blocks(a.nt);
+  } else if (kind == kFieldGrad) {
     kernel = p.tile == kTileF64Few ? pair_grad_f64<kTileF64Few> : pair_grad_f64<kTileF64>;
   } else if (kind == LUDVM_FIELD_PSI) {
     kernel = p.tile == kTileF64Few ? pair_scalar_f64<kScalarPsi, kTileF64Few> : pair_scalar_f64<kScalarPsi, kTileF64>;
@@ -252,7 +266,7 @@ static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, 
   TimedLaunch t{};
   bool active = false;
   CHK(timed_begin(c, t, active));
-  hipLaunchKernelGGL(kernel, dim3(blocks_for(a.nt), (unsigned)p.nsplit), dim3(kBlock), 0, c->stream, a);
+  hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)p.nsplit), dim3(kBlock), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   CHK(timed_end(c, t, active));
   if (p.nsplit > 1) {
@@ -271,7 +285,8 @@ static int scalar_device(ludvm_ctx* c, int kind, PairArgs a, long long plan_nt, 
 // Host sources up, the sum over targets `a` describes (array targets are uploaded here), nt results per column down: out[k]
 // takes column k (one column, or the gradient's three).
 static int scalar_host(ludvm_ctx* c, int kind, PairArgs a, const double* xs, const double* zs, const double* gs, size_t ns,
-                       const double* xt, const double* zt, size_t nt, size_t plan_nt, double vcore, double* const* out) {
+                       const double* xt, const double* zt, size_t nt, size_t plan_nt, double vcore, double* const* out,
+                       bool hilo = false) {
   const size_t ncol = (size_t)field_columns(kind);
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->arena, 3 * Arena::need(ns, 8) + 2 * Arena::need(nt, 8) + Arena::need(ncol * nt, 8)));
@@ -297,7 +312,7 @@ static int scalar_host(ludvm_ctx* c, int kind, PairArgs a, const double* xs, con
     a.nt = (long long)nt;
     const double v2 = vcore * vcore;
     a.vc4 = v2 * v2;
-    CHK(scalar_device(c, kind, a, (long long)plan_nt, dout));
+    CHK(scalar_device(c, kind, a, (long long)plan_nt, dout, hilo));
   }
   for (size_t k = 0; k < ncol; ++k) HIPCHK(c, hipMemcpyAsync(out[k], dout + k * nt, nt * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -354,6 +369,68 @@ int ludvm_flowfield_gradient_rows_f64(ludvm_ctx* c, double xmin, double zmin, do
   // (planned for the whole grid: a block of rows is then bit for bit what the whole-grid call computes for them)
   double* const out[3] = {ux, uz, wx};
   return scalar_host(c, kFieldGrad, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, out);
+}
+
+/* ---- the same sums in hi+lo fp32 (field_hilo_f32) ---- */
+
+// what the four f32x2 entries refuse before their twins' checks: the stream function, and a core the fp32 pair cannot hold
+static int hilo_refusal(ludvm_ctx* c, int kind, double vcore) {
+  if (kind == LUDVM_FIELD_PSI) return fail(c, LUDVM_E_ARG, "the stream function has no fp32 route");
+  if (kind != LUDVM_FIELD_OMEGA && kind != kFieldGrad) return fail(c, LUDVM_E_ARG, "unknown field kind");
+  if (!(vcore >= 1e-6) || !std::isfinite(vcore)) return fail(c, LUDVM_E_ARG, "the fp32 route needs a finite vcore >= 1e-6");
+  return LUDVM_OK;
+}
+
+int ludvm_scalar_f32x2(ludvm_ctx* c, int kind, const double* xs, const double* zs, const double* gs, size_t ns, const double* xt,
+                       const double* zt, size_t nt, double vcore, double* out) {
+  if (!c) return LUDVM_E_ARG;
+  CHK(hilo_refusal(c, kind, vcore));
+  if (nt == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !xt || !zt || !out) return fail(c, LUDVM_E_ARG, "null array");
+  return scalar_host(c, kind, PairArgs{}, xs, zs, gs, ns, xt, zt, nt, nt, vcore, &out, true);
+}
+
+int ludvm_flowfield_scalar_rows_f32x2(ludvm_ctx* c, int kind, double xmin, double zmin, double dr, size_t nx, size_t nz,
+                                      size_t row_first, size_t row_count, const double* xs, const double* zs, const double* gs,
+                                      size_t ns, double vcore, double* out) {
+  if (!c) return LUDVM_E_ARG;
+  CHK(hilo_refusal(c, kind, vcore));
+  if (row_first > nx || row_count > nx - row_first) return fail(c, LUDVM_E_ARG, "rows outside the grid");
+  if (row_count == 0 || nz == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !out) return fail(c, LUDVM_E_ARG, "null array");
+  PairArgs a{};
+  a.grid_nz = (long long)nz;
+  a.grid_row0 = (long long)row_first;
+  a.xmin = xmin; a.zmin = zmin; a.dr = dr;
+  // (planned for the whole grid: a block of rows is then bit for bit what the whole-grid call computes for them)
+  return scalar_host(c, kind, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, &out, true);
+}
+
+int ludvm_gradient_f32x2(ludvm_ctx* c, const double* xs, const double* zs, const double* gs, size_t ns, const double* xt,
+                         const double* zt, size_t nt, double vcore, double* ux, double* uz, double* wx) {
+  if (!c) return LUDVM_E_ARG;
+  CHK(hilo_refusal(c, kFieldGrad, vcore));
+  if (nt == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !xt || !zt || !ux || !uz || !wx) return fail(c, LUDVM_E_ARG, "null array");
+  double* const out[3] = {ux, uz, wx};
+  return scalar_host(c, kFieldGrad, PairArgs{}, xs, zs, gs, ns, xt, zt, nt, nt, vcore, out, true);
+}
+
+int ludvm_flowfield_gradient_rows_f32x2(ludvm_ctx* c, double xmin, double zmin, double dr, size_t nx, size_t nz, size_t row_first,
+                                        size_t row_count, const double* xs, const double* zs, const double* gs, size_t ns,
+                                        double vcore, double* ux, double* uz, double* wx) {
+  if (!c) return LUDVM_E_ARG;
+  CHK(hilo_refusal(c, kFieldGrad, vcore));
+  if (row_first > nx || row_count > nx - row_first) return fail(c, LUDVM_E_ARG, "rows outside the grid");
+  if (row_count == 0 || nz == 0) return LUDVM_OK;
+  if ((ns && (!xs || !zs || !gs)) || !ux || !uz || !wx) return fail(c, LUDVM_E_ARG, "null array");
+  PairArgs a{};
+  a.grid_nz = (long long)nz;
+  a.grid_row0 = (long long)row_first;
+  a.xmin = xmin; a.zmin = zmin; a.dr = dr;
+  // (planned for the whole grid: a block of rows is then bit for bit what the whole-grid call computes for them)
+  double* const out[3] = {ux, uz, wx};
+  return scalar_host(c, kFieldGrad, a, xs, zs, gs, ns, nullptr, nullptr, row_count * nz, nx * nz, vcore, out, true);
 }
 
 }  // extern "C"

@@ -244,6 +244,32 @@ inline size_t observer_slab_bytes(const ObserverRule& r, long long count) {
   return (size_t)observer_want(r, count) * 2 * (size_t)(observer_tiles(r, count) * r.point_tile) * 8;
 }
 
+// ---- launch rule of the hi+lo fp32 field sums (field_kernels.hpp: field_hilo_f32, analytic vorticity and velocity gradient) -----
+// Targets in workgroups of kFieldHiloTargets (256 lanes x kFieldHiloPerLane points), sources in tiles of kFieldHiloTile; the
+// sources in `nsplit` splits of `chunk` sources, a multiple of the tile, so that target workgroups x splits comes to about
+// kFieldHiloGroups (eight workgroups per CU), with at most kFieldHiloMaxSplit splits (the finishers add them one after the
+// other).  A function of plan_nt -- the whole grid's points when the launch is a block of its rows -- and ns alone: everything
+// the rounding of a result depends on.
+constexpr int kFieldHiloPerLane = 4;
+constexpr int kFieldHiloTile = 256;
+constexpr long long kFieldHiloTargets = (long long)kPlanBlock * kFieldHiloPerLane;
+constexpr long long kFieldHiloGroups = 2048;
+constexpr long long kFieldHiloMaxSplit = 64;
+struct FieldHiloPlan { long long chunk; int nsplit; };
+
+inline FieldHiloPlan field_hilo_plan(long long plan_nt, long long ns) {
+  const long long tiles = plan_max(1, (plan_nt + kFieldHiloTargets - 1) / kFieldHiloTargets);
+  const long long want = plan_min(kFieldHiloMaxSplit, plan_max(1, kFieldHiloGroups / tiles));
+  ns = plan_max(ns, 1);
+  FieldHiloPlan p;
+  p.chunk = ((ns + want - 1) / want + kFieldHiloTile - 1) / kFieldHiloTile * kFieldHiloTile;
+  p.nsplit = (int)((ns + p.chunk - 1) / p.chunk);          // <= want
+  return p;
+}
+// workgroups over the targets of one launch, and the columns of a slab row (the lanes past nt store nothing)
+inline long long field_hilo_blocks(long long nt) { return plan_max(1, (nt + kFieldHiloTargets - 1) / kFieldHiloTargets); }
+inline long long field_hilo_pad(long long nt) { return (nt + 63) / 64 * 64; }
+
 // the instantiation's name as a profiler prints it
 inline void direct_kernel_name(const DirectVariant& v, char* out, size_t len) {
   if (v.kernel == kDirectF64Few) std::snprintf(out, len, "pair_f64_few<%d>", v.tile);

@@ -821,25 +821,41 @@ class Engine:
             raise ValueError("kind: 'psi' or 'omega' (or the library's code)")
         return code
 
-    def scalar_field(self, kind, circulation, xw, zw, xp, zp, v_core):
+    def _field_entry(self, what, f64_name, precision, code=None):
+        """the library function of a field sum in `precision`: 'f64', or 'f32x2' (hi+lo fp32 pairs: 'omega' and the gradient);
+        code: the scalar sums' kind"""
+        if precision == "f64":
+            return getattr(self._lib, f64_name)
+        if precision != "f32x2":
+            raise ValueError(f"{what}: precision must be 'f64' or 'f32x2', not {precision!r}")
+        if code == _ffi.FIELD_KINDS["psi"]:
+            raise ValueError(f"{what}: the stream function has no fp32 route (precision='f32x2' serves 'omega')")
+        name = f64_name[:-len("f64")] + "f32x2"
+        self._need(name)
+        return getattr(self._lib, name)
+
+    def scalar_field(self, kind, circulation, xw, zw, xp, zp, v_core, precision="f64"):
         """float64 [Np]: the stream function (kind 'psi': sum G / (4 pi) ln((r^2 + s) / 2), s = sqrt(r^4 + v_core^4), whose z and
         -x derivatives are `induce`'s u and w) or the core model's vorticity (kind 'omega': dw/dx - du/dz of that
         velocity in closed form, -sum G v_core^4 / (pi s^3)) of the
-        vortices at the points, in float64 throughout (ludvm_scalar_f64)."""
+        vortices at the points, in float64 throughout (ludvm_scalar_f64).  precision='f32x2': 'omega' with the pair arithmetic in
+        hi+lo fp32 (ludvm_scalar_f32x2: float64 in and out, <= 2e-6 of max|omega|, v_core >= 1e-6); 'psi' has no such route."""
         code = self._field_kind(kind, "ludvm_scalar_f64")
+        fn = self._field_entry("scalar_field", "ludvm_scalar_f64", precision, code)
         g, xs, zs, xt, zt = _f64(circulation), _f64(xw), _f64(zw), _f64(xp), _f64(zp)
         if not (len(g) == len(xs) == len(zs)) or len(xt) != len(zt):
             raise ValueError("scalar_field: source arrays (and target arrays) must have equal lengths")
         out = np.empty(len(xt))
-        self._check(self._lib.ludvm_scalar_f64(self._ctx, code, _pd(xs), _pd(zs), _pd(g), len(xs), _pd(xt), _pd(zt), len(xt),
-                                               float(v_core), _pd(out)))
+        self._check(fn(self._ctx, code, _pd(xs), _pd(zs), _pd(g), len(xs), _pd(xt), _pd(zt), len(xt), float(v_core), _pd(out)))
         return out
 
-    def flowfield_scalar(self, kind, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core, row_first=0, row_count=None):
+    def flowfield_scalar(self, kind, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core, row_first=0, row_count=None,
+                         precision="f64"):
         """float64 [row_count, nz]: `scalar_field` on rows [row_first, row_first + row_count) of the flow-field grid
         (xmin + i*dr, zmin + j*dr), generated on the device; every row by default.  A block of rows carries the whole-grid
-        call's bits (ludvm_flowfield_scalar_rows_f64)."""
+        call's bits (ludvm_flowfield_scalar_rows_f64; precision='f32x2': ludvm_flowfield_scalar_rows_f32x2, as `scalar_field`)."""
         code = self._field_kind(kind, "ludvm_flowfield_scalar_rows_f64")
+        fn = self._field_entry("flowfield_scalar", "ludvm_flowfield_scalar_rows_f64", precision, code)
         g, xs, zs = _f64(circulation), _f64(xw), _f64(zw)
         if not (len(g) == len(xs) == len(zs)):
             raise ValueError("flowfield_scalar: source arrays must have equal lengths")
@@ -848,9 +864,8 @@ class Engine:
         if nx < 0 or nz < 0 or row_first < 0 or row_count < 0:
             raise ValueError("flowfield_scalar: nx, nz, row_first and row_count must not be negative")
         out = np.empty(max(row_count, 0) * nz)
-        self._check(self._lib.ludvm_flowfield_scalar_rows_f64(self._ctx, code, float(xmin), float(zmin), float(dr), nx, nz,
-                                                              row_first, row_count, _pd(xs), _pd(zs), _pd(g), len(xs),
-                                                              float(v_core), _pd(out)))
+        self._check(fn(self._ctx, code, float(xmin), float(zmin), float(dr), nx, nz, row_first, row_count, _pd(xs), _pd(zs), _pd(g),
+                       len(xs), float(v_core), _pd(out)))
         return out.reshape(row_count, nz)
 
     # -- velocity gradient ------------------------------------------------------------------------
@@ -858,23 +873,28 @@ class Engine:
         if not hasattr(self._lib, fn):
             raise LudvmHipError(_ffi.E_STATE, f"this build of the library has no {fn}")
 
-    def gradient_field(self, circulation, xw, zw, xp, zp, v_core):
+    def gradient_field(self, circulation, xw, zw, xp, zp, v_core, precision="f64"):
         """(ux, uz, wx), float64 [Np] each: du/dx, du/dz and dw/dx of `induce`'s velocity at the points, in closed form and in
-        float64 throughout (ludvm_gradient_f64); dw/dz = -ux, wx - uz is `scalar_field('omega', ...)`."""
+        float64 throughout (ludvm_gradient_f64); dw/dz = -ux, wx - uz is `scalar_field('omega', ...)`.  precision='f32x2': the
+        pair arithmetic in hi+lo fp32 (ludvm_gradient_f32x2: float64 in and out, <= 2e-6 of max|grad u|, v_core >= 1e-6)."""
         self._need("ludvm_gradient_f64")
+        fn = self._field_entry("gradient_field", "ludvm_gradient_f64", precision)
         g, xs, zs, xt, zt = _f64(circulation), _f64(xw), _f64(zw), _f64(xp), _f64(zp)
         if not (len(g) == len(xs) == len(zs)) or len(xt) != len(zt):
             raise ValueError("gradient_field: source arrays (and target arrays) must have equal lengths")
         ux, uz, wx = np.empty(len(xt)), np.empty(len(xt)), np.empty(len(xt))
-        self._check(self._lib.ludvm_gradient_f64(self._ctx, _pd(xs), _pd(zs), _pd(g), len(xs), _pd(xt), _pd(zt), len(xt),
-                                                 float(v_core), _pd(ux), _pd(uz), _pd(wx)))
+        self._check(fn(self._ctx, _pd(xs), _pd(zs), _pd(g), len(xs), _pd(xt), _pd(zt), len(xt), float(v_core), _pd(ux), _pd(uz),
+                       _pd(wx)))
         return ux, uz, wx
 
-    def flowfield_gradient(self, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core, row_first=0, row_count=None):
+    def flowfield_gradient(self, xmin, zmin, dr, nx, nz, circulation, xw, zw, v_core, row_first=0, row_count=None,
+                           precision="f64"):
         """(ux, uz, wx), float64 [row_count, nz] each: `gradient_field` on rows [row_first, row_first + row_count) of the
         flow-field grid (xmin + i*dr, zmin + j*dr), generated on the device; every row by default.  A block of rows carries
-        the whole-grid call's bits (ludvm_flowfield_gradient_rows_f64)."""
+        the whole-grid call's bits (ludvm_flowfield_gradient_rows_f64; precision='f32x2': ludvm_flowfield_gradient_rows_f32x2, as
+        `gradient_field`)."""
         self._need("ludvm_flowfield_gradient_rows_f64")
+        fn = self._field_entry("flowfield_gradient", "ludvm_flowfield_gradient_rows_f64", precision)
         g, xs, zs = _f64(circulation), _f64(xw), _f64(zw)
         if not (len(g) == len(xs) == len(zs)):
             raise ValueError("flowfield_gradient: source arrays must have equal lengths")
@@ -883,9 +903,8 @@ class Engine:
         if nx < 0 or nz < 0 or row_first < 0 or row_count < 0:
             raise ValueError("flowfield_gradient: nx, nz, row_first and row_count must not be negative")
         ux, uz, wx = (np.empty(max(row_count, 0) * nz) for _ in range(3))
-        self._check(self._lib.ludvm_flowfield_gradient_rows_f64(self._ctx, float(xmin), float(zmin), float(dr), nx, nz,
-                                                                row_first, row_count, _pd(xs), _pd(zs), _pd(g), len(xs),
-                                                                float(v_core), _pd(ux), _pd(uz), _pd(wx)))
+        self._check(fn(self._ctx, float(xmin), float(zmin), float(dr), nx, nz, row_first, row_count, _pd(xs), _pd(zs), _pd(g),
+                       len(xs), float(v_core), _pd(ux), _pd(uz), _pd(wx)))
         return ux.reshape(row_count, nz), uz.reshape(row_count, nz), wx.reshape(row_count, nz)
 
     def fixed_point_probe(self, values, scale_log2):

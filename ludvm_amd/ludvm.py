@@ -16,6 +16,7 @@ MI355X the constructor raises.
 
 Citations are file:line into the reference's LUDVM.py.
 """
+import inspect
 import timeit
 
 import numpy as np
@@ -803,7 +804,8 @@ class LUDVM:
         """Vorticity omega = dw/dx - du/dz at points (xp, zp) of the velocity field `induced_velocity` gives for vortices
         (circulation, xw, zw), in closed form: -sum G v_core^4 / (pi s^3), s = sqrt(r^4 + v_core^4) -- the sign convention of
         `ome_ff`, no grid and no differences.  One new float64 array, float64 on the GPU whatever the run's `precision`; 0
-        with `viscous=False` (NaN at a point on top of a vortex)."""
+        with `viscous=False` (NaN at a point on top of a vortex).  (The hi+lo fp32 route of the sum:
+        `engine.scalar_field('omega', ..., precision='f32x2')`, or `flowfield(omega=True, field_precision='f32x2')` on a mesh.)"""
         return self._scalar_field('omega', 'the analytic vorticity', circulation, xw, zw, xp, zp, viscous)
 
     def velocity_gradient(self, circulation, xw, zw, xp, zp, viscous=True):
@@ -811,7 +813,8 @@ class LUDVM:
         gives for vortices (circulation, xw, zw), in closed form: no grid and no differences.  dw/dz = -ux (the field is
         divergence free), wx - uz is `vorticity`, and Q = -ux^2 - uz wx is positive in a vortex core and negative in a
         shear layer.  Three new float64 arrays, float64 on the GPU whatever the run's `precision`; with `viscous=False` the
-        point vortex's gradient (NaN at a point on top of a vortex)."""
+        point vortex's gradient (NaN at a point on top of a vortex).  (The hi+lo fp32 route of the sums:
+        `engine.gradient_field(..., precision='f32x2')`, or `flowfield(grad=True, field_precision='f32x2')` on a mesh.)"""
         if self._shard is not None and self._shard.world > 1:
             raise ValueError("the velocity gradient runs on one GPU: not with `distributed` or more than one device in `devices`")
         if not hasattr(self.engine, 'gradient_field'):
@@ -1905,7 +1908,8 @@ class LUDVM:
         LUDVM(..., snapshot_steps=LUDVM.flowfield_rows_needed(tsteps))."""
         return sorted({r for s in tsteps for r in ((int(s) - 1, int(s)) if int(s) > 0 else (0,))})
 
-    def flowfield(self, xmin=-10, xmax=0, zmin=-4, zmax=4, dr=0.02, tsteps=[0, 1, 2], psi=False, omega=False, grad=False):
+    def flowfield(self, xmin=-10, xmax=0, zmin=-4, zmax=4, dr=0.02, tsteps=[0, 1, 2], psi=False, omega=False, grad=False,
+                  field_precision='f64'):
         """Velocity and vorticity on the uniform mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr)
         at the requested time steps (LUDVM.py:1186-1298).  The mesh points are generated on the
         device (x-major, as meshgrid(indexing='ij') ravels, :1194-1195); wake and bound vortices go in
@@ -1921,7 +1925,14 @@ class LUDVM:
         any dr.  `grad=True` adds the velocity gradient in closed form from the same sources on the same mesh
         (`velocity_gradient`): `ux_ff`, `uz_ff`, `wx_ff` and `q_ff` = -ux^2 - uz wx (the Q / Okubo-Weiss criterion: positive in a
         vortex core, negative in a shear layer), [nsteps, nx, nz] each.  One GPU only; u_ff, w_ff and ome_ff (and psi_ff,
-        omega_ff) are what they are without the flags."""
+        omega_ff) are what they are without the flags.  field_precision='f32x2' evaluates `omega_ff` and the gradient fields (and
+        with them `q_ff`) with the pairs in hi+lo fp32: float64 arrays as before, <= 2e-6 of the field's maximum wherever the
+        wake lies.  `psi_ff` stays float64 (its logarithm has no fp32 route); u_ff, w_ff and ome_ff follow the run's `precision`
+        as they always do."""
+        if field_precision not in ('f64', 'f32x2'):
+            raise ValueError(f"field_precision must be 'f64' or 'f32x2', not {field_precision!r}")
+        if field_precision == 'f32x2' and self._shard is not None and self._shard.world > 1:
+            raise ValueError("gradient fields run on one GPU: not with `distributed` or more than one device in `devices`")
         scalars = [kind for kind, on in (('psi', psi), ('omega', omega)) if on]
         if scalars:
             if self._shard is not None and self._shard.world > 1:
@@ -1933,6 +1944,19 @@ class LUDVM:
                 raise ValueError("gradient fields run on one GPU: not with `distributed` or more than one device in `devices`")
             if not hasattr(self.engine, 'flowfield_gradient'):
                 raise RuntimeError("flowfield(grad=True): this engine has no flowfield_gradient")
+        # the default calls the engine as it always was called; 'f32x2' needs an engine whose methods know the keyword
+        omega_kw = grad_kw = {}
+        if field_precision == 'f32x2':
+            def route(name):
+                try:
+                    known = 'precision' in inspect.signature(getattr(self.engine, name)).parameters
+                except (TypeError, ValueError):
+                    known = False
+                if not known:
+                    raise RuntimeError(f"flowfield(field_precision='f32x2'): this engine's {name} has no precision='f32x2'")
+                return {'precision': 'f32x2'}
+            omega_kw = route('flowfield_scalar') if omega else {}
+            grad_kw = route('flowfield_gradient') if grad else {}
         x1, z1 = np.arange(xmin, xmax, dr), np.arange(zmin, zmax, dr)
         nx, nz = len(x1), len(z1)
         x, z = np.meshgrid(x1, z1, indexing='ij')
@@ -1976,10 +2000,11 @@ class LUDVM:
                 u[ii], w[ii] = uf, wf
                 ome[ii] = self.engine.vorticity(uf, wf, dr)
             for kind in scalars:
-                extra[kind][ii] = self.engine.flowfield_scalar(kind, xmin, zmin, dr, nx, nz, g, xw, zw, self.v_core)
+                extra[kind][ii] = self.engine.flowfield_scalar(kind, xmin, zmin, dr, nx, nz, g, xw, zw, self.v_core,
+                                                               **(omega_kw if kind == 'omega' else {}))
             if grad:
                 gradient[0, ii], gradient[1, ii], gradient[2, ii] = self.engine.flowfield_gradient(xmin, zmin, dr, nx, nz, g, xw, zw,
-                                                                                                    self.v_core)
+                                                                                                    self.v_core, **grad_kw)
         self.x_ff, self.z_ff = x, z
         self.u_ff, self.w_ff = u, w
         self.ome_ff = ome

@@ -3,7 +3,8 @@ states how a launch of the direct pair kernels divides its sources and targets a
 C++17.  This module compiles, once per process, a few lines of main() around it with the host C++ compiler and returns what
 they print: constants() -- the plan's constants and default knobs --, plan(cases) -- a Plan per case --, origin_index(b, p, n)
 -- which vortex lends origin class (block b, index parity p) of n stored vortices its origin --, observer_plan(kind, count, ns_ub)
--- the launch of a marched observer's kernels (probes, tracers, survey) over `count` points with at most ns_ub sources.
+-- the launch of a marched observer's kernels (probes, tracers, survey) over `count` points with at most ns_ub sources,
+field_hilo_plan(plan_nt, ns) -- the source splits of the hi+lo fp32 field sums (analytic vorticity, velocity gradient).
 A case is a dict: precision ('f32' | 'f32x2' | 'f64'), ns, nt, and optionally local (positions on local origins: what
 LUDVM_PREC_F32 is wherever the library lays the positions out itself), grid_nz (> 0: a flow-field grid of that many points per
 row, nt = its points), slab (the results stay in the partial slabs for a fused finisher), plan_nt (the whole grid's points
@@ -36,6 +37,13 @@ int main(int argc, char** argv) {
       const ObserverPlan p = observer_plan(r, count, ns);
       std::printf("%lld %lld %lld %d %lld %zu %lld %lld\n", p.tiles, p.pad, p.chunk, p.nsplit, observer_want(r, count),
                   observer_slab_bytes(r, count), r.point_tile, r.src_tile);
+    }
+    return 0;
+  }
+  if (argc > 1 && std::strcmp(argv[1], "field_hilo") == 0) {
+    for (long long nt, ns; std::scanf("%lld %lld", &nt, &ns) == 2;) {
+      const FieldHiloPlan p = field_hilo_plan(nt, ns);
+      std::printf("%lld %d %lld %d %d\n", p.chunk, p.nsplit, kFieldHiloTargets, kFieldHiloTile, kFieldHiloPerLane);
     }
     return 0;
   }
@@ -132,3 +140,14 @@ def observer_plan(kind, count, ns_ub):
     assert len(out) == len(counts) * len(bounds)
     rows = [ObserverPlan(*map(int, l.split())) for l in out]
     return rows if hasattr(count, "__len__") or hasattr(ns_ub, "__len__") else rows[0]
+
+
+# nsplit splits of chunk sources (the last may hold fewer); targets: points of one workgroup (256 lanes x per_lane); tile:
+# sources staged at once
+FieldHiloPlan = collections.namedtuple("FieldHiloPlan", "chunk nsplit targets tile per_lane")
+
+
+def field_hilo_plan(plan_nt, ns):
+    """The source splits of field_hilo_f32 for plan_nt targets (the whole grid's points when the launch is a block of its rows)
+    and ns sources: a function of the two counts alone."""
+    return FieldHiloPlan(*map(int, _ask(["%d %d\n" % (int(plan_nt), int(ns))], "field_hilo")[0].split()))
