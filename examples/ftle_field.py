@@ -2,7 +2,7 @@
 """Forward-time FTLE field of the README case's wake, and a Q snapshot beside it.
 
 A mesh of passive tracers is released behind the plunging foil (tunnel frame: the mesh rides with the pivot until its release)
-and every tracer carries the deformation gradient F of its own path through the device-resident march (tracer_gradient=True):
+and every tracer carries the deformation gradient F of its own path through the device-resident march (tracer_gradient=True; --f32x2: 'f32x2'):
 no neighbouring paths are differenced, so the field does not saturate once neighbours separate.  The finite-time Lyapunov
 exponent ln sigma_max(F) / T over the rest of the run is printed as its ridge -- for every mesh column the height of the largest
 exponent: the material lines that bound the wake vortices -- and the Q / Okubo-Weiss field `q_ff` = -ux^2 - uz wx of the same
@@ -24,7 +24,8 @@ ap.add_argument("--tf", type=float, default=20.0)
 ap.add_argument("--dt", type=float, default=5e-2)
 ap.add_argument("--release-at", type=float, default=0.5, help="fraction of the run after which the mesh is released")
 ap.add_argument("--dr", type=float, default=0.05, help="spacing of the tracer mesh")
-ap.add_argument("--f32x2", action="store_true", help="the Q snapshot's gradient sums in hi+lo fp32 (field_precision='f32x2')")
+ap.add_argument("--f32x2", action="store_true", help="hi+lo fp32 pair sums: the marched tracer mesh on tracer_precision='f32x2', tracer_gradient='f32x2', "
+                "and the Q snapshot's gradient sums with field_precision='f32x2'")
 ap.add_argument("--plot", default=None, help="write the FTLE field and the Q snapshot to this PNG")
 args = ap.parse_args()
 
@@ -36,7 +37,7 @@ X, Z = np.meshgrid(x1, z1, indexing="ij")
 M = X.size
 sim = LUDVM(t0=0, tf=args.tf, dt=args.dt, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012",
             verbose=False, tracers=np.stack([X.ravel(), Z.ravel()]), tracer_release=np.full(M, release), tracer_frame="tunnel",
-            tracer_gradient=True)
+            **(dict(tracer_precision="f32x2", tracer_gradient="f32x2") if args.f32x2 else dict(tracer_gradient=True)))
 last = sim.nt - 1
 T = sim.dt * (last - release + 1)
 ftle = sim.tracer_ftle().reshape(X.shape)

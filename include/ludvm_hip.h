@@ -469,7 +469,8 @@ int ludvm_march_set_tracer_precision(ludvm_ctx* ctx, int precision);
  * ln sigma_max(F) / T with T = dt (step - release + 1).
  *
  * ludvm_march_set_tracer_gradient: on = 1 makes the marched steps carry F (float64 tracers only: LUDVM_E_STATE while the
- *   tracer precision is 2, and ludvm_march_set_tracer_precision then refuses 2); F is [4][count], or NULL for the identity (a run
+ *   tracer precision is 2, and ludvm_march_set_tracer_precision then refuses 2; ludvm_march_set_tracer_gradient_f32x2, below,
+ *   is the hi+lo fp32 route); F is [4][count], or NULL for the identity (a run
  *   that is continued gives what ludvm_march_tracer_gradient_state returned).  on = 0 stops it.  Valid only while tracers are set
  *   (LUDVM_E_STATE otherwise); a flag other than 0 and 1 or an F that is not finite is LUDVM_E_ARG and changes nothing.
  *   ludvm_march_set_tracers and ludvm_march_setup reset it to off.
@@ -483,6 +484,27 @@ int ludvm_march_set_tracer_precision(ludvm_ctx* ctx, int precision);
 int ludvm_march_set_tracer_gradient(ludvm_ctx* ctx, int on, const double* F);
 int ludvm_march_read_tracer_gradient(ludvm_ctx* ctx, double* F, size_t rows_cap, long long* steps_out, size_t* nrows_out);
 int ludvm_march_tracer_gradient_state(ludvm_ctx* ctx, double* F);
+
+/* ---- the tracers' deformation gradient in hi+lo fp32 (an addition to ABI 7: detect it by symbol) ------------------
+ *
+ * The two setters above each refuse while the other is on; this entry sets both.  Every marched step then evaluates (u, w)_i
+ * AND the raw sums A, B, C of G_i at each released tracer in ONE walk over the step's sources (LUDVM.py:1095-1106's sources, as
+ * for the probes), in packed fp32 on hi+lo positions: per pair the operations of precision 2 above for u and w, operation for
+ * operation under the same launch plan, then the products of ludvm_gradient_f32x2 (below) from the same dx, dz, r2 and
+ * reciprocal square root; a tile's 256 pairs summed in fp32 (even and odd sources apart), the tile sums, the source splits,
+ * the Euler update, G_i and F <- (I + dt G_i) F in float64 as above (LUDVM.py:1120-1127's step and its exact derivative).
+ *
+ * ludvm_march_set_tracer_gradient_f32x2: sets the tracer precision to 2 and switches the deformation gradient on.  F has
+ *   ludvm_march_set_tracer_gradient's contract: NULL is the identity, otherwise [4][count] finite values (LUDVM_E_ARG, and
+ *   nothing changes, otherwise).  Valid only while tracers are set (LUDVM_E_STATE otherwise).  While it is on,
+ *   ludvm_march_set_tracer_gradient(ctx, 0, NULL) switches the gradient off and leaves plain precision-2 tracers,
+ *   ludvm_march_set_tracer_precision is LUDVM_E_STATE for either value, ludvm_march_read_tracer_gradient and
+ *   ludvm_march_tracer_gradient_state answer as they do for the float64 gradient; ludvm_march_set_tracers and ludvm_march_setup
+ *   reset everything.
+ * Guarantee: the tracer positions are, bit for bit, those of plain precision-2 tracers, and every other result of
+ *   ludvm_march_run keeps its bits; F repeats bit for bit however a run is cut into calls, but is not the float64 route's F: each
+ *   component of G_i is within ludvm_gradient_f32x2's bound of the exact sum, wherever the wake is. */
+int ludvm_march_set_tracer_gradient_f32x2(ludvm_ctx* ctx, const double* F);
 
 /* ---- wake survey: running field moments inside the march (an addition to ABI 7: detect it by symbol) -----------
  *

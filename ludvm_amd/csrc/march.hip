@@ -178,9 +178,11 @@ int march_tracer_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   double* out = static_cast<double*>(c->tracer_out.p);
   if (c->tracer_gradient) {
     double* gslab = static_cast<double*>(c->tracer_grad_part.p);
-    hipLaunchKernelGGL(march_grad_tracer_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, seed, seed + M,
-                       release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M, p.pad,
-                       (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+    // (hi+lo fp32: the plan's tiles, each spread over kTracerF32Tile / kTracerGradF32Tile workgroups; chunk, nsplit and pad are the plan's)
+    const unsigned gx = (unsigned)(f32x2 ? p.tiles * (kTracerF32Tile / kTracerGradF32Tile) : p.tiles);
+    hipLaunchKernelGGL(f32x2 ? march_f32x2_grad_tracer_partial : march_grad_tracer_partial, dim3(gx, (unsigned)p.nsplit), dim3(kBlock), 0,
+                       st, seed, seed + M, release, release + M, (const double*)cur, (const double*)(cur + M), shift, s, (long long)M,
+                       p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
                        static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, gslab);
     HIPCHK(c, hipGetLastError());
     const bool rec = rec_row >= 0;
@@ -515,8 +517,28 @@ int ludvm_march_set_tracer_precision(ludvm_ctx* c, int precision) {
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
   if (precision != 0 && precision != 2) return fail(c, LUDVM_E_ARG, "march: tracer precision is 0 (float64) or 2 (hi+lo fp32)");
+  if (c->tracer_gradient && c->tracer_precision == 2)
+    return fail(c, LUDVM_E_STATE, "march: the tracers carry their deformation gradient in hi+lo fp32 (ludvm_march_set_tracer_gradient_f32x2); "
+                                  "switch it off first");
   if (precision == 2 && c->tracer_gradient) return fail(c, LUDVM_E_STATE, "march: the tracers' deformation gradient needs float64 tracers");
   c->tracer_precision = precision;
+  return LUDVM_OK;
+}
+
+// F (NULL: the identity) into the resident F11 | F12 | F21 | F22 [M], and the five-column slab [split][5][m_pad] of `kind`'s plan
+// (5 / 2 of the plain one); the deformation gradient is on when this returns LUDVM_OK
+static int tracer_gradient_on(ludvm_ctx* c, const double* F, ObserverKind kind) {
+  const size_t M = c->tracer_count;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> f(4 * M, 0.0);
+  if (F) std::copy(F, F + 4 * M, f.begin());
+  else std::fill(f.begin(), f.begin() + M, 1.0), std::fill(f.begin() + 3 * M, f.end(), 1.0);
+  CHK(ensure(c, c->tracer_F, 4 * M * 8));
+  CHK(ensure(c, c->tracer_grad_part, observer_slab_bytes(kObserverRules[kind], (long long)M) / 2 * 5));
+  HIPCHK(c, hipMemcpyAsync(c->tracer_F.p, f.data(), 4 * M * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (f lives on this frame)
+  c->tracer_gradient = true;
+  c->tracer_grad_ran = false;
   return LUDVM_OK;
 }
 
@@ -530,21 +552,21 @@ int ludvm_march_set_tracer_gradient(ludvm_ctx* c, int on, const double* F) {
     for (size_t k = 0; k < 4 * M; ++k)
       if (!std::isfinite(F[k])) return fail(c, LUDVM_E_ARG, "march: the tracers' deformation gradient must be finite");
   if (!on) {
-    c->tracer_gradient = false;
+    c->tracer_gradient = false;      // (the tracers keep their precision: plain hi+lo fp32 tracers after the fp32 route)
     c->tracer_grad_ran = false;
     return LUDVM_OK;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  std::vector<double> f(4 * M, 0.0);
-  if (F) std::copy(F, F + 4 * M, f.begin());
-  else std::fill(f.begin(), f.begin() + M, 1.0), std::fill(f.begin() + 3 * M, f.end(), 1.0);
-  // (the five-column slab [split][5][m_pad] of kObsTracers' plan: 5 / 2 of the plain one)
-  CHK(ensure(c, c->tracer_F, 4 * M * 8));
-  CHK(ensure(c, c->tracer_grad_part, observer_slab_bytes(kObserverRules[kObsTracers], (long long)M) / 2 * 5));
-  HIPCHK(c, hipMemcpyAsync(c->tracer_F.p, f.data(), 4 * M * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // (f lives on this frame)
-  c->tracer_gradient = true;
-  c->tracer_grad_ran = false;
+  return tracer_gradient_on(c, F, kObsTracers);
+}
+
+int ludvm_march_set_tracer_gradient_f32x2(ludvm_ctx* c, const double* F) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->tracer_count == 0) return fail(c, LUDVM_E_STATE, "march: no tracers are set");
+  if (F)
+    for (size_t k = 0; k < 4 * c->tracer_count; ++k)
+      if (!std::isfinite(F[k])) return fail(c, LUDVM_E_ARG, "march: the tracers' deformation gradient must be finite");
+  CHK(tracer_gradient_on(c, F, kObsTracersF32x2));
+  c->tracer_precision = 2;
   return LUDVM_OK;
 }
 

@@ -1302,4 +1302,144 @@ march_f32x2_tracer_partial(const double* __restrict__ seed_x, const double* __re
   observer_store<kTracerF32PerLane, kBlock>(slab, m_pad, [&](int k, long long) { return free_[k]; }, au, aw);
 }
 
+// ---- the tracers' deformation gradient in hi+lo fp32 (ludvm_march_set_tracer_gradient_f32x2) ----------------------------------------
+// The five columns of march_grad_tracer_partial -- u | w | A | B | C -- from ONE walk in packed fp32 on hi+lo positions, for
+// march_grad_tracer_finish unchanged behind it (the float64 Euler step and F <- (I + dt G) F).
+// hilo_field_grad_f32 is the body: hilo_field_f32's staging, padding and splits, and per packed pair of sources
+//   first   pair2_f32's operations for tu, tw, operation for operation: dx dx, fma(dz, dz, .), fma(r2, r2, vc4), v_rsq_f32, the
+//           product with G, two fmas -- a tracer's (u, w), so its path, has the plain f32x2 tracers' bits
+//   then    from the same dx, dz, r2, y and G y, field_hilo_f32<true>'s terms in that kernel's product order (field_kernels.hpp:
+//           every factor of e's products is at most about 1, so no intermediate leaves fp32's range over |x| <= 1e4):
+//               C += (G y) (y y),   e = (G y) (y r2),   A += e (y (dx dz)),   B += e (y (dx^2 - dz^2))
+// One reciprocal square root per pair, five packed tile accumulators per point; 22 v_pk_*_f32 + 2 v_rsq_f32 per two pairs and
+// point (6 for the differences, 6 of pair2_f32, 10 of the gradient terms).  A pad pair adds exact zeros to all five (y = 0 there and every
+// product of y meets a finite partner).  At the end of a 256-source tile the low half, then the high half, of each accumulator
+// is added to the lane's float64 sum.
+template <int PPL>
+__device__ __forceinline__ void hilo_field_grad_f32(const double (&xd)[PPL], const double (&zd)[PPL], const double* __restrict__ xs,
+                                                    const double* __restrict__ zs, const double* __restrict__ gs, long long s_begin,
+                                                    long long s_end, double vc4, double (&au)[PPL], double (&aw)[PPL],
+                                                    double (&ga)[PPL], double (&gb)[PPL], double (&gc)[PPL]) {
+  static_assert(kHiloTile == kBlock, "one source slot per lane");
+  __shared__ __attribute__((aligned(16))) float lxh[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lxl[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lzh[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lzl[kHiloTile];
+  __shared__ __attribute__((aligned(16))) float lg[kHiloTile];
+  const int tid = threadIdx.x;
+  const float vc4s = (float)vc4;
+  const f32x2 vc4p = {vc4s, vc4s};
+  f32x2 xph[PPL], xpl[PPL], zph[PPL], zpl[PPL];
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    float h, l;
+    split_hilo(xd[k], h, l);
+    xph[k] = (f32x2){h, h}; xpl[k] = (f32x2){l, l};
+    split_hilo(zd[k], h, l);
+    zph[k] = (f32x2){h, h}; zpl[k] = (f32x2){l, l};
+  }
+  for (long long base = s_begin; base < s_end; base += kHiloTile) {
+    __syncthreads();                                // previous tile fully consumed
+    {
+      const long long si = base + tid;
+      float xh = kPadPosF, xl = 0.0f, zh = kPadPosF, zl = 0.0f, g = 0.0f;
+      if (si < s_end) {
+        split_hilo(xs[si], xh, xl);
+        split_hilo(zs[si], zh, zl);
+        g = (float)gs[si];
+      }
+      lxh[tid] = xh; lxl[tid] = xl; lzh[tid] = zh; lzl[tid] = zl; lg[tid] = g;
+    }
+    __syncthreads();
+    f32x2 tu[PPL], tw[PPL], ta[PPL], tb[PPL], tc[PPL];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      tu[k] = (f32x2){0.0f, 0.0f}; tw[k] = (f32x2){0.0f, 0.0f};
+      ta[k] = (f32x2){0.0f, 0.0f}; tb[k] = (f32x2){0.0f, 0.0f}; tc[k] = (f32x2){0.0f, 0.0f};
+    }
+#pragma unroll 2
+    for (int j = 0; j < kHiloTile; j += 4) {
+      const f32x4 X = *reinterpret_cast<const f32x4*>(&lxh[j]);
+      const f32x4 XL = *reinterpret_cast<const f32x4*>(&lxl[j]);
+      const f32x4 Z = *reinterpret_cast<const f32x4*>(&lzh[j]);
+      const f32x4 ZL = *reinterpret_cast<const f32x4*>(&lzl[j]);
+      const f32x4 G = *reinterpret_cast<const f32x4*>(&lg[j]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const f32x2 xs2 = h ? (f32x2){X.z, X.w} : (f32x2){X.x, X.y};
+        const f32x2 xl2 = h ? (f32x2){XL.z, XL.w} : (f32x2){XL.x, XL.y};
+        const f32x2 zs2 = h ? (f32x2){Z.z, Z.w} : (f32x2){Z.x, Z.y};
+        const f32x2 zl2 = h ? (f32x2){ZL.z, ZL.w} : (f32x2){ZL.x, ZL.y};
+        const f32x2 gs2 = h ? (f32x2){G.z, G.w} : (f32x2){G.x, G.y};
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) {
+          const f32x2 dx = (xph[k] - xs2) + (xpl[k] - xl2);
+          const f32x2 dz = (zph[k] - zs2) + (zpl[k] - zl2);
+          // (pair2_f32, operation for operation)
+          const f32x2 dxx = dx * dx;
+          const f32x2 r2 = __builtin_elementwise_fma(dz, dz, dxx);
+          const f32x2 q = __builtin_elementwise_fma(r2, r2, vc4p);
+          const f32x2 y = {__builtin_amdgcn_rsqf(q.x), __builtin_amdgcn_rsqf(q.y)};
+          const f32x2 gy = y * gs2;
+          tu[k] = __builtin_elementwise_fma(dz, gy, tu[k]);
+          tw[k] = __builtin_elementwise_fma(dx, gy, tw[k]);
+          // (field_hilo_f32<true>'s terms, in its product order)
+          tc[k] = __builtin_elementwise_fma(gy, y * y, tc[k]);
+          const f32x2 e = gy * (y * r2);
+          ta[k] = __builtin_elementwise_fma(e, y * (dx * dz), ta[k]);
+          tb[k] = __builtin_elementwise_fma(e, y * __builtin_elementwise_fma(-dz, dz, dxx), tb[k]);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+      au[k] += (double)tu[k].x; au[k] += (double)tu[k].y;
+      aw[k] += (double)tw[k].x; aw[k] += (double)tw[k].y;
+      ga[k] += (double)ta[k].x; ga[k] += (double)ta[k].y;
+      gb[k] += (double)tb[k].x; gb[k] += (double)tb[k].y;
+      gc[k] += (double)tc[k].x; gc[k] += (double)tc[k].y;
+    }
+  }
+}
+
+// march_f32x2_tracer_partial's loader, tiles_held test and pad position under the kObsTracersF32x2 plan (the same chunk, nsplit
+// and m_pad: the summation order of u and w is the plain f32x2 tracers'), hilo_field_grad_f32 as the body, and
+// march_grad_tracer_partial's slab [split][5][m_pad].  A workgroup owns kTracerGradF32Tile tracers (tracer t0 + k * 256 + lane in
+// register set k of the lane): kTracerF32Tile / kTracerGradF32Tile workgroups per tile of the plan.  Nothing of a tracer's sums
+// depends on that spread: every tracer sees the same operations on the same operands in the same order in whichever lane.
+constexpr int kTracerGradF32PerLane = 2;
+constexpr int kTracerGradF32Tile = kBlock * kTracerGradF32PerLane;
+
+__global__ void __launch_bounds__(kBlock)
+march_f32x2_grad_tracer_partial(const double* __restrict__ seed_x, const double* __restrict__ seed_z,
+                                const long long* __restrict__ release, const long long* __restrict__ tile_min, const double* cur_x,
+                                const double* cur_z, const double* shift, long long step, long long count, long long m_pad,
+                                const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
+                                const MarchState* S, int nfoil, long long chunk, double vc4, double* slab) {
+  constexpr int PPL = kTracerGradF32PerLane;
+  static_assert(kTracerGradF32Tile % kTracerTile == 0 && kTracerF32Tile % kTracerGradF32Tile == 0,
+                "whole tile_min entries per workgroup, whole workgroups per tile of the plan");
+  if (tiles_held<kTracerGradF32Tile / kTracerTile>(tile_min, step, count)) return;      // (uniform: before any barrier)
+  __builtin_amdgcn_s_setprio(3);
+  const SplitRange src = split_range(S, nfoil, chunk);
+  double xp[PPL], zp[PPL], au[PPL], aw[PPL], ga[PPL], gb[PPL], gc[PPL];
+  bool free_[PPL];
+  load_tracers<PPL>(seed_x, seed_z, release, cur_x, cur_z, shift, step, count, -(double)kPadPosF, xp, zp, au, aw, free_);
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) { ga[k] = 0.0; gb[k] = 0.0; gc[k] = 0.0; }
+  hilo_field_grad_f32<PPL>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw, ga, gb, gc);
+  double* row = slab + (long long)blockIdx.y * 5 * m_pad;
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long m = observer_point<PPL, kBlock>(k);
+    if (free_[k]) {
+      row[m] = au[k] * kInv2PiD;
+      row[m_pad + m] = -aw[k] * kInv2PiD;
+      row[2 * m_pad + m] = ga[k];
+      row[3 * m_pad + m] = gb[k];
+      row[4 * m_pad + m] = gc[k];
+    }
+  }
+}
+
 }  // namespace ludvm

@@ -552,6 +552,20 @@ class Engine:
                 raise ValueError("march_set_tracer_gradient: F must be [4, M]")
         self._check(self._lib.ludvm_march_set_tracer_gradient(self._ctx, code, _pd(f)))
 
+    def march_set_tracer_gradient_f32x2(self, F=None):
+        """The tracers' deformation gradient in hi+lo fp32 (ludvm_march_set_tracer_gradient_f32x2): sets the tracers' precision
+        to 'f32x2' and switches the gradient on -- u, w and the gradient's sums from one fp32 walk over the sources, the Euler
+        update and F <- (I + dt grad(u, w)) F in float64.  F as `march_set_tracer_gradient`'s.  Valid while tracers are set;
+        `march_set_tracer_gradient(False)` leaves plain 'f32x2' tracers."""
+        if not hasattr(self._lib, "ludvm_march_set_tracer_gradient_f32x2"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_tracer_gradient_f32x2")
+        f = None
+        if F is not None:
+            f = np.ascontiguousarray(F, dtype=np.float64)
+            if f.shape != (4, getattr(self, "_march_ntracers", 0)):
+                raise ValueError("march_set_tracer_gradient_f32x2: F must be [4, M]")
+        self._check(self._lib.ludvm_march_set_tracer_gradient_f32x2(self._ctx, _pd(f)))
+
     def march_tracer_gradient(self):
         """(steps int64 [R], F float64 [R, 4, M]): the deformation-gradient rows the last `march_run` call recorded, the steps of
         `march_tracers` (ludvm_march_read_tracer_gradient)."""

@@ -148,7 +148,13 @@ class LUDVM:
                  every other result keep their bits; F repeats bit for bit however the run is cut, checkpoints included (they
                  carry it).  Refused: without `tracers`, with march=False, with tracer_precision='f32x2', in a sweep, with
                  `distributed` or more than one device; a run that cannot take the march raises.  Out of scope: backward-time
-                 FTLE, the gradient on the per-step path
+                 FTLE, the gradient on the per-step path.
+                 'f32x2' (needs tracer_precision='f32x2'): the same F from ONE walk over the sources in packed fp32 on hi+lo
+                 positions -- per pair the plain 'f32x2' tracers' operations for u and w, then the gradient's three raw sums
+                 from the same differences and reciprocal square root; the tile sums, the Euler update and the product in
+                 float64.  The positions are, bit for bit, the plain 'f32x2' tracers'; each component of G_i is within
+                 (152 * 2^-23 + (ns + 16) * 2^-52) sum|G| / (2 pi v_core^2) of the exact sum wherever the wake is (DESIGN.md
+                 section 4.18 has the cost).  Same results, same refusals, `tracer_gradient` holds 'f32x2'
       survey     None (default), or the points of a wake survey: a [2, K] array (x row, z row), or a dict(xmin, xmax, zmin, zmax,
                  dr) meaning the mesh arange(xmin, xmax, dr) x arange(zmin, zmax, dr), x-major as `flowfield` builds it
                  (1 <= K <= 1048576).  In every sampled step the field of `probes` is evaluated at the points and added to
@@ -398,16 +404,22 @@ class LUDVM:
     @staticmethod
     def _check_tracer_gradient(tracer_gradient, traced, march=True, tracer_precision='f64'):
         """ValueError from the keywords alone (nothing else has been created yet)."""
-        if not isinstance(tracer_gradient, (bool, np.bool_)):
-            raise ValueError(f"tracer_gradient must be True or False (got {tracer_gradient!r})")
+        f32x2 = isinstance(tracer_gradient, str) and tracer_gradient == 'f32x2'
+        if not f32x2 and not isinstance(tracer_gradient, (bool, np.bool_)):
+            raise ValueError(f"tracer_gradient must be True or False, or 'f32x2' (got {tracer_gradient!r})")
         if not tracer_gradient:
             return
         if not traced:
             raise ValueError("tracer_gradient needs `tracers`")
         if not march:
             raise ValueError("tracer_gradient is evaluated inside the device-resident march: not with march=False")
-        if tracer_precision != 'f64':
-            raise ValueError(f"tracer_gradient needs float64 tracers: not with tracer_precision={tracer_precision!r}")
+        if f32x2:
+            if tracer_precision != 'f32x2':
+                raise ValueError("tracer_gradient='f32x2' needs tracer_precision='f32x2' (its positions are the hi+lo fp32 tracers'): "
+                                 f"not with tracer_precision={tracer_precision!r}")
+        elif tracer_precision != 'f64':
+            raise ValueError(f"tracer_gradient needs float64 tracers: not with tracer_precision={tracer_precision!r} "
+                             "(tracer_gradient='f32x2' is the fp32 route)")
 
     @staticmethod
     def _check_survey_gradient(survey_gradient, surveyed, survey_precision='f64'):
@@ -559,9 +571,9 @@ class LUDVM:
             self.tracer_precision = tracer_precision
             if self.tracer_precision != 'f64':      # (float64 tracers keep the checkpoints they had)
                 self._ctor.update(tracer_precision=self.tracer_precision)
-            self.tracer_gradient = bool(tracer_gradient)
+            self.tracer_gradient = 'f32x2' if isinstance(tracer_gradient, str) else bool(tracer_gradient)
             if self.tracer_gradient:                # (tracers without it likewise)
-                self._ctor.update(tracer_gradient=True)
+                self._ctor.update(tracer_gradient=self.tracer_gradient)
         if survey is not None:              # (likewise; a mesh travels as its five numbers)
             self._ctor.update(survey={k: float(v) for k, v in survey.items()} if isinstance(survey, dict) else survey_xz.tolist(),
                               survey_frame=survey_frame, survey_steps=list(survey_win))
@@ -1214,11 +1226,15 @@ class LUDVM:
         if S.sbins is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_bins'):
             raise RuntimeError("survey_bins: this engine marches but has no march_set_survey_bins (pass march=False for the per-step "
                                "path)")
-        f32_tracers = S.tracers is not None and self.tracer_precision == 'f32x2'
-        if f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_precision'):
-            raise RuntimeError("tracer_precision='f32x2': this engine marches but has no march_set_tracer_precision")
         grad_tracers = S.tracers is not None and self.tracer_gradient
-        if grad_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_gradient'):
+        # (tracer_gradient='f32x2': u, w and the gradient's sums from one hi+lo fp32 walk, so ONE setter for precision and gradient)
+        grad_f32_tracers = isinstance(grad_tracers, str) and grad_tracers == 'f32x2'
+        if grad_f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_gradient_f32x2'):
+            raise RuntimeError("tracer_gradient='f32x2': this engine marches but has no march_set_tracer_gradient_f32x2")
+        f32_tracers = S.tracers is not None and self.tracer_precision == 'f32x2'
+        if f32_tracers and not grad_f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_precision'):
+            raise RuntimeError("tracer_precision='f32x2': this engine marches but has no march_set_tracer_precision")
+        if grad_tracers and not grad_f32_tracers and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_tracer_gradient'):
             raise RuntimeError("tracer_gradient: this engine marches but has no march_set_tracer_gradient")
         f32_survey = S.survey is not None and self.survey_precision == 'f32'
         if f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_precision'):
@@ -1243,9 +1259,11 @@ class LUDVM:
             if S.tracers is not None:
                 eng.march_set_tracers(S.tracers[0], S.tracers[1], release=self.tracer_release,
                                       shift_x=self.xpiv if self.tracer_frame == 'tunnel' else None, cur=S.tcur, record_steps=S.trec)
-                if f32_tracers:
+                if grad_f32_tracers:
+                    eng.march_set_tracer_gradient_f32x2(F=S.tF)
+                elif f32_tracers:
                     eng.march_set_tracer_precision('f32x2')
-                if grad_tracers:
+                elif grad_tracers:
                     eng.march_set_tracer_gradient(True, F=S.tF)
             if S.survey is not None:
                 eng.march_set_survey(S.survey[0], S.survey[1], shift_x=self.xpiv if self.survey_frame == 'tunnel' else None,
@@ -1263,6 +1281,10 @@ class LUDVM:
                                                   bin_gsums=S.sbgsums if carried else None)
         if grad_survey and not S.can_march and not hasattr(eng, 'gradient_field'):
             raise RuntimeError("survey_gradient: the per-step path needs an engine with gradient_field")
+        if grad_f32_tracers and not S.can_march:
+            # (neither float64 nor the per-step path in its place)
+            raise RuntimeError("tracer_gradient='f32x2' is evaluated inside the device-resident march, which this run cannot take "
+                               "(an engine without march_run, method, Npoints or Ncoeffs outside its limits)")
         if f32_tracers and not S.can_march:
             # (no float64 in its place: the per-step path has no fp32 tracer sums)
             raise RuntimeError("tracer_precision='f32x2' is evaluated inside the device-resident march, which this run cannot take "
