@@ -778,6 +778,46 @@ int ludvm_ensemble_run_surveyed(ludvm_ctx* ctx, size_t members, int npan, int nc
                                 const double* sshift_x, size_t sshift_rows, long long first, long long stop, long long every,
                                 double* survey_sums, size_t survey_doubles);
 
+/* ---- bins of the survey in an ensemble: phase-locked (conditional) averages for every member -------------------------
+ *
+ * ludvm_ensemble_run_surveyed_binned is ludvm_ensemble_run_surveyed with the bins of ludvm_march_set_survey_bins accumulated
+ * inside the one launch.  In a sampled step i of member m whose entry b = bin_of_step[kin_off + i] is >= 0 the five terms u, w,
+ * u^2, w^2, u w that have just been added to the member's plain sums at point k are added, by the same lane, with the same
+ * expressions in the same order, to block b of the member's bin sums.
+ *   bin_of_step [bin_rows]      one entry per kinematics row (bin_rows = kin_rows): the bin of step i of member m is
+ *                               bin_of_step[kin_off + i], -1 for none; every entry lies in -1 .. nbins - 1.  Entries of steps
+ *                               the window does not sample (row 0 included) are checked but not used; every member has a
+ *                               table of its own, so one nbins serves members of different periods, dt and length
+ *   nbins                       0 .. LUDVM_ENSEMBLE_MAX_SURVEY_BINS; 0 is ludvm_ensemble_run_surveyed itself (the bin arguments
+ *                               are not looked at)
+ *   bin_sums (host)             [members][nbins][5][nsurvey] doubles (bin_doubles = exactly that number).  The samples of a
+ *                               bin are the caller's to count, from the table and the window
+ * Every other argument, output, limit and guarantee is ludvm_ensemble_run_surveyed's, and those outputs -- rows, wake records,
+ * wake_n, probe rows, tracer records and the plain survey sums -- keep the bits of the same call without bins: the bins add
+ * five read-modify-writes per point to memory nothing else reads.  Block b of a member equals, bit for bit, the plain sums
+ * the member gets from ludvm_ensemble_run_surveyed when the sampled steps are exactly bin b's steps ((u, w) of a step do
+ * not depend on which other steps are sampled, and a block sees its steps in step order).  A member's bin sums do not depend
+ * on the batch and repeat bit for bit; a member differs from ludvm_march_run(LUDVM_PREC_F64) with ludvm_march_set_survey_bins
+ * by summation order only.  The library zero-fills both sum buffers on the call's stream and allocates everything before it
+ * launches anything; nothing is kept on the context.  Checked on the host before anything touches the device (LUDVM_E_ARG):
+ * nbins outside 0 .. 64, nbins > 0 with nsurvey = 0, null arrays, bin_rows != kin_rows, an entry outside -1 .. nbins - 1,
+ * bin_doubles != members * nbins * 5 * nsurvey, and members * (nbins + 1) * 40 * nsurvey bytes of plain and bin sums over
+ * 1 GiB (the message gives the size: split the batch).  A sharded context answers LUDVM_E_STATE.
+ * The entry point is an addition to ABI 7: detect it by its symbol. */
+#define LUDVM_ENSEMBLE_MAX_SURVEY_BINS 64
+int ludvm_ensemble_run_surveyed_binned(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars,
+                                       size_t scalar_count, const double* tables, const double* kin, size_t kin_rows,
+                                       const double* init, const double* free_xzg, size_t free_count, const long long* desc,
+                                       const long long* snap_steps, size_t nsnap, double* rows, size_t rows_count, double* wakes,
+                                       size_t wake_doubles, long long* wake_n, const double* probe_x, const double* probe_z,
+                                       size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w,
+                                       const double* seed_x, const double* seed_z, const long long* release, size_t ntracer,
+                                       const double* tshift_x, size_t tshift_rows, const long long* trec_steps, size_t ntrec,
+                                       double* tracer_rows, size_t tracer_doubles, const double* survey_x, const double* survey_z,
+                                       size_t nsurvey, const double* sshift_x, size_t sshift_rows, long long first, long long stop,
+                                       long long every, double* survey_sums, size_t survey_doubles, const int* bin_of_step,
+                                       size_t bin_rows, int nbins, double* bin_sums, size_t bin_doubles);
+
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 
 /* Grid targets generated on the device, x-major ravel like np.meshgrid(indexing='ij')

@@ -33,6 +33,7 @@ ENSEMBLE_MAX_TRACERS = 4096    # LUDVM_ENSEMBLE_MAX_TRACERS
 ENSEMBLE_TRACER_BYTES = 1 << 30  # most bytes of tracer records (members * (recorded steps + 1) * 2 * 8 * tracers) one ludvm_ensemble_run_traced call returns
 ENSEMBLE_MAX_SURVEY = 4096     # LUDVM_ENSEMBLE_MAX_SURVEY
 ENSEMBLE_SURVEY_BYTES = 1 << 30  # most bytes of survey sums (members * 5 * 8 * points) one ludvm_ensemble_run_surveyed call returns
+ENSEMBLE_MAX_SURVEY_BINS = 64  # LUDVM_ENSEMBLE_MAX_SURVEY_BINS; with bins ENSEMBLE_SURVEY_BYTES bounds members * (bins + 1) * 5 * 8 * points
 MARCH_MAX_PROBES = 4096  # LUDVM_MARCH_MAX_PROBES
 MARCH_MAX_TRACERS = 262144  # LUDVM_MARCH_MAX_TRACERS
 MARCH_MAX_SURVEY = 1048576  # LUDVM_MARCH_MAX_SURVEY
@@ -132,6 +133,12 @@ SIGNATURES = {
                                     POINTER(c_longlong), _pd, _pd, c_size_t, _pd, c_size_t, _pd, _pd,
                                     _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, POINTER(c_longlong), c_size_t, _pd, c_size_t,
                                     _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_size_t],
+    "ludvm_ensemble_run_surveyed_binned": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
+                                           POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
+                                           POINTER(c_longlong), _pd, _pd, c_size_t, _pd, c_size_t, _pd, _pd,
+                                           _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, POINTER(c_longlong), c_size_t, _pd, c_size_t,
+                                           _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_size_t,
+                                           POINTER(c_int), c_size_t, c_int, _pd, c_size_t],
     "ludvm_flowfield_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
                             c_double, _pf, _pf],
     "ludvm_flowfield_vorticity_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
@@ -169,7 +176,8 @@ ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm
                   "ludvm_gradient_f64", "ludvm_flowfield_gradient_rows_f64", "ludvm_march_set_tracer_gradient",
                   "ludvm_march_read_tracer_gradient", "ludvm_march_tracer_gradient_state", "ludvm_march_set_survey_gradient",
                   "ludvm_march_read_survey_gradient", "ludvm_scalar_f32x2", "ludvm_flowfield_scalar_rows_f32x2",
-                  "ludvm_gradient_f32x2", "ludvm_flowfield_gradient_rows_f32x2", "ludvm_march_set_tracer_gradient_f32x2")
+                  "ludvm_gradient_f32x2", "ludvm_flowfield_gradient_rows_f32x2", "ludvm_march_set_tracer_gradient_f32x2",
+                  "ludvm_ensemble_run_surveyed_binned")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -34,6 +34,10 @@
 //                      the K survey points of the sweep, shifted by the member's own offset of the step, then the member's five
 //                      raw sums [5][K] += u, w, u^2, w^2, u w by the lane that owns the point.  The phase reads the slab and
 //                      writes nothing but the member's sums: ensemble_march / ensemble_traced do not contain it.
+// With bins of the survey (ensemble_binned<PROBES, TRACERS>; the definition of march_binned_survey_finish), inside 2s:
+//   2s. bins           on a sampled step whose entry b of the member's table is >= 0 the lane that has just added a point's
+//                      five terms to the plain sums adds the same five terms to block b of the member's bin sums [B][5][K].
+//                      Nothing else changes: ensemble_surveyed does not contain it.
 //
 
 // Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
@@ -243,14 +247,24 @@ struct EnsembleSurvey {
   double* sums;                 // [5][K] raw sums of this member: u, w, u^2, w^2, u w (zero before the launch)
 };
 
+// The bins of a member's survey (ensemble_binned only), one record per member in a device array of its own indexed by
+// blockIdx.x: EnsembleMember, EnsembleTracers and EnsembleSurvey stay what the other kernels read.
+struct EnsembleSurveyBins {
+  const int* bin_of_step;       // nt entries of this member: the bin of a sampled step, -1 for none
+  double* sums;                 // [nbins][5][K] raw sums of this member, a block per bin (zero before the launch)
+};
+
 // One sampled step of the survey: sources [0, ns) of the member's slab -> (u, w) at the K points, each shifted by `shift` in
 // x, then sums[c][k] += for c = 0 .. 4, the terms formed as march_survey_finish forms them.  Tiles as ens_probe_row's, and
 // its order of summation: (u, w) are the bits of a probe row at the same points.  The lane that owns a point (the slice-0
-// lane of the sliced path) is the only writer of its five sums: plain loads and stores.  All threads of the workgroup call
-// this; it ends in a barrier.
+// lane of the sliced path) is the only writer of its five sums: plain loads and stores.  BINS: the same lane then adds the
+// same five terms to `bin` [5][K], the block of the step's bin (null: the step has none; the same for every lane).  All
+// threads of the workgroup call this; it ends in a barrier.
+template <bool BINS>
 __device__ __forceinline__ void ens_survey_step(const EnsembleSurvey& V, const double* __restrict__ xs, const double* __restrict__ zs,
                                                 const double* __restrict__ gs, long long ns, double shift, double vc4, double* lx,
-                                                double* lz, double* lg, double (*pu)[kBlock / 2], double (*pw)[kBlock / 2]) {
+                                                double* lz, double* lg, double (*pu)[kBlock / 2], double (*pw)[kBlock / 2],
+                                                [[maybe_unused]] double* bin) {
   const int j = threadIdx.x;
   const int K = (int)V.K;
   for (int t0 = 0; t0 < K; t0 += kBlock) {
@@ -287,18 +301,31 @@ __device__ __forceinline__ void ens_survey_step(const EnsembleSurvey& V, const d
       s[2 * (size_t)K] = __builtin_fma(u, u, s[2 * (size_t)K]);
       s[3 * (size_t)K] = __builtin_fma(w, w, s[3 * (size_t)K]);
       s[4 * (size_t)K] = __builtin_fma(u, w, s[4 * (size_t)K]);
+      if constexpr (BINS) {
+        if (bin) {
+          double* b = bin + k;
+          b[0] += u;
+          b[K] += w;
+          b[2 * (size_t)K] = __builtin_fma(u, u, b[2 * (size_t)K]);
+          b[3 * (size_t)K] = __builtin_fma(w, w, b[3 * (size_t)K]);
+          b[4 * (size_t)K] = __builtin_fma(u, w, b[4 * (size_t)K]);
+        }
+      }
     }
   }
   __syncthreads();
 }
 
 // The time loop of one member.  ensemble_march<PROBES> is <PROBES, false, false>: what it compiled to before there were tracers;
-// ensemble_traced<PROBES> is <PROBES, true, false>: what it compiled to before there was a survey.
-template <bool PROBES, bool TRACERS, bool SURVEY>
+// ensemble_traced<PROBES> is <PROBES, true, false>: what it compiled to before there was a survey; ensemble_surveyed<PROBES,
+// TRACERS> is <PROBES, TRACERS, true>: what it compiled to before there were bins.
+template <bool PROBES, bool TRACERS, bool SURVEY, bool BINS = false>
 __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps,
                                                int nsnap, const EnsembleTracers* __restrict__ tracers,
                                                const long long* __restrict__ trec_steps, int ntrec,
-                                               const EnsembleSurvey* __restrict__ surveys) {
+                                               const EnsembleSurvey* __restrict__ surveys,
+                                               [[maybe_unused]] const EnsembleSurveyBins* __restrict__ bins = nullptr) {
+  static_assert(SURVEY || !BINS, "bins belong to a survey");
   __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lz[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lg[kEnsTile + kEnsGroup];
@@ -537,8 +564,16 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
     if constexpr (SURVEY) {
       const EnsembleSurvey& V = surveys[blockIdx.x];
       // (the same for every lane of the workgroup: an unsampled step skips the phase before its first barrier)
-      if (step >= V.first && step < V.stop && (step - V.first) % V.every == 0)
-        ens_survey_step(V, xc, zc, g, n + npan, V.shift ? V.shift[step] : 0.0, m.vc4, lx, lz, lg, pu, pw);
+      if (step >= V.first && step < V.stop && (step - V.first) % V.every == 0) {
+        double* bin = nullptr;
+        if constexpr (BINS) {
+          // (read once per sampled step; the same for every lane of the workgroup)
+          const EnsembleSurveyBins& Q = bins[blockIdx.x];
+          const int b = Q.bin_of_step[step];
+          if (b >= 0) bin = Q.sums + (size_t)b * 5 * (size_t)V.K;
+        }
+        ens_survey_step<BINS>(V, xc, zc, g, n + npan, V.shift ? V.shift[step] : 0.0, m.vc4, lx, lz, lg, pu, pw, bin);
+      }
     }
 
     // ---- 3. roll-up (:1095-1127) and 4. placement of the coming step (:672-681, :788-800) -------------------------------
@@ -605,6 +640,15 @@ ensemble_surveyed(const EnsembleMember* __restrict__ members, const long long* _
                   const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec,
                   const EnsembleSurvey* __restrict__ surveys) {
   ens_member_run<PROBES, TRACERS, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, surveys);
+}
+
+// ensemble_surveyed<PROBES, TRACERS> with the bins of phase 2s: the launches of ludvm_ensemble_run_surveyed_binned
+template <bool PROBES, bool TRACERS>
+__global__ void __launch_bounds__(kBlock)
+ensemble_binned(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap,
+                const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec,
+                const EnsembleSurvey* __restrict__ surveys, const EnsembleSurveyBins* __restrict__ bins) {
+  ens_member_run<PROBES, TRACERS, true, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, surveys, bins);
 }
 
 }  // namespace ludvm

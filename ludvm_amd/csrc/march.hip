@@ -988,10 +988,14 @@ struct EnsembleSurveyArgs {
   const double* shift_x = nullptr; size_t shift_rows = 0;
   long long first = 1, stop = 0, every = 1;
   double* sums = nullptr; size_t doubles = 0;
+  // the bins of ludvm_ensemble_run_surveyed_binned (nbins = 0: none, nothing else is looked at)
+  const int* bin_of_step = nullptr; size_t bin_rows = 0;
+  int nbins = 0;
+  double* bin_sums = nullptr; size_t bin_doubles = 0;
 };
 
 // ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at), ludvm_ensemble_run_probed, with tracers
-// ludvm_ensemble_run_traced and, with a survey, ludvm_ensemble_run_surveyed
+// ludvm_ensemble_run_traced, with a survey ludvm_ensemble_run_surveyed and, with bins, ludvm_ensemble_run_surveyed_binned
 int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
@@ -1060,6 +1064,24 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
                                       " points) are over 1 GiB; split the batch");
     if (sv.doubles != members * 5 * K) return fail(c, LUDVM_E_ARG, "ensemble: survey sums must hold members x 5 x points doubles");
   }
+  if (sv.nbins < 0 || sv.nbins > LUDVM_ENSEMBLE_MAX_SURVEY_BINS)
+    return fail(c, LUDVM_E_ARG, "ensemble: 0 <= survey bins <= " + std::to_string(LUDVM_ENSEMBLE_MAX_SURVEY_BINS));
+  const size_t B = (size_t)sv.nbins;
+  if (B) {
+    if (!K) return fail(c, LUDVM_E_ARG, "ensemble: survey bins need survey points");
+    if (!sv.bin_of_step || !sv.bin_sums) return fail(c, LUDVM_E_ARG, "null array");
+    if (sv.bin_rows != kin_rows) return fail(c, LUDVM_E_ARG, "ensemble: survey bins must be one per kinematics row");
+    for (size_t k = 0; k < sv.bin_rows; ++k)
+      if (sv.bin_of_step[k] < -1 || sv.bin_of_step[k] >= sv.nbins)
+        return fail(c, LUDVM_E_ARG, "ensemble: a survey bin is -1 (none) or 0 .. bins - 1");
+    // members x (bins + 1) x 5 x 8 x K bytes of plain and bin sums: at most 1 GiB
+    if (members > ((((size_t)1 << 30) / 40) / K) / (B + 1))
+      return fail(c, LUDVM_E_ARG, "ensemble: " + std::to_string(40.0 * (double)members * (double)(B + 1) * (double)K / (1 << 20)) +
+                                      " MiB of survey sums (5 x 8 x " + std::to_string(members) + " members x (" + std::to_string(B) +
+                                      " bins + 1) x " + std::to_string(K) + " points) are over 1 GiB; split the batch");
+    if (sv.bin_doubles != members * B * 5 * K)
+      return fail(c, LUDVM_E_ARG, "ensemble: survey bin sums must hold members x bins x 5 x points doubles");
+  }
   if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
     return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
@@ -1116,7 +1138,9 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   const size_t in_survey = K ? 2 * Arena::need(K, 8) + (sshift ? Arena::need(sv.shift_rows, 8) : 0) +
                                    Arena::need(members, sizeof(EnsembleSurvey))
                              : 0;
-  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey));
+  // (bins: the table and the members' bin records behind those; the bin sums behind the outputs)
+  const size_t in_bins = B ? Arena::need(sv.bin_rows, sizeof(int)) + Arena::need(members, sizeof(EnsembleSurveyBins)) : 0;
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey + in_bins));
   CHK(ensure(c, c->ens_work, work_doubles * 8));
   const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
   const size_t out_n = Arena::need(members * nrec, 8);
@@ -1124,7 +1148,8 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   const size_t trec_doubles = members * (ntrec + 1) * 2 * M;
   const size_t out_tracer = M ? Arena::need(trec_doubles, 8) : 0;
   const size_t out_survey = K ? Arena::need(members * 5 * K, 8) : 0;
-  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey));
+  const size_t out_bins = B ? Arena::need(members * B * 5 * K, 8) : 0;
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey + out_bins));
   Arena in(c->ens_in.p), out(c->ens_out.p);
   double* d_tab = in.take<double>(members * tab_doubles);
   double* d_kin = in.take<double>(kin_rows * krow);
@@ -1165,9 +1190,18 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     d_sv = in.take<EnsembleSurvey>(members);
     d_vsums = out.take<double>(members * 5 * K);
   }
+  int* d_btab = nullptr;
+  double* d_bsums = nullptr;
+  EnsembleSurveyBins* d_sb = nullptr;
+  if (B) {
+    d_btab = in.take<int>(sv.bin_rows);
+    d_sb = in.take<EnsembleSurveyBins>(members);
+    d_bsums = out.take<double>(members * B * 5 * K);
+  }
 
   std::vector<EnsembleMember> hm(members);
   std::vector<EnsembleSurvey> hv(K ? members : 0);
+  std::vector<EnsembleSurveyBins> hb(B ? members : 0);
   std::vector<EnsembleTracers> ht(M ? members : 0);
   std::vector<long long> tmin(ttiles, std::numeric_limits<long long>::max());     // earliest release step of each tile
   for (size_t k = 0; k < M; ++k) tmin[k / kBlock] = std::min(tmin[k / kBlock], tr.release[k]);
@@ -1208,6 +1242,10 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
       v.shift = d_vshift ? d_vshift + (size_t)d[1] : nullptr;
       v.first = sv.first; v.stop = sv.stop; v.every = sv.every;
       v.sums = d_vsums + mi * 5 * K;
+    }
+    if (B) {
+      hb[mi].bin_of_step = d_btab + (size_t)d[1];
+      hb[mi].sums = d_bsums + mi * B * 5 * K;
     }
     e.rows = d_rows + (size_t)d[4] * row_doubles;
     e.rec = d_wakes + (size_t)d[5];
@@ -1250,8 +1288,22 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     // (the kernel adds to the sums)
     HIPCHK(c, hipMemsetAsync(d_vsums, 0, members * 5 * K * 8, c->stream));
   }
+  if (B) {
+    HIPCHK(c, hipMemcpyAsync(d_btab, sv.bin_of_step, sv.bin_rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sb, hb.data(), members * sizeof(EnsembleSurveyBins), hipMemcpyHostToDevice, c->stream));
+    // (the kernel adds to the bin sums)
+    HIPCHK(c, hipMemsetAsync(d_bsums, 0, members * B * 5 * K * 8, c->stream));
+  }
   // ONE launch: a workgroup per member, all of its time steps inside
-  if (K) {
+  if (B) {
+    const dim3 grid((unsigned)members), block(kBlock);
+    const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
+    const long long* ar = d_trec; const EnsembleSurvey* av = d_sv; const EnsembleSurveyBins* ab = d_sb;
+    if (M && nprobe) hipLaunchKernelGGL((ensemble_binned<true, true>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab);
+    else if (M) hipLaunchKernelGGL((ensemble_binned<false, true>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab);
+    else if (nprobe) hipLaunchKernelGGL((ensemble_binned<true, false>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab);
+    else hipLaunchKernelGGL((ensemble_binned<false, false>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab);
+  } else if (K) {
     const dim3 grid((unsigned)members), block(kBlock);
     const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
     const long long* ar = d_trec; const EnsembleSurvey* av = d_sv;
@@ -1281,7 +1333,8 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   }
   if (M) HIPCHK(c, hipMemcpyAsync(tr.rows, d_trows, trec_doubles * 8, hipMemcpyDeviceToHost, c->stream));
   if (K) HIPCHK(c, hipMemcpyAsync(sv.sums, d_vsums, members * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv and tmin live on this frame)
+  if (B) HIPCHK(c, hipMemcpyAsync(sv.bin_sums, d_bsums, members * B * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv, hb and tmin live on this frame)
   return LUDVM_OK;
 }
 
@@ -1347,6 +1400,35 @@ int ludvm_ensemble_run_surveyed(ludvm_ctx* c, size_t members, int npan, int ncoe
   sv.shift_x = sshift_x; sv.shift_rows = sshift_rows;
   sv.first = first; sv.stop = stop; sv.every = every;
   sv.sums = survey_sums; sv.doubles = survey_doubles;
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
+                           shift_rows, probe_u, probe_w, tr, sv);
+}
+
+int ludvm_ensemble_run_surveyed_binned(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                                       const double* tables, const double* kin, size_t kin_rows, const double* init,
+                                       const double* free_xzg, size_t free_count, const long long* desc, const long long* snap_steps,
+                                       size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
+                                       long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
+                                       const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w, const double* seed_x,
+                                       const double* seed_z, const long long* release, size_t ntracer, const double* tshift_x,
+                                       size_t tshift_rows, const long long* trec_steps, size_t ntrec, double* tracer_rows,
+                                       size_t tracer_doubles, const double* survey_x, const double* survey_z, size_t nsurvey,
+                                       const double* sshift_x, size_t sshift_rows, long long first, long long stop, long long every,
+                                       double* survey_sums, size_t survey_doubles, const int* bin_of_step, size_t bin_rows, int nbins,
+                                       double* bin_sums, size_t bin_doubles) {
+  EnsembleTracerArgs tr;
+  tr.seed_x = seed_x; tr.seed_z = seed_z; tr.release = release; tr.count = ntracer;
+  tr.shift_x = tshift_x; tr.shift_rows = tshift_rows;
+  tr.rec_steps = trec_steps; tr.nrec = ntrec;
+  tr.rows = tracer_rows; tr.doubles = tracer_doubles;
+  EnsembleSurveyArgs sv;
+  sv.x = survey_x; sv.z = survey_z; sv.count = nsurvey;
+  sv.shift_x = sshift_x; sv.shift_rows = sshift_rows;
+  sv.first = first; sv.stop = stop; sv.every = every;
+  sv.sums = survey_sums; sv.doubles = survey_doubles;
+  sv.bin_of_step = bin_of_step; sv.bin_rows = bin_rows; sv.nbins = nbins;
+  sv.bin_sums = bin_sums; sv.bin_doubles = bin_doubles;
   return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
                            snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
                            shift_rows, probe_u, probe_w, tr, sv);

@@ -708,29 +708,52 @@ class Engine:
         (i - first) % every == 0) point k sits at (survey_x[k] + survey_shift_x[kin_off + i], survey_z[k]).
         -> `ensemble_run_traced`'s tuple with survey_sums [members, 5, K] appended: sum u, sum w, sum u^2, sum w^2, sum u w of
         each member over its sampled steps (counting them is the caller's)."""
-        if not hasattr(self._lib, "ludvm_ensemble_run_surveyed"):
-            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_ensemble_run_surveyed")
+        return self._ensemble_surveyed("ensemble_run_surveyed", None, npan, ncoef, scalars, tables, kin, init, free_xzg, desc,
+                                       snap_steps, survey_x, survey_z, survey_steps, survey_shift_x, seed_x, seed_z, release, shift_x,
+                                       record_steps, probe_x, probe_z, probe_shift_x)
+
+    def ensemble_run_surveyed_binned(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=(), *, survey_x,
+                                     survey_z, survey_steps, bin_of_step, nbins, survey_shift_x=None, seed_x=(), seed_z=(),
+                                     release=(), shift_x=None, record_steps=(), probe_x=None, probe_z=None, probe_shift_x=None):
+        """`ensemble_run_surveyed` (tracers and probes optional) with the survey's bins accumulated inside the launch
+        (ludvm_ensemble_run_surveyed_binned): bin_of_step holds one integer per row of `kin` -- the bin 0 .. nbins - 1 of step i
+        of a member at [kin_off + i], -1 for none (entries of steps the window does not sample are not used); 1 <= nbins <= 64.
+        -> `ensemble_run_surveyed`'s tuple with bin_sums [members, nbins, 5, K] appended: block b of a member holds its five raw
+        sums over its sampled steps of bin b (counting them is the caller's)."""
+        if int(nbins) < 1:
+            raise ValueError("ensemble_run_surveyed_binned: nbins >= 1 (without bins: ensemble_run_surveyed)")
+        table = np.ascontiguousarray(bin_of_step, dtype=np.intc).reshape(-1)
+        return self._ensemble_surveyed("ensemble_run_surveyed_binned", (table, int(nbins)), npan, ncoef, scalars, tables, kin, init,
+                                       free_xzg, desc, snap_steps, survey_x, survey_z, survey_steps, survey_shift_x, seed_x, seed_z,
+                                       release, shift_x, record_steps, probe_x, probe_z, probe_shift_x)
+
+    def _ensemble_surveyed(self, who, bins, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, survey_x, survey_z,
+                           survey_steps, survey_shift_x, seed_x, seed_z, release, shift_x, record_steps, probe_x, probe_z,
+                           probe_shift_x):
+        if not hasattr(self._lib, "ludvm_" + who):
+            raise LudvmHipError(_ffi.E_STATE, f"this build of the library has no ludvm_{who}")
         vx, vz = _f64(survey_x), _f64(survey_z)
         if len(vx) != len(vz):
-            raise ValueError("ensemble_run_surveyed: survey_x and survey_z must have the same length")
+            raise ValueError(f"{who}: survey_x and survey_z must have the same length")
         first, stop, every = (int(v) for v in survey_steps)
         vsh = None if survey_shift_x is None else _f64(survey_shift_x)
         sx, sz = _f64(seed_x), _f64(seed_z)
         rel = np.ascontiguousarray(release, dtype=np.int64).reshape(-1)
         if len(sx) != len(sz) or len(rel) != len(sx):
-            raise ValueError("ensemble_run_surveyed: seed_x, seed_z and release must have the same length")
+            raise ValueError(f"{who}: seed_x, seed_z and release must have the same length")
         sh = None if shift_x is None else _f64(shift_x)
         rec = np.ascontiguousarray(list(record_steps), dtype=np.int64).reshape(-1)
         probes = None
         if probe_x is not None or probe_z is not None:
             px, pz = _f64(probe_x), _f64(probe_z)
             if len(px) != len(pz):
-                raise ValueError("ensemble_run_surveyed: probe_x and probe_z must have the same length")
+                raise ValueError(f"{who}: probe_x and probe_z must have the same length")
             probes = (px, pz, None if probe_shift_x is None else _f64(probe_shift_x))
         return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, (sx, sz, rel, sh, rec),
-                              (vx, vz, vsh, first, stop, every))
+                              (vx, vz, vsh, first, stop, every), bins)
 
-    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None, survey=None):
+    def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None, survey=None,
+                  bins=None):
         npan, ncoef = int(npan), int(ncoef)
         desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
         members = desc.shape[0]
@@ -759,11 +782,18 @@ class Engine:
             if survey is not None:
                 vx, vz, vsh, first, stop, every = survey
                 sums = np.zeros([members, 5, len(vx)])
-                self._check(self._lib.ludvm_ensemble_run_surveyed(
-                    *args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh), _pd(pu), _pd(pw), _pd(sx), _pd(sz),
-                    rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),
-                    _pd(trows), trows.size, _pd(vx), _pd(vz), len(vx), _pd(vsh), 0 if vsh is None else len(vsh), first, stop, every,
-                    _pd(sums), sums.size))
+                sargs = (*args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh), _pd(pu), _pd(pw), _pd(sx), _pd(sz),
+                         rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),
+                         _pd(trows), trows.size, _pd(vx), _pd(vz), len(vx), _pd(vsh), 0 if vsh is None else len(vsh), first, stop,
+                         every, _pd(sums), sums.size)
+                if bins is not None:
+                    table, nbins = bins
+                    bsums = np.zeros([members, nbins, 5, len(vx)])
+                    self._check(self._lib.ludvm_ensemble_run_surveyed_binned(
+                        *sargs, table.ctypes.data_as(POINTER(c_int)), len(table), nbins, _pd(bsums), bsums.size))
+                    out = (rows, wakes, wake_n, trows) if probes is None else (rows, wakes, wake_n, trows, pu, pw)
+                    return out + (sums, bsums)
+                self._check(self._lib.ludvm_ensemble_run_surveyed(*sargs))
                 return (rows, wakes, wake_n, trows, sums) if probes is None else (rows, wakes, wake_n, trows, pu, pw, sums)
             self._check(self._lib.ludvm_ensemble_run_traced(
                 *args, _pd(px), _pd(pz), len(px), _pd(sh), 0 if sh is None else len(sh), _pd(pu), _pd(pw), _pd(sx), _pd(sz),

@@ -1,6 +1,7 @@
 """`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run; with velocity probes
 Engine.ensemble_run_probed / ludvm_ensemble_run_probed; with passive tracers Engine.ensemble_run_traced /
-ludvm_ensemble_run_traced; with a wake survey Engine.ensemble_run_surveyed / ludvm_ensemble_run_surveyed).
+ludvm_ensemble_run_traced; with a wake survey Engine.ensemble_run_surveyed / ludvm_ensemble_run_surveyed; with a phase-locked
+one Engine.ensemble_run_surveyed_binned / ludvm_ensemble_run_surveyed_binned).
 
 A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
 'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
@@ -22,6 +23,9 @@ from .ludvm import LUDVM, SparseHistory
 
 __all__ = ["sweep"]
 
+_BINS_SOLO = ("the bins of a sweep are common to it: sweep(cases, survey=..., survey_phases=...) -- survey_bins / survey_period / "
+              "survey_phase0 belong to a solo run, LUDVM(..., survey=..., survey_bins=...)")
+
 _REFUSED = {
     # keyword -> (value that is fine, why not otherwise)
     "checkpoint_every": (0, "a sweep has no checkpoint / resume"),
@@ -38,9 +42,9 @@ _REFUSED = {
     "survey": (None, "the survey of a sweep is common to it: sweep(cases, survey=...)"),
     "survey_steps": (None, "the survey of a sweep is common to it: sweep(cases, survey=...)"),
     "survey_frame": ("lab", "the survey of a sweep is common to it: sweep(cases, survey=...)"),
-    "survey_bins": (None, "binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)"),
-    "survey_period": (None, "binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)"),
-    "survey_phase0": (None, "binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)"),
+    "survey_bins": (None, _BINS_SOLO),
+    "survey_period": (None, _BINS_SOLO),
+    "survey_phase0": (None, _BINS_SOLO),
 }
 
 
@@ -60,7 +64,7 @@ def _check_case(idx, kw, first):
     """Everything that can be refused from the keywords alone (no device, no engine call)."""
     who = f"sweep: member {idx}: "
     for key in ("engine", "device", "snapshot_steps", "verbose", "probes", "probe_frame", "particles", "particle_release",
-                "particle_frame", "particle_steps"):
+                "particle_frame", "particle_steps", "survey_phases"):
         if key in kw:
             raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
     if "survey_precision" in kw:
@@ -188,8 +192,73 @@ def _check_sweep_survey(survey, survey_frame, survey_steps, merged):
     return xz, shape, win
 
 
+def _check_sweep_phases(survey_phases, surveyed, merged):
+    """The sweep's bins -> (one table int64 [nt] per member: the bin of every sampled step, -1 elsewhere; B; the bin centres [B]
+    or None for explicit tables), or None without `survey_phases`; refused from the keywords alone.  A member's table is the one
+    a solo run builds (LUDVM._check_survey_bins) from its own time levels, t0 and frequency, its window clipped to its nt."""
+    if survey_phases is None:
+        return None
+    most = _ffi.ENSEMBLE_MAX_SURVEY_BINS
+    form = "survey_phases must be an int B or a sequence of one integer array [nt] per member"
+    if surveyed is None:
+        raise ValueError("sweep: survey_phases needs `survey`")
+    if isinstance(survey_phases, (bool, np.bool_)):
+        raise ValueError("sweep: " + form)
+    K, win = surveyed[0].shape[1], surveyed[2]
+    given = None
+    if isinstance(survey_phases, (int, np.integer)):
+        B = int(survey_phases)
+        if not 1 <= B <= most:
+            raise ValueError(f"sweep: survey_phases: 1 <= B <= {most} (got {B})")
+    else:
+        try:
+            given = list(survey_phases)
+        except TypeError as e:
+            raise ValueError("sweep: " + form) from e
+        if len(given) != len(merged):
+            raise ValueError(f"sweep: survey_phases: one table per member ({len(given)} tables for {len(merged)} members)")
+        tops = []
+        for idx, (raw, kw) in enumerate(zip(given, merged)):
+            nt = _time_levels(kw)
+            try:
+                raw = np.asarray(raw)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"sweep: member {idx}: " + form) from e
+            if raw.dtype.kind not in "iu" or raw.shape != (nt,):
+                raise ValueError(f"sweep: member {idx}: survey_phases: a table holds one integer per time step, [nt] with nt = {nt}")
+            if raw.min() < -1:
+                raise ValueError(f"sweep: member {idx}: survey_phases: a table's entries are -1 (no bin) or a bin 0 .. B-1")
+            given[idx] = raw.astype(np.int64)
+            tops.append(int(raw.max()))
+        B = max(tops) + 1
+        if B > most:
+            raise ValueError(f"sweep: member {int(np.argmax(tops))}: survey_phases: at most {most} bins (the table's largest entry is "
+                             f"{B - 1})")
+    size = len(merged) * (B + 1) * 5 * 8 * K
+    if size > _ffi.ENSEMBLE_SURVEY_BYTES:
+        raise ValueError(f"sweep: survey_phases: {len(merged)} members x ({B} bins + 1) x {K} points are {size} bytes "
+                         f"({size / 2**30:.2f} GiB) of survey sums, over the {_ffi.ENSEMBLE_SURVEY_BYTES >> 30} GiB one launch "
+                         "returns: split the case list")
+    tables, phase = [], None
+    for idx, kw in enumerate(merged):
+        t0, tf, dt = kw.get("t0", 0), kw.get("tf", 12), kw.get("dt", 1.5e-2)
+        t = np.arange(t0, tf + dt, dt)
+        f = kw.get("k", 0.2 * np.pi) * kw.get("Uinf", 1) / (2 * np.pi * kw.get("chord", 1))
+        if given is None and not f > 0:
+            raise ValueError(f"sweep: member {idx}: survey_phases={B}: the motion has no period (k = 0): give the sweep one table per "
+                             "member, or run the member on its own with survey_period")
+        try:
+            table, _, phase = LUDVM._check_survey_bins(B if given is None else given[idx], None, None, K,
+                                                       (win[0], min(win[1], len(t)), win[2]), t, t0, f)
+        except ValueError as e:
+            raise ValueError(f"sweep: member {idx}: " + str(e).replace("survey_bins", "survey_phases")) from e
+        tables.append(table)
+    return tables, B, phase
+
+
 def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", particles=None, particle_release=None,
-          particle_frame="lab", particle_steps=None, survey=None, survey_frame="lab", survey_steps=None, verbose=False, cls=LUDVM,
+          particle_frame="lab", particle_steps=None, survey=None, survey_frame="lab", survey_steps=None, survey_phases=None, verbose=False,
+          cls=LUDVM,
           **common):
     """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
     return the list of LUDVM objects, in order.  Each carries what a solo
@@ -225,6 +294,18 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     `particles` in one launch; everything else a member returns, probe rows and tracer paths included, is bit-identical to the
     sweep without a survey.
 
+    survey_phases: None, or the bins of a phase-locked survey, the sweep-level form of LUDVM(..., survey_bins=) (which, with
+    survey_period and survey_phase0, stays a solo keyword and is refused here).  An int B (1 .. 64) bins every member by its OWN
+    motion -- period 1 / f of the member, phase 0 at its t0, the table a solo run of the member builds with survey_bins=B -- so
+    members of different k, dt or tf get different tables under one B; a member without a period (k = 0) is refused by name.  Or
+    a sequence with one integer array [nt] per member, entries -1 (no bin) .. B - 1 with the meaning of the solo table; B is 1 + the
+    largest entry over all members, at most 64.  The bin sums are accumulated inside the one launch, by the lane that adds the
+    plain sums, and every member carries the attributes of a solo run with survey_bins: `survey_nbins`, `survey_bin_of_step`,
+    `survey_bin_count`, `survey_bin_sums` [B, 5, ...], `survey_bin_mean_u` / `_w`, `survey_bin_uu` / `_ww` / `_uw` (nan for an empty
+    bin), `survey_phase` (None for tables), `survey_coherent_*`, `survey_random_*`, beside the plain survey attributes.  Composes
+    with `probes` and `particles`; everything else a member returns, the plain survey sums included, is bit-identical to the sweep
+    without survey_phases, and bin b's sums are bit for bit the plain sums of a sweep that samples exactly bin b's steps.
+
     Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
@@ -239,9 +320,13 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     finite, a survey_frame other than 'lab' / 'tunnel', survey_steps that are not three integers with first >= 1 and every >= 1
     or that hold no step of some member (named), survey_steps without `survey`, `survey_precision`, `tracer_precision`, `tracer_gradient` or `survey_gradient` anywhere (the sweep's or a member's), an engine without
     ensemble_run_surveyed, and
-    survey sums (40 bytes x members x K) over 1 GiB: split the case list.
+    survey sums (40 bytes x members x K) over 1 GiB: split the case list; `survey_phases` inside a member's dict, without `survey`,
+    a bool, B outside 1 .. 64, a sequence that does not hold one table per member, a table (member named) that is not an integer
+    array [nt] or has entries below -1, a member none of whose sampled steps has a bin, `survey_bins` / `survey_period` /
+    `survey_phase0` anywhere, an engine without ensemble_run_surveyed_binned, and plain and bin sums (40 bytes x members x (B + 1)
+    x K) over 1 GiB: split the case list.
 
-    Out of scope: per-member probe, seed or survey point sets and windows, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe, seed or survey point sets and windows, gradient or harmonic sums of a survey in a sweep, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     if "survey_precision" in common:
         raise ValueError(f"sweep: survey_precision={common['survey_precision']!r}: the survey of a sweep is evaluated in float64 "
@@ -257,7 +342,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
                          "(run a member on its own, LUDVM(..., survey=..., survey_gradient=True))")
     for key in ("survey_bins", "survey_period", "survey_phase0"):
         if common.get(key) is not None:
-            raise ValueError(f"sweep: {key}={common[key]!r}: binned surveys run solo for now: LUDVM(..., survey=..., survey_bins=...)")
+            raise ValueError(f"sweep: {key}={common[key]!r}: {_BINS_SOLO}")
     cases = list(cases)
     if not cases:
         return []
@@ -271,6 +356,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     probe_xz = _check_sweep_probes(probes, probe_frame, merged)
     traced = _check_sweep_particles(particles, particle_release, particle_frame, particle_steps, snapshot_steps, merged)
     surveyed = _check_sweep_survey(survey, survey_frame, survey_steps, merged)
+    binned = _check_sweep_phases(survey_phases, surveyed, merged)
     if engine is None:
         from .engine import Engine
         engine = Engine(device)
@@ -282,6 +368,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         raise ValueError("sweep: particles: this engine has no ensemble_run_traced")
     if surveyed is not None and not hasattr(engine, "ensemble_run_surveyed"):
         raise ValueError("sweep: survey: this engine has no ensemble_run_surveyed")
+    if binned is not None and not hasattr(engine, "ensemble_run_surveyed_binned"):
+        raise ValueError("sweep: survey_phases: this engine has no ensemble_run_surveyed_binned")
     snaps = sorted({int(s) for s in snapshot_steps})
     dev_snaps = [s for s in snaps if s >= 1]
     if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
@@ -318,6 +406,10 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
             sim._survey_xz, sim._survey_shape = surveyed[0].copy(), surveyed[1]
             sim.survey_x, sim.survey_z = sim._survey_xz[0].reshape(surveyed[1]), sim._survey_xz[1].reshape(surveyed[1])
             sim.survey_frame, sim.survey_steps = survey_frame, (surveyed[2][0], min(surveyed[2][1], sim.nt), surveyed[2][2])
+            if binned is not None:
+                if len(binned[0][idx]) != sim.nt:       # (a .dat section or a subclass that sets its own time levels)
+                    raise ValueError(f"sweep: member {idx}: survey_phases: the member has {sim.nt} time levels, its table {len(binned[0][idx])}")
+                sim.survey_nbins, sim.survey_bin_of_step, sim.survey_phase = binned[1], binned[0][idx], binned[2]
         if probe_xz is not None or traced is not None or surveyed is not None:
             shift.append(np.asarray(sim.xpiv, dtype=float))
         nt, nf = sim.nt, S.nf
@@ -342,9 +434,16 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
                      survey_shift_x=np.concatenate(shift) if survey_frame == "tunnel" else None)
         if probe_xz is not None:
             targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
-            rows, wakes, wake_n, trows, pu, pw, ssums = engine.ensemble_run_surveyed(*packed, **targs)
+        if binned is not None:
+            # (one entry per kinematics row, like the offsets: member m's step i at [kin_off + i])
+            *out, ssums, bsums = engine.ensemble_run_surveyed_binned(*packed, **targs, bin_of_step=np.concatenate(binned[0]),
+                                                                     nbins=binned[1])
         else:
-            rows, wakes, wake_n, trows, ssums = engine.ensemble_run_surveyed(*packed, **targs)
+            *out, ssums = engine.ensemble_run_surveyed(*packed, **targs)
+        if probe_xz is not None:
+            rows, wakes, wake_n, trows, pu, pw = out
+        else:
+            rows, wakes, wake_n, trows = out
     elif traced is not None:
         if probe_xz is not None:
             targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
@@ -374,6 +473,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         if surveyed is not None:
             first, stop, every = sim.survey_steps
             sim._survey_results(ssums[idx], len(range(first, stop, every)))
+            if binned is not None:              # (the samples of a bin: counted on the host from the member's table)
+                table = sim.survey_bin_of_step
+                sim._survey_bin_results(bsums[idx], np.bincount(table[table >= 0], minlength=sim.survey_nbins))
         cap = nf + 2 * (nt - 1)
         R = rows[r0:r0 + nt - 1]
         hist = _RecordedWakes()

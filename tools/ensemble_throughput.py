@@ -24,7 +24,13 @@ at step 1, the last step recorded).
     python tools/ensemble_throughput.py --survey-leg [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_survey_cost.txt
 What a wake survey in a sweep costs: the same device call of 256 copies of config 1 without a survey on this
 build and on the parent build, alternated; then with K = 256 and K = 4096 survey points (a rake in the tunnel frame, every
-step sampled), and the probe phase on the K = 256 rake beside them."""
+step sampled), and the probe phase on the K = 256 rake beside them.
+
+    python tools/ensemble_throughput.py --survey-leg --bins 8 [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_survey_bins_cost.txt
+What the bins of a survey in a sweep cost: the surveyed device call of 256 copies of config 1 at K = 256 and K =
+4096 (every step sampled) on the parent build and on this one, alternated -- the same kernels -- and, on this build, the same
+call with every step in one of B phase bins of the stroke (ludvm_ensemble_run_surveyed_binned): the added time per sampled step,
+and beside it the call with ONE bin -- the same updates in the kernel, B times less to clear and to copy back."""
 import argparse
 import os
 import sys
@@ -43,6 +49,7 @@ ap.add_argument("--window", type=float, default=1.0, help="seconds a timed windo
 ap.add_argument("--probes-leg", action="store_true", help="the cost of probes in a sweep instead of the size ladder")
 ap.add_argument("--particles-leg", action="store_true", help="the cost of passive tracers in a sweep instead of the size ladder")
 ap.add_argument("--survey-leg", action="store_true", help="the cost of a wake survey in a sweep instead of the size ladder")
+ap.add_argument("--bins", type=int, default=0, help="survey leg: the cost of B phase bins over the plain survey instead (0: the plain leg)")
 ap.add_argument("--parent-lib", default="", help="probes / particles / survey leg: a build of the parent commit, timed beside this one")
 a = ap.parse_args()
 
@@ -372,9 +379,89 @@ def survey_leg():
         print("unsurveyed device call against the parent build: NOT MEASURED (no --parent-lib given)")
 
 
+def survey_bins_leg(nbins):
+    """Device call only, like the survey leg: B = 256 copies of config 1 packed once; the surveyed call with and without bins."""
+    B = 256
+    kept = {}
+    plain_call = inner
+
+    def keep(*args, **kw):
+        kept[len(args[7])] = args
+        return plain_call(*args, **kw)
+    eng.ensemble_run = keep
+    sims = sweep([dict(CONFIG1)] * B, engine=eng)
+    del eng.ensemble_run
+    engines = {"this build": eng}
+    if a.parent_lib:
+        engines["parent build"] = Engine(0, lib_path=os.path.abspath(a.parent_lib))
+    packed, s1 = kept[B], sims[0]
+    shift = np.concatenate([s.xpiv for s in sims])
+    # the phase bin of every step of config 1 (200 steps per period), the table `sweep(..., survey_phases=nbins)` builds
+    steps_per_period = int(round(1.0 / s1.f / s1.dt))
+    table = np.tile((np.arange(s1.nt) % steps_per_period) * nbins // steps_per_period, B)
+
+    def variant(which, K, bins):
+        e = engines[which]
+        vx, vz = np.full(K, 2.0), np.linspace(-2.0, 2.0, K)
+        kw = dict(survey_x=vx, survey_z=vz, survey_steps=(1, 1 << 62, 1), survey_shift_x=shift)
+        if bins:
+            # (one bin: the same ten memory operations per point and step, an eighth of the sums cleared and returned)
+            tb = table if bins > 1 else np.zeros_like(table)
+            return lambda: e.ensemble_run_surveyed_binned(*packed, **kw, bin_of_step=tb, nbins=bins)
+        return lambda: e.ensemble_run_surveyed(*packed, **kw)
+    order = []
+    for K in (256, 4096):
+        order += ([("parent build", K, 0)] if a.parent_lib else []) + [("this build", K, 0), ("this build", K, nbins)]
+        if nbins > 1:
+            order.append(("this build", K, 1))
+    calls = {v: variant(*v) for v in order}
+    reps_in = {}
+    for v, f in calls.items():                        # warm-up of every shape (buffers grow here)
+        f()
+        t0 = time.perf_counter()
+        f()
+        reps_in[v] = max(1, int(a.window / (time.perf_counter() - t0)))
+    T = {v: [] for v in order}
+    for _ in range(a.reps):                           # the variants alternated
+        for v, f in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps_in[v]):
+                f()
+            T[v].append((time.perf_counter() - t0) / reps_in[v] * 1e3)
+    print(f"# survey bins leg: device call (host clock around the synchronous entry point: uploads, ONE kernel, downloads) of 256 copies\n"
+          f"# of config 1 packed once, a survey of K points with every step sampled, without bins and with every step in one of {nbins} bins;\n"
+          "# ms per call, min / median / max over the windows and the build's own spread (max - min) / min")
+    nsrc = s1.n_freevort + np.arange(1, s1.nt) + np.cumsum((s1.LEV_shed[1:] != -1).astype(np.int64)) + s1.Npoints - 1
+    for v in order:
+        which, K, bins = v
+        t = np.array(T[v])
+        line = (f"{which:<13} B {B:4d}  K {K:5d}  bins {bins:2d}  windows of {reps_in[v]:3d}  device call {t.min():9.3f} / {np.median(t):9.3f} / "
+                f"{t.max():9.3f}  spread {(t.max() - t.min()) / t.min() * 100:5.2f} %")
+        if bins:
+            base = np.array(T[(which, K, 0)])
+            added = np.median(t) - np.median(base)
+            line += (f"\n{'':13} added over the plain survey {added:9.3f} ms per call ({added / np.median(base) * 100:+.2f} % of it; the plain "
+                     f"survey's own windows span {(base.max() - base.min()) / base.min() * 100:.2f} %) = {added / (s1.nt - 1) * 1e3:8.3f} us per "
+                     f"sampled step (of every member, side by side); {B * K * (s1.nt - 1) * 10:.3e} more memory operations against "
+                     f"{B * K * int(nsrc.sum()):.3e} survey pairs; bin sums returned {B * bins * 5 * K * 8 / 2**20:.1f} MiB beside "
+                     f"{B * 5 * K * 8 / 2**20:.1f} MiB of plain sums")
+        print(line, flush=True)
+    for K in (256, 4096):
+        if a.parent_lib:
+            p, n = np.array(T[("parent build", K, 0)]), np.array(T[("this build", K, 0)])
+            print(f"plain surveyed device call at K = {K}, this build against the parent build: median {np.median(n) / np.median(p):.4f} x; the "
+                  f"parent's own windows span {p.min():.3f} .. {p.max():.3f} ms, this build's {n.min():.3f} .. {n.max():.3f} ms: "
+                  f"{'inside' if p.min() <= np.median(n) <= p.max() else 'OUTSIDE'} the parent's run-to-run spread")
+        else:
+            print(f"plain surveyed device call at K = {K} against the parent build: NOT MEASURED (no --parent-lib given)")
+
+
 if a.survey_leg:
     eng.ensemble_run = inner
-    survey_leg()
+    if a.bins:
+        survey_bins_leg(a.bins)
+    else:
+        survey_leg()
     sys.exit(0)
 if a.particles_leg:
     eng.ensemble_run = inner
