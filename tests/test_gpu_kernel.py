@@ -1074,7 +1074,8 @@ def test_symmetric_kernel_rotation_split_variants(exp_eng, n):
     1, 2 or 4 wavefronts, by the size rule (0, the default: the rule's number for the bulk and four for the work items
     dispatched last -- mixed granularity -- where the rule gives fewer than four), with the mixed form at every size (-1) or
     at none (-2) (ludvm_set_sym_tuning): sampled targets against the C oracle, all vortices against the direct kernel; every
-    variant repeats bit for bit."""
+    variant repeats bit for bit.  At the smallest size (2.7e8 pairs: a fraction of a second of the C oracle) the oracle is taken at
+    ALL targets, for every variant."""
     import torch
     from ludvm_amd import LudvmHipError
     eng = exp_eng          # the measurement build: the negative codes force a variant at every size
@@ -1089,6 +1090,9 @@ def test_symmetric_kernel_rotation_split_variants(exp_eng, n):
     sel = np.r_[0:200, n - 200:n, rng.choice(n, 300, replace=False)]
     ur, wr = c_oracle.induced_velocity(g.astype(float), x.astype(float), z.astype(float), x[sel].astype(float),
                                        z[sel].astype(float), 0.065)
+    everywhere = n == 16384 + 77
+    if everywhere:
+        ua, wa = c_oracle.induced_velocity(g.astype(float), x.astype(float), z.astype(float), x.astype(float), z.astype(float), 0.065)
 
     def velocities():
         du.fill_(float("nan")); dw.fill_(float("nan"))
@@ -1107,6 +1111,8 @@ def test_symmetric_kernel_rotation_split_variants(exp_eng, n):
                 u, w = velocities()
                 assert _rel(u[sel], w[sel], ur, wr) < 1e-5, (t, r)
                 assert _rel(u, w, ud, wd) < 1e-5, (t, r)
+                if everywhere:
+                    assert _rel(u, w, ua, wa) < 1e-5, (t, r, "all targets")
                 u2, w2 = velocities()
                 assert np.array_equal(u, u2) and np.array_equal(w, w2), (t, r)
         with pytest.raises(LudvmHipError):
