@@ -8,7 +8,10 @@ phase are the extremes of the mean vorticity and the place of the largest mean Q
 and, over all samples, the enstrophy split into its coherent and random parts and the integral of the production of
 fluctuation energy -<u_i' u_j'> dU_i/dx_j, from the survey's own Reynolds stresses and mean gradient.
 
-    python examples/wake_vorticity.py [--tf 20] [--dt 5e-2] [--skip 0.25] [--dr 0.05] [--plot out.png]
+--f32x2 takes the same ten sums from one walk per sampled step in packed fp32 on hi+lo positions (survey_gradient='f32x2'): the
+same attributes from the same code, the pair sums -- the velocity's too -- at the hi+lo tier instead of float64.
+
+    python examples/wake_vorticity.py [--tf 20] [--dt 5e-2] [--skip 0.25] [--dr 0.05] [--f32x2] [--plot out.png]
 """
 import argparse
 import os
@@ -24,6 +27,7 @@ ap.add_argument("--tf", type=float, default=20.0)
 ap.add_argument("--dt", type=float, default=5e-2)
 ap.add_argument("--skip", type=float, default=0.25, help="fraction of the run left out of the averages (the starting vortex)")
 ap.add_argument("--dr", type=float, default=0.05, help="spacing of the survey mesh")
+ap.add_argument("--f32x2", action="store_true", help="the pair sums of the survey in hi+lo fp32 (survey_gradient='f32x2')")
 ap.add_argument("--plot", default=None, help="write the eight vorticity maps with their Q = 0 contours to this PNG")
 args = ap.parse_args()
 
@@ -33,7 +37,8 @@ B = 8
 # the mesh, x measured from the pivot: from the trailing edge to five chords behind it
 mesh = dict(xmin=0.8, xmax=5.8, zmin=-2.0, zmax=2.0, dr=args.dr)
 sim = LUDVM(t0=0, tf=args.tf, dt=args.dt, chord=1, rho=1.225, Uinf=1, Npoints=81, Ncoeffs=30, LESPcrit=0.2, Naca="0012",
-            verbose=False, survey=mesh, survey_frame="tunnel", survey_steps=(first, nt, 1), survey_bins=B, survey_gradient=True)
+            verbose=False, survey=mesh, survey_frame="tunnel", survey_steps=(first, nt, 1), survey_bins=B,
+            survey_gradient="f32x2" if args.f32x2 else True)
 x, z = sim.survey_x, sim.survey_z
 print(f"{x.size} survey points ({x.shape[0]} x {x.shape[1]}), steps {first} .. {nt - 1}: {sim.survey_count} samples, "
       f"{sim.survey_bin_count.tolist()} per phase bin")

@@ -621,6 +621,31 @@ int ludvm_march_read_survey_bins(ludvm_ctx* ctx, double* sums, long long* counts
 int ludvm_march_set_survey_gradient(ludvm_ctx* ctx, int on, const double* gsums, const double* bin_gsums);
 int ludvm_march_read_survey_gradient(ludvm_ctx* ctx, double* gsums, double* bin_gsums);
 
+/* ---- gradient sums of the survey in hi+lo fp32 (an addition to ABI 7: detect it by symbol) -----------------------
+ *
+ * The same ten sums with the pair arithmetic in fp32: every sampled step evaluates (u, w)_i AND the raw sums A, B, C at each
+ * survey point in ONE walk over the step's sources, in packed fp32 on hi+lo positions -- the walk of
+ * ludvm_march_set_tracer_gradient_f32x2 (above), per pair the operations of tracer precision 2 for u and w, then the products of
+ * ludvm_gradient_f32x2 (below) from the same dx, dz, r2 and reciprocal square root; a tile's 256 pairs summed in fp32 (even and
+ * odd sources apart), the tile sums, the source splits, ux, e, om, Q and all ten sums in float64 by the finishers of
+ * ludvm_march_set_survey_gradient.  The walk takes the place of the survey's pair walk, so the VELOCITY sums of such a survey
+ * are the fused walk's as well: hi+lo tier (within 2e-6 of max|u| of the float64 field), not the float64 survey's bits.  It is
+ * not a survey precision: ludvm_march_set_survey_precision stays at 0, and no origins, classes or guard are involved -- the
+ * error does not depend on where the wake is or on how far it has rolled up.
+ *
+ * ludvm_march_set_survey_gradient_f32x2: ludvm_march_set_survey_gradient's arguments without `on`, with its validation and its
+ *   codes: LUDVM_E_STATE when there is no survey, when the survey precision is 1, or when gsums is NULL although the survey or
+ *   one of its bins already has samples; LUDVM_E_ARG for bin_gsums without bins or without gsums and for a value that is not
+ *   finite.  A refused call leaves the context as it was.  While the route is on, ludvm_march_set_survey_precision(ctx, 1) is
+ *   LUDVM_E_STATE, ludvm_march_set_survey_gradient(ctx, 0, ..) removes the sums and the route,
+ *   ludvm_march_set_survey_gradient(ctx, 1, ..) switches to the float64 pair, ludvm_march_read_survey_gradient answers as before;
+ *   ludvm_march_set_survey, ludvm_march_set_survey_bins and ludvm_march_setup reset it: the call order stays survey, bins, gradient.
+ * Guarantees: everything else ludvm_march_run produces keeps its bits (the survey reads the wake and writes buffers of its own);
+ *   bin b's two blocks equal, bit for bit, the plain sums of such a survey that samples exactly bin b's steps; all sums repeat bit
+ *   for bit however a run is cut into calls; each gradient term is within ludvm_gradient_f32x2's bound of the exact sum (DESIGN.md
+ *   section 4.20).  A context without the route enqueues exactly what it enqueued before this entry existed. */
+int ludvm_march_set_survey_gradient_f32x2(ludvm_ctx* ctx, const double* gsums, const double* bin_gsums);
+
 /* ---- ensemble of small simulations: many whole runs of LUDVM.time_loop in one launch (LUDVM.py:597-1171) --------
  *
  * A parameter sweep (LESPcrit, k, alpha_max, dt, a gust vortex, 'Faure' / 'Ramesh') is `members` independent simulations,

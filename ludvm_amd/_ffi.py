@@ -112,6 +112,7 @@ SIGNATURES = {
     "ludvm_march_read_survey_bins": [c_void_p, _pd, POINTER(c_longlong)],
     "ludvm_march_set_survey_gradient": [c_void_p, c_int, _pd, _pd],
     "ludvm_march_read_survey_gradient": [c_void_p, _pd, _pd],
+    "ludvm_march_set_survey_gradient_f32x2": [c_void_p, _pd, _pd],
     "ludvm_march_set_tracer_precision": [c_void_p, c_int],
     "ludvm_march_set_tracer_gradient": [c_void_p, c_int, _pd],
     "ludvm_march_set_tracer_gradient_f32x2": [c_void_p, _pd],
@@ -177,7 +178,7 @@ ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm
                   "ludvm_march_read_tracer_gradient", "ludvm_march_tracer_gradient_state", "ludvm_march_set_survey_gradient",
                   "ludvm_march_read_survey_gradient", "ludvm_scalar_f32x2", "ludvm_flowfield_scalar_rows_f32x2",
                   "ludvm_gradient_f32x2", "ludvm_flowfield_gradient_rows_f32x2", "ludvm_march_set_tracer_gradient_f32x2",
-                  "ludvm_ensemble_run_surveyed_binned")
+                  "ludvm_ensemble_run_surveyed_binned", "ludvm_march_set_survey_gradient_f32x2")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

@@ -148,6 +148,9 @@ struct ludvm_ctx {
   // [nbins][5][K] and the five-column partial slab of one sampled step; the sample counts are the velocity sums' own
   Buf survey_gsums, survey_bin_gsums, survey_grad_part;
   bool survey_gradient = false;
+  // with survey_gradient: the five columns come from one walk in hi+lo fp32 under kObsSurveyF32's plan
+  // (ludvm_march_set_survey_gradient_f32x2); survey_precision stays 0
+  bool survey_gradient_f32x2 = false;
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

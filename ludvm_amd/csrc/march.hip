@@ -30,7 +30,7 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->survey_samples = 0;
   c->survey_precision = 0;
   c->survey_nbins = 0;      // ... and its bins (ludvm_march_set_survey_bins)
-  c->survey_gradient = false;
+  c->survey_gradient = c->survey_gradient_f32x2 = false;
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -130,6 +130,10 @@ static_assert(rule_is(kObsProbes, kProbeLanes, kFieldTile) && rule_is(kObsTracer
                   rule_is(kObsTracersF32x2, kTracerF32Tile, kHiloTile) && rule_is(kObsSurvey, kSurveyTile, kFieldTile) &&
                   rule_is(kObsSurveyF32, kSurveyF32Tile, kLocalTile),
               "the observer rules' point and source tiles are the kernels'");
+// the survey's hi+lo fp32 gradient walk runs under kObsSurveyF32: its source tile, and whole workgroups per tile of that plan
+static_assert(rule_is(kObsSurveyF32, kSurveyF32Tile, kHiloTile) && kSurveyF32Tile % kSurveyGradF32Tile == 0 &&
+                  kSurveyGradF32Tile == kBlock * kSurveyGradF32PerLane,
+              "march_f32x2_grad_survey_partial: kObsSurveyF32's tiles, spread over kSurveyF32Tile / kSurveyGradF32Tile workgroups");
 
 // the x offset of time step s (NULL: the lab frame)
 const double* step_shift(const Buf& shift, bool shifted, long long s) {
@@ -220,19 +224,22 @@ bool survey_samples_step(const ludvm_ctx* c, long long s) {
 int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s) {
   const MarchSetup& m = c->msetup;
   const size_t K = c->survey_count;
-  const bool f32 = c->survey_precision == 1;
-  const ObserverPlan p = observer_plan(kObserverRules[f32 ? kObsSurveyF32 : kObsSurvey], (long long)K, n_ub + (long long)m.npan);
+  const bool f32 = c->survey_precision == 1, gf32 = c->survey_gradient && c->survey_gradient_f32x2;
+  const ObserverPlan p = observer_plan(kObserverRules[f32 || gf32 ? kObsSurveyF32 : kObsSurvey], (long long)K, n_ub + (long long)m.npan);
   const double* pxz = static_cast<const double*>(c->survey_xz.p);
   const double* shift = step_shift(c->survey_shift, c->survey_shifted, s);
   const int bin = c->survey_nbins ? c->survey_bin_of_row[(size_t)s] : -1;
   if (c->survey_gradient) {
-    // the gradient pair takes the place of the plain pair under the same plan (float64: the setters see to it): the velocity
-    // sums keep their bits, the gradient sums and the five-column slab are further buffers of the survey's own
+    // the gradient pair takes the place of the plain pair.  float64: under the same plan (the setters see to it), the velocity
+    // sums keep their bits.  hi+lo fp32: kObsSurveyF32's plan, its tiles each spread over kSurveyF32Tile / kSurveyGradF32Tile
+    // workgroups (chunk, nsplit and pad are the plan's); the velocity sums are that walk's.  The gradient sums and the
+    // five-column slab are further buffers of the survey's own
     double* gslab = static_cast<double*>(c->survey_grad_part.p);
     double* sums = static_cast<double*>(c->survey_sums.p);
     double* gsums = static_cast<double*>(c->survey_gsums.p);
-    hipLaunchKernelGGL(march_grad_survey_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, pxz, pxz + K, shift,
-                       (long long)K, p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
+    const unsigned gx = (unsigned)(gf32 ? p.tiles * (kSurveyF32Tile / kSurveyGradF32Tile) : p.tiles);
+    hipLaunchKernelGGL(gf32 ? march_f32x2_grad_survey_partial : march_grad_survey_partial, dim3(gx, (unsigned)p.nsplit), dim3(kBlock), 0,
+                       st, pxz, pxz + K, shift, (long long)K, p.pad, (const double*)c->x64, (const double*)c->z64, (const double*)c->g64,
                        static_cast<const MarchState*>(c->march_state.p), m.npan, p.chunk, m.vc4, gslab);
     HIPCHK(c, hipGetLastError());
     if (bin >= 0)
@@ -321,7 +328,7 @@ int ludvm_march_set_survey(ludvm_ctx* c, const double* x, const double* z, size_
   c->survey_samples = 0;
   c->survey_precision = 0;         // float64 until ludvm_march_set_survey_precision says otherwise
   c->survey_nbins = 0;             // (and no bins until ludvm_march_set_survey_bins)
-  c->survey_gradient = false;      // (and no gradient sums until ludvm_march_set_survey_gradient)
+  c->survey_gradient = c->survey_gradient_f32x2 = false;      // (and no gradient sums until ludvm_march_set_survey_gradient)
   if (count == 0) return LUDVM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_sums, kSurveySums * count * 8));
@@ -347,14 +354,10 @@ int ludvm_march_set_survey_precision(ludvm_ctx* c, int precision) {
   return LUDVM_OK;
 }
 
-int ludvm_march_set_survey_gradient(ludvm_ctx* c, int on, const double* gsums, const double* bin_gsums) {
-  if (!c) return LUDVM_E_ARG;
-  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
-  if (on != 0 && on != 1) return fail(c, LUDVM_E_ARG, "march: the survey gradient flag is 0 or 1");
-  if (!on) {
-    c->survey_gradient = false;
-    return LUDVM_OK;
-  }
+// gsums / bin_gsums (NULL: zeros) into the resident gradient sums, and the five-column slab [split][5][k_pad] of `kind`'s plan
+// (5 / 2 of the plain one); the gradient sums are on, by the float64 pair (kObsSurvey) or by the hi+lo fp32 walk (kObsSurveyF32),
+// when this returns LUDVM_OK.  A refusal leaves the context as it was; a failure behind it, without gradient sums.
+static int survey_gradient_on(ludvm_ctx* c, const double* gsums, const double* bin_gsums, ObserverKind kind) {
   if (c->survey_precision != 0) return fail(c, LUDVM_E_STATE, "march: the survey's gradient sums need a float64 survey");
   const size_t K = c->survey_count, B = (size_t)c->survey_nbins;
   if (bin_gsums && B == 0) return fail(c, LUDVM_E_ARG, "march: survey bin gradient sums without survey bins");
@@ -369,12 +372,11 @@ int ludvm_march_set_survey_gradient(ludvm_ctx* c, int on, const double* gsums, c
     if (!std::isfinite(gsums[k])) return fail(c, LUDVM_E_ARG, "march: survey gradient sums must be finite");
   for (size_t k = 0; bin_gsums && k < B * kSurveySums * K; ++k)
     if (!std::isfinite(bin_gsums[k])) return fail(c, LUDVM_E_ARG, "march: survey bin gradient sums must be finite");
-  c->survey_gradient = false;      // (a failure from here on leaves the context without gradient sums)
+  c->survey_gradient = c->survey_gradient_f32x2 = false;      // (a failure from here on leaves the context without gradient sums)
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_gsums, kSurveySums * K * 8));
   if (B) CHK(ensure(c, c->survey_bin_gsums, B * kSurveySums * K * 8));
-  // (the five-column slab [split][5][k_pad] of kObsSurvey's plan: 5 / 2 of the plain one)
-  CHK(ensure(c, c->survey_grad_part, observer_slab_bytes(kObserverRules[kObsSurvey], (long long)K) / 2 * 5));
+  CHK(ensure(c, c->survey_grad_part, observer_slab_bytes(kObserverRules[kind], (long long)K) / 2 * 5));
   if (gsums) HIPCHK(c, hipMemcpyAsync(c->survey_gsums.p, gsums, kSurveySums * K * 8, hipMemcpyHostToDevice, c->stream));
   else HIPCHK(c, hipMemsetAsync(c->survey_gsums.p, 0, kSurveySums * K * 8, c->stream));
   if (B && bin_gsums)
@@ -382,7 +384,25 @@ int ludvm_march_set_survey_gradient(ludvm_ctx* c, int on, const double* gsums, c
   else if (B) HIPCHK(c, hipMemsetAsync(c->survey_bin_gsums.p, 0, B * kSurveySums * K * 8, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->survey_gradient = true;
+  c->survey_gradient_f32x2 = kind == kObsSurveyF32;
   return LUDVM_OK;
+}
+
+int ludvm_march_set_survey_gradient(ludvm_ctx* c, int on, const double* gsums, const double* bin_gsums) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  if (on != 0 && on != 1) return fail(c, LUDVM_E_ARG, "march: the survey gradient flag is 0 or 1");
+  if (!on) {
+    c->survey_gradient = c->survey_gradient_f32x2 = false;      // (the sums and, where it was on, the hi+lo fp32 route)
+    return LUDVM_OK;
+  }
+  return survey_gradient_on(c, gsums, bin_gsums, kObsSurvey);
+}
+
+int ludvm_march_set_survey_gradient_f32x2(ludvm_ctx* c, const double* gsums, const double* bin_gsums) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || c->survey_count == 0) return fail(c, LUDVM_E_STATE, "march: no survey is set");
+  return survey_gradient_on(c, gsums, bin_gsums, kObsSurveyF32);
 }
 
 int ludvm_march_read_survey_gradient(ludvm_ctx* c, double* gsums, double* bin_gsums) {
@@ -420,7 +440,7 @@ int ludvm_march_set_survey_bins(ludvm_ctx* c, const int* bin_of_row, size_t rows
     return fail(c, LUDVM_E_ARG, "march: at most " + std::to_string(LUDVM_MARCH_MAX_SURVEY_BINS) + " survey bins");
   if (nbins == 0) {
     c->survey_nbins = 0;
-    c->survey_gradient = false;    // (the gradient sums are set after the bins)
+    c->survey_gradient = c->survey_gradient_f32x2 = false;    // (the gradient sums are set after the bins)
     return LUDVM_OK;
   }
   if ((size_t)nbins * K > (size_t)LUDVM_MARCH_MAX_SURVEY_BIN_POINTS)
@@ -438,7 +458,7 @@ int ludvm_march_set_survey_bins(ludvm_ctx* c, const int* bin_of_row, size_t rows
   for (int b = 0; counts && b < nbins; ++b)
     if (counts[b] < 0) return fail(c, LUDVM_E_ARG, "march: survey bin counts must be >= 0");
   c->survey_nbins = 0;             // (a failure from here on leaves the context without bins)
-  c->survey_gradient = false;      // (the gradient sums are set after the bins)
+  c->survey_gradient = c->survey_gradient_f32x2 = false;      // (the gradient sums are set after the bins)
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure(c, c->survey_bin_sums, doubles * 8));
   if (sums) HIPCHK(c, hipMemcpyAsync(c->survey_bin_sums.p, sums, doubles * 8, hipMemcpyHostToDevice, c->stream));

@@ -1442,4 +1442,50 @@ march_f32x2_grad_tracer_partial(const double* __restrict__ seed_x, const double*
   }
 }
 
+// ---- the survey's gradient sums in hi+lo fp32 (ludvm_march_set_survey_gradient_f32x2) --------------------------------------------
+// The five columns of march_grad_survey_partial -- u | w | A | B | C -- from ONE walk in packed fp32 on hi+lo positions, for
+// march_grad_survey_finish / march_binned_grad_survey_finish unchanged behind it.  Made of existing pieces:
+//   loader  load_fixed_points, the survey's (the per-step shift included); a lane without a point walks along at -kPadPosF, as in
+//           the hi+lo tracer kernels (kPadPosD does not fit fp32), away from the sources' padding, and stores nothing
+//   body    hilo_field_grad_f32<2>, the tracers' instantiation: no classes, no guard, an error that does not grow with the distance
+//           from the coordinate origin.  A pad pair (G = 0 at hi = kPadPosF) adds exact zeros to all five accumulators: y = 0
+//           there and every product of y meets a finite partner (section 4.17's argument)
+//   plan    kObsSurveyF32's (chunk, nsplit and k_pad; its source tile is kHiloTile).  A workgroup owns kSurveyGradF32Tile points
+//           (point t0 + k * 256 + lane in register set k of the lane): kSurveyF32Tile / kSurveyGradF32Tile workgroups per tile of
+//           the plan.  A workgroup whose points all lie past `count` leaves before the first barrier
+//   store   march_grad_survey_partial's slab [split][5][k_pad], u and w scaled as there, A, B, C raw, where m < count
+// Nothing of a point's sums depends on the spread: every point sees the same operations on the same operands in the same order in
+// whichever lane or workgroup it lands.  The velocity columns are this walk's (hi+lo tier), not march_survey_partial's bits.
+constexpr int kSurveyGradF32PerLane = 2;
+constexpr int kSurveyGradF32Tile = kBlock * kSurveyGradF32PerLane;
+
+__global__ void __launch_bounds__(kBlock)
+march_f32x2_grad_survey_partial(const double* __restrict__ px, const double* __restrict__ pz, const double* shift, long long count,
+                                long long k_pad, const double* __restrict__ xs, const double* __restrict__ zs,
+                                const double* __restrict__ gs, const MarchState* S, int nfoil, long long chunk, double vc4,
+                                double* slab) {
+  constexpr int PPL = kSurveyGradF32PerLane;
+  static_assert(kSurveyF32Tile % kSurveyGradF32Tile == 0, "whole workgroups per tile of the plan");
+  if ((long long)blockIdx.x * kSurveyGradF32Tile >= count) return;      // (uniform: before any barrier)
+  __builtin_amdgcn_s_setprio(3);
+  const SplitRange src = split_range(S, nfoil, chunk);
+  double xp[PPL], zp[PPL], au[PPL], aw[PPL], ga[PPL], gb[PPL], gc[PPL];
+  load_fixed_points<PPL, kBlock>(px, pz, shift, count, -(double)kPadPosF, xp, zp, au, aw);
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) { ga[k] = 0.0; gb[k] = 0.0; gc[k] = 0.0; }
+  hilo_field_grad_f32<PPL>(xp, zp, xs, zs, gs, src.begin, src.end, vc4, au, aw, ga, gb, gc);
+  double* row = slab + (long long)blockIdx.y * 5 * k_pad;
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) {
+    const long long m = observer_point<PPL, kBlock>(k);
+    if (m < count) {
+      row[m] = au[k] * kInv2PiD;
+      row[k_pad + m] = -aw[k] * kInv2PiD;
+      row[2 * k_pad + m] = ga[k];
+      row[3 * k_pad + m] = gb[k];
+      row[4 * k_pad + m] = gc[k];
+    }
+  }
+}
+
 }  // namespace ludvm

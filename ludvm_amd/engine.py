@@ -628,6 +628,27 @@ class Engine:
                 raise ValueError("march_set_survey_gradient: bin_gsums must be [nbins, 5, K]")
         self._check(self._lib.ludvm_march_set_survey_gradient(self._ctx, code, _pd(g), _pd(bg)))
 
+    def march_set_survey_gradient_f32x2(self, gsums=None, bin_gsums=None):
+        """Gradient sums of the survey in hi+lo fp32 (ludvm_march_set_survey_gradient_f32x2): the ten sums of
+        `march_set_survey_gradient`, with u, w and the gradient's raw sums of every sampled step from ONE fp32 walk over the
+        sources on hi+lo positions; the tile sums, the splits and all ten sums stay float64.  The velocity sums of such a
+        survey are that walk's too (hi+lo tier, not the float64 survey's bits).  gsums and bin_gsums as
+        `march_set_survey_gradient`'s; valid while a float64 survey is set, after `march_set_survey` and
+        `march_set_survey_bins`, which forget it.  `march_set_survey_gradient(False)` removes the sums and the route."""
+        if not hasattr(self._lib, "ludvm_march_set_survey_gradient_f32x2"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_survey_gradient_f32x2")
+        K, B = getattr(self, "_march_nsurvey", 0), getattr(self, "_march_nbins", 0)
+        g = bg = None
+        if gsums is not None:
+            g = np.ascontiguousarray(gsums, dtype=np.float64)
+            if g.shape != (5, K):
+                raise ValueError("march_set_survey_gradient_f32x2: gsums must be [5, K]")
+        if bin_gsums is not None:
+            bg = np.ascontiguousarray(bin_gsums, dtype=np.float64)
+            if bg.ndim != 3 or bg.shape[1:] != (5, K) or (B and bg.shape[0] != B):
+                raise ValueError("march_set_survey_gradient_f32x2: bin_gsums must be [nbins, 5, K]")
+        self._check(self._lib.ludvm_march_set_survey_gradient_f32x2(self._ctx, _pd(g), _pd(bg)))
+
     def march_survey_gradient(self):
         """(gsums float64 [5, K], bin_gsums float64 [B, 5, K] or None without bins): the survey's gradient sums -- ux, e, omega,
         omega^2, Q per point -- as they stand (ludvm_march_read_survey_gradient); their counts are `march_survey`'s and

@@ -213,8 +213,17 @@ class LUDVM:
                  [B, 5, ...], `survey_bin_mean_ux`, `_strain`, `_omega`, `_q`, `survey_bin_omega2`, and `survey_coherent_omega2` /
                  `survey_random_omega2`, the variance of omega split as the velocity moments are.  The counts are the velocity
                  sums' own.  The sums are bit-identical however the run is cut, checkpoints included.  The
-                 per-step path (march=False) adds the same terms from `Engine.gradient_field`.  Refused: not a bool, without
-                 `survey`, with survey_precision='f32', in a sweep, with `devices` > 1 or `distributed`
+                 per-step path (march=False) adds the same terms from `Engine.gradient_field`.  Refused: not a bool or 'f32x2',
+                 without `survey`, with survey_precision='f32', in a sweep, with `devices` > 1 or `distributed`.
+                 'f32x2': the same ten sums and result attributes with the pair arithmetic in fp32 -- in every sampled step u, w
+                 and the raw sums A, B, C at every survey point come from ONE walk over the step's sources, in packed fp32 on
+                 hi+lo positions (the walk of tracer_gradient='f32x2'); tile sums, splits and all sums stay float64.  The fused
+                 walk takes the place of the survey's pair walk, so the VELOCITY sums of such a survey are the fused walk's too:
+                 hi+lo tier (means within 2e-6 of max|u| of the float64 survey's), not float64 bits.  The error does not depend
+                 on where the wake is or how far it has rolled up; every other result of the run keeps its bits; the sums are
+                 bit-identical however the run is cut, and a bin is still the plain sums of its steps.
+                 Not a survey precision: refused with survey_precision other than 'f64' (it brings its own arithmetic), with
+                 march=False, and with a run that cannot take the march (RuntimeError, no float64 in its place)
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -247,7 +256,7 @@ class LUDVM:
                     raise ValueError("tracers run on one GPU: not with more than one device in `devices`")
                 if kwargs.get('survey_gradient', False) is not False:
                     cls._check_survey_gradient(kwargs['survey_gradient'], kwargs.get('survey') is not None,
-                                               kwargs.get('survey_precision', 'f64'))
+                                               kwargs.get('survey_precision', 'f64'), kwargs.get('march', True))
                     raise ValueError("survey_gradient runs on one GPU: not with more than one device in `devices`")
                 if kwargs.get('survey') is not None:
                     cls._check_survey(kwargs['survey'], kwargs.get('survey_frame', 'lab'), kwargs.get('survey_steps'))
@@ -422,15 +431,22 @@ class LUDVM:
                              "(tracer_gradient='f32x2' is the fp32 route)")
 
     @staticmethod
-    def _check_survey_gradient(survey_gradient, surveyed, survey_precision='f64'):
+    def _check_survey_gradient(survey_gradient, surveyed, survey_precision='f64', march=True):
         """ValueError from the keywords alone (nothing else has been created yet)."""
-        if not isinstance(survey_gradient, (bool, np.bool_)):
-            raise ValueError(f"survey_gradient must be True or False (got {survey_gradient!r})")
+        f32x2 = isinstance(survey_gradient, str) and survey_gradient == 'f32x2'
+        if not f32x2 and not isinstance(survey_gradient, (bool, np.bool_)):
+            raise ValueError(f"survey_gradient must be True or False, or 'f32x2' (got {survey_gradient!r})")
         if not survey_gradient:
             return
         if not surveyed:
             raise ValueError("survey_gradient needs `survey`")
-        if survey_precision != 'f64':
+        if f32x2:
+            if survey_precision != 'f64':
+                raise ValueError("survey_gradient='f32x2' brings its own arithmetic (one hi+lo fp32 walk for the velocity and the "
+                                 f"gradient sums): not with survey_precision={survey_precision!r}")
+            if not march:
+                raise ValueError("survey_gradient='f32x2' is evaluated inside the device-resident march: not with march=False")
+        elif survey_precision != 'f64':
             raise ValueError(f"survey_gradient needs a float64 survey: not with survey_precision={survey_precision!r}")
 
     @staticmethod
@@ -537,7 +553,7 @@ class LUDVM:
             raise ValueError("survey_frame must be 'lab' or 'tunnel'")
         elif survey_steps is not None:
             raise ValueError("survey_steps needs `survey`")
-        self._check_survey_gradient(survey_gradient, survey is not None, survey_precision)
+        self._check_survey_gradient(survey_gradient, survey is not None, survey_precision, march)
         if survey_gradient and distributed is not None and distributed is not False:
             raise ValueError("survey_gradient runs on one GPU: not with `distributed`")
         self._check_survey_precision(survey_precision, survey is not None, march)
@@ -588,9 +604,9 @@ class LUDVM:
                                   survey_period=None if survey_period is None else float(survey_period),
                                   survey_phase0=None if survey_phase0 is None else float(survey_phase0))
                 self.survey_nbins, self.survey_bin_of_step, self.survey_phase = bin_count, bin_table, bin_phase
-            self.survey_gradient = bool(survey_gradient)
+            self.survey_gradient = 'f32x2' if isinstance(survey_gradient, str) else bool(survey_gradient)
             if self.survey_gradient:                # (a survey without it likewise)
-                self._ctor.update(survey_gradient=True)
+                self._ctor.update(survey_gradient=self.survey_gradient)
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -1240,7 +1256,11 @@ class LUDVM:
         if f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_precision'):
             raise RuntimeError("survey_precision='f32': this engine marches but has no march_set_survey_precision")
         grad_survey = S.sgsums is not None
-        if grad_survey and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_gradient'):
+        # (survey_gradient='f32x2': u, w and the gradient's sums of a sampled step from one hi+lo fp32 walk, a setter of its own)
+        grad_f32_survey = grad_survey and isinstance(self.survey_gradient, str) and self.survey_gradient == 'f32x2'
+        if grad_f32_survey and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_gradient_f32x2'):
+            raise RuntimeError("survey_gradient='f32x2': this engine marches but has no march_set_survey_gradient_f32x2")
+        if grad_survey and not grad_f32_survey and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_gradient'):
             raise RuntimeError("survey_gradient: this engine marches but has no march_set_survey_gradient (pass march=False for the "
                                "per-step path)")
         # preallocated host buffers for the two device calls of a step (engines that offer them)
@@ -1277,8 +1297,16 @@ class LUDVM:
                 if grad_survey:
                     # (after the survey and its bins, which forget it; sums that are carried go together with their counts)
                     carried = bool(S.scount) or (S.sbins is not None and bool(S.sbcounts.any()))
-                    eng.march_set_survey_gradient(True, gsums=S.sgsums if carried else None,
-                                                  bin_gsums=S.sbgsums if carried else None)
+                    if grad_f32_survey:
+                        eng.march_set_survey_gradient_f32x2(gsums=S.sgsums if carried else None,
+                                                            bin_gsums=S.sbgsums if carried else None)
+                    else:
+                        eng.march_set_survey_gradient(True, gsums=S.sgsums if carried else None,
+                                                      bin_gsums=S.sbgsums if carried else None)
+        if grad_f32_survey and not S.can_march:
+            # (neither float64 nor the per-step path in its place)
+            raise RuntimeError("survey_gradient='f32x2' is evaluated inside the device-resident march, which this run cannot take "
+                               "(an engine without march_run, method, Npoints or Ncoeffs outside its limits)")
         if grad_survey and not S.can_march and not hasattr(eng, 'gradient_field'):
             raise RuntimeError("survey_gradient: the per-step path needs an engine with gradient_field")
         if grad_f32_tracers and not S.can_march:

@@ -5,11 +5,13 @@
 A sampled step of a gradient survey against a sampled step of the plain float64 survey: the run of tools/tracer_gradient_cost.py
 (config 1's foil at dt = 1e-3, fp32 roll-up, sparse history), --points survey points in the tunnel frame, every step from --first
 on sampled, so that every sampled step sees the wake of that many steps: about 22 000 vortices at the defaults.  Plain run /
-survey / survey with survey_gradient=True alternated; the added wall time per sampled step of each, medians of --repeats runs,
-and their ratio.  The plain survey kernels are the parent build's, instruction for instruction: the gradient pair takes their
-place only when the flag is set.
+survey / survey with survey_gradient=True / survey with survey_gradient='f32x2' alternated; the added wall time per sampled step of
+each, medians of --repeats runs, and their ratios.  The plain survey kernels and the float64 gradient pair are the parent
+build's, instruction for instruction: the gradient pair takes the plain pair's place only when the flag is set, the hi+lo fp32
+walk only with 'f32x2'.
 
-Report only: no ratio is promised.  The same body costs 1.48 on the tracers (profiles/tracer_gradient_cost.txt)."""
+Report only: no ratio is promised.  The float64 body costs 1.48 on the tracers, the fused hi+lo walk 0.34 of the float64
+gradient-tracer step (profiles/tracer_gradient_cost.txt)."""
 import argparse
 import os
 import statistics
@@ -40,7 +42,8 @@ K = args.points
 rng = np.random.default_rng(1)
 surveyed = dict(survey=np.stack([rng.uniform(-1.0, 3.0, K), rng.uniform(-2.0, 2.0, K)]), survey_frame="tunnel",
                 survey_steps=(args.first, args.steps + 1, 1))
-variants = {"plain": {}, "survey": surveyed, "gradient": dict(surveyed, survey_gradient=True)}
+variants = {"plain": {}, "survey": surveyed, "gradient": dict(surveyed, survey_gradient=True),
+            "gradient_f32x2": dict(surveyed, survey_gradient="f32x2")}
 
 
 def run(extra):
@@ -64,13 +67,19 @@ lines += [f"# {sim.nt - 1} steps at dt = 1e-3 (config 1's foil, precision f32, s
           f"sampled: {sampled} sampled steps,",
           f"# sources {ns[args.first]} .. {ns[-1]}, {pairs:.4g} point pairs; runs alternated, medians of {args.repeats}"]
 for k in variants:
-    line = f"{k:9s} min {min(ts[k]):.4f} median {med[k]:.4f} max {max(ts[k]):.4f} s"
+    line = f"{k:14s} min {min(ts[k]):.4f} median {med[k]:.4f} max {max(ts[k]):.4f} s"
     if k != "plain":
         add = med[k] - med["plain"]
         line += f"; added {add:.4f} s = {add / sampled * 1e6:.2f} us per sampled step, {pairs / max(add, 1e-9):.3g} pairs/s of the added time"
     lines.append(line)
 lines.append(f"gradient-survey step / plain float64 survey step (added time per sampled step) = "
              f"{(med['gradient'] - med['plain']) / max(med['survey'] - med['plain'], 1e-9):.2f}")
+# (the denominator: the float64 gradient-survey step, survey_gradient=True -- the code path of the build before the route -- in the
+# same process and rounds)
+lines.append(f"'f32x2' gradient-survey step / float64 gradient-survey step (added time per sampled step) = "
+             f"{(med['gradient_f32x2'] - med['plain']) / max(med['gradient'] - med['plain'], 1e-9):.2f}")
+lines.append(f"'f32x2' gradient-survey step / plain float64 survey step (added time per sampled step) = "
+             f"{(med['gradient_f32x2'] - med['plain']) / max(med['survey'] - med['plain'], 1e-9):.2f}")
 report = "\n".join(lines) + "\n"
 print(report, end="")
 if args.out:
