@@ -843,6 +843,46 @@ int ludvm_ensemble_run_surveyed_binned(ludvm_ctx* ctx, size_t members, int npan,
                                        long long every, double* survey_sums, size_t survey_doubles, const int* bin_of_step,
                                        size_t bin_rows, int nbins, double* bin_sums, size_t bin_doubles);
 
+/* ---- gradient sums of the survey in an ensemble: mean vorticity, strain and Q for every member -----------------------
+ *
+ * ludvm_ensemble_run_surveyed_graded is ludvm_ensemble_run_surveyed_binned (nbins = 0 allowed: no bins) with the gradient sums
+ * of ludvm_march_set_survey_gradient accumulated inside the one launch.  The definition is the same: in a sampled step i of
+ * member m the closed-form gradient of the survey's field -- the same sources, wake and bound vortices of step i -- at
+ * (survey_x[k] + shift[i], survey_z[k]) gives, from the raw pair sums A, B, C of ludvm_gradient_f64,
+ *   ux = -A / pi    e = B / (2 pi)    om = -vcore^4 C / pi    Q = om^2 / 4 - ux^2 - e^2
+ * and the member's five gradient sums at point k grow by ux, e, om, om^2, Q, in step order, added by the lane that adds the
+ * velocity terms.  In a step with a bin b the same five terms are added to block b of the member's bin gradient sums.
+ *   grad_sums (host)            [members][5][nsurvey] doubles (grad_doubles = exactly that number): sum ux, sum e, sum om,
+ *                               sum om^2, sum Q of each member
+ *   bin_grad_sums (host)        [members][nbins][5][nsurvey] doubles (bin_grad_doubles = exactly that number); required exactly
+ *                               when nbins > 0 (nbins = 0: NULL and 0)
+ * grad_doubles = 0 with both arrays NULL is ludvm_ensemble_run_surveyed_binned itself.  Every other argument, output, limit and
+ * guarantee is ludvm_ensemble_run_surveyed_binned's, and those outputs -- rows, wake records, wake_n, probe rows, tracer
+ * records, the plain survey sums and the bin sums -- keep the bits of the same call without gradient sums: the pair walk forms
+ * (u, w) with the same operations in the same order and carries three more accumulators.  Block b of a member's bin gradient
+ * sums equals, bit for bit, the gradient sums the member gets when the sampled steps are exactly bin b's steps.  A member's
+ * gradient sums do not depend on the batch and repeat bit for bit; a member differs from ludvm_march_run(LUDVM_PREC_F64) with
+ * ludvm_march_set_survey_gradient by summation order only.  The library zero-fills all sum buffers on the call's stream and
+ * allocates everything before it launches anything; nothing is kept on the context.  Checked on the host before anything
+ * touches the device (LUDVM_E_ARG): grad_doubles > 0 with nsurvey = 0, grad_sums NULL, bin_grad_sums NULL with nbins > 0 or
+ * given with nbins = 0, grad_doubles != members * 5 * nsurvey, bin_grad_doubles != members * nbins * 5 * nsurvey, and
+ * members * (nbins + 1) * 80 * nsurvey bytes of plain, bin and gradient sums over 1 GiB (the message gives the size: split the
+ * batch).  A sharded context answers LUDVM_E_STATE.
+ * The entry point is an addition to ABI 7: detect it by its symbol. */
+int ludvm_ensemble_run_surveyed_graded(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars,
+                                       size_t scalar_count, const double* tables, const double* kin, size_t kin_rows,
+                                       const double* init, const double* free_xzg, size_t free_count, const long long* desc,
+                                       const long long* snap_steps, size_t nsnap, double* rows, size_t rows_count, double* wakes,
+                                       size_t wake_doubles, long long* wake_n, const double* probe_x, const double* probe_z,
+                                       size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w,
+                                       const double* seed_x, const double* seed_z, const long long* release, size_t ntracer,
+                                       const double* tshift_x, size_t tshift_rows, const long long* trec_steps, size_t ntrec,
+                                       double* tracer_rows, size_t tracer_doubles, const double* survey_x, const double* survey_z,
+                                       size_t nsurvey, const double* sshift_x, size_t sshift_rows, long long first, long long stop,
+                                       long long every, double* survey_sums, size_t survey_doubles, const int* bin_of_step,
+                                       size_t bin_rows, int nbins, double* bin_sums, size_t bin_doubles, double* grad_sums,
+                                       size_t grad_doubles, double* bin_grad_sums, size_t bin_grad_doubles);
+
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 
 /* Grid targets generated on the device, x-major ravel like np.meshgrid(indexing='ij')

@@ -38,6 +38,13 @@
 //   2s. bins           on a sampled step whose entry b of the member's table is >= 0 the lane that has just added a point's
 //                      five terms to the plain sums adds the same five terms to block b of the member's bin sums [B][5][K].
 //                      Nothing else changes: ensemble_surveyed does not contain it.
+// With gradient sums of the survey (ensemble_graded<PROBES, TRACERS>; the definition of march_grad_survey_partial /
+// march_grad_survey_finish and, with a bin, march_binned_grad_survey_finish), inside 2s:
+//   2s. gradient       the pair walk of a sampled step also carries the raw sums A, B, C of the closed-form velocity gradient
+//                      at the survey points; the lane that adds a point's velocity terms then adds ux, e, om, om^2, Q to the
+//                      member's gradient sums [5][K] and, on a step with a bin, to block b of its [B][5][K].  (u, w) keep their
+//                      bits: the velocity sums and bins are those of the sweep without gradient sums.  The bins' table is a
+//                      run-time value here (null: no bins).  Nothing else changes: no other kernel contains it.
 //
 
 // Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
@@ -129,6 +136,71 @@ __device__ __forceinline__ void ens_pair_sums(const double* __restrict__ xs, con
         for (int k = 0; k < kEnsGroup; ++k) { nx[k] = lx[j + kEnsGroup + k]; nz[k] = lz[j + kEnsGroup + k]; ng[k] = lg[j + kEnsGroup + k]; }
 #pragma unroll
         for (int k = 0; k < kEnsGroup; ++k) ens_pair(xp, zp, cx[k], cz[k], cg[k], vc4, au, aw);
+#pragma unroll
+        for (int k = 0; k < kEnsGroup; ++k) { cx[k] = nx[k]; cz[k] = nz[k]; cg[k] = ng[k]; }
+      }
+    }
+  }
+}
+
+// One Vatistas pair with the three raw sums of the closed-form gradient (ensemble_graded only): ens_pair's statements first,
+// operation for operation -- au and aw keep their bits -- then field_grad_f64's updates of A, B, C (march_kernels.hpp) in its
+// order.  A pad source (G = 0 at kPadPosD) adds exact zeros by the argument written there: y = 0 at the pad, and G y^3 is
+// multiplied in before r2 and dx dz, both finite.
+__device__ __forceinline__ void ens_grad_pair(double xp, double zp, double xs, double zs, double gs, double vc4, double& au, double& aw,
+                                              double& ga, double& gb, double& gc) {
+  const double dx = xp - xs;
+  const double dz = zp - zs;
+  const double dxx = dx * dx;
+  const double r2 = __builtin_fma(dz, dz, dxx);
+  const double q = __builtin_fma(r2, r2, vc4);
+  const double y = rsqrt_f64(q);
+  const double s = gs * y;
+  au = __builtin_fma(dz, s, au);
+  aw = __builtin_fma(dx, s, aw);
+  const double c = s * (y * y);                       // G y^3
+  const double e = c * r2;
+  gc += c;
+  ga = __builtin_fma(e, dx * dz, ga);
+  gb = __builtin_fma(e, __builtin_fma(-dz, dz, dxx), gb);
+}
+
+// ens_pair_sums with ens_grad_pair as the body: the same staging, the same four-ahead prefetching walk of the point-per-lane
+// path and the same slice ranges, so au and aw are ens_pair_sums' bits.  Raw sums: the caller scales.
+template <bool SLICED>
+__device__ __forceinline__ void ens_grad_pair_sums(const double* __restrict__ xs, const double* __restrict__ zs,
+                                                   const double* __restrict__ gs, long long ns, double xp, double zp, double vc4,
+                                                   bool mine, int slice, int slices, double* lx, double* lz, double* lg, double& au,
+                                                   double& aw, double& ga, double& gb, double& gc) {
+  const int tid = threadIdx.x;
+  const int sub = (kEnsTile + slices - 1) / slices;
+  au = 0.0; aw = 0.0; ga = 0.0; gb = 0.0; gc = 0.0;
+  for (long long base = 0; base < ns; base += kEnsTile) {
+    const int cnt = (int)(ns - base < kEnsTile ? ns - base : kEnsTile);
+    const int cnt_pad = (cnt + kEnsGroup - 1) / kEnsGroup * kEnsGroup;
+    __syncthreads();
+    if (tid < cnt_pad) {
+      const bool ok = tid < cnt;
+      lx[tid] = ok ? xs[base + tid] : kPadPosD; lz[tid] = ok ? zs[base + tid] : kPadPosD; lg[tid] = ok ? gs[base + tid] : 0.0;
+    }
+    __syncthreads();
+    if (!mine) continue;
+    if (SLICED) {
+      const int j0 = slice * sub;
+      int j1 = j0 + sub;
+      if (j1 > cnt) j1 = cnt;
+#pragma unroll 4
+      for (int j = j0; j < j1; ++j) ens_grad_pair(xp, zp, lx[j], lz[j], lg[j], vc4, au, aw, ga, gb, gc);
+    } else {
+      double cx[kEnsGroup], cz[kEnsGroup], cg[kEnsGroup];
+#pragma unroll
+      for (int k = 0; k < kEnsGroup; ++k) { cx[k] = lx[k]; cz[k] = lz[k]; cg[k] = lg[k]; }
+      for (int j = 0; j < cnt_pad; j += kEnsGroup) {
+        double nx[kEnsGroup], nz[kEnsGroup], ng[kEnsGroup];
+#pragma unroll
+        for (int k = 0; k < kEnsGroup; ++k) { nx[k] = lx[j + kEnsGroup + k]; nz[k] = lz[j + kEnsGroup + k]; ng[k] = lg[j + kEnsGroup + k]; }
+#pragma unroll
+        for (int k = 0; k < kEnsGroup; ++k) ens_grad_pair(xp, zp, cx[k], cz[k], cg[k], vc4, au, aw, ga, gb, gc);
 #pragma unroll
         for (int k = 0; k < kEnsGroup; ++k) { cx[k] = nx[k]; cz[k] = nz[k]; cg[k] = ng[k]; }
       }
@@ -316,16 +388,107 @@ __device__ __forceinline__ void ens_survey_step(const EnsembleSurvey& V, const d
   __syncthreads();
 }
 
+// The gradient sums of a member's survey (ensemble_graded only), one record per member in a device array of its own indexed by
+// blockIdx.x: EnsembleMember, EnsembleTracers, EnsembleSurvey and EnsembleSurveyBins stay what the other kernels read.
+struct EnsembleSurveyGrad {
+  double* sums;                 // [5][K] raw sums of this member: ux, e, om, om^2, Q (zero before the launch)
+  double* bin_sums;             // [nbins][5][K], a block per bin (zero before the launch), or null without bins
+};
+
+// ens_survey_step<true> with the gradient sums (the definition of march_grad_survey_partial / march_grad_survey_finish): the
+// walk is ens_grad_pair_sums, (u, w) and the ten velocity terms are formed and added exactly as ens_survey_step forms and adds
+// them -- the velocity sums keep the bits of the sweep without gradient sums.  On the sliced path the raw partials of A, B, C
+// are added in slice order like u and w; pu / pw carry (u, w), (A, B) and C in turn, a barrier between the rounds.  Then ux,
+// e, om as grad_split_sums forms them and survey_grad_add with stride K into `gsums`, and -- the step has a bin -- into `gbin`
+// [5][K], the bin's gradient block (`bin` and `gbin` are null together; the same for every lane).  The lane that owns a point
+// is the only writer of its ten sums and of its bin's ten: plain loads and stores.  All threads of the workgroup call this; it
+// ends in a barrier.
+__device__ __forceinline__ void ens_grad_survey_step(const EnsembleSurvey& V, const double* __restrict__ xs,
+                                                     const double* __restrict__ zs, const double* __restrict__ gs, long long ns,
+                                                     double shift, double vc4, double* lx, double* lz, double* lg,
+                                                     double (*pu)[kBlock / 2], double (*pw)[kBlock / 2], double* bin, double* gsums,
+                                                     double* gbin) {
+  const int j = threadIdx.x;
+  const int K = (int)V.K;
+  for (int t0 = 0; t0 < K; t0 += kBlock) {
+    const int cnt = K - t0 < kBlock ? K - t0 : kBlock;
+    double u = 0.0, w = 0.0, ga = 0.0, gb = 0.0, gc = 0.0;
+    int k = -1;                 // the point this lane adds to the sums, if any
+    if (cnt > kBlock / 2) {
+      const bool mine = j < cnt;
+      const double xp = mine ? V.x[t0 + j] + shift : 0.0, zp = mine ? V.z[t0 + j] : 0.0;
+      double au, aw;
+      ens_grad_pair_sums<false>(xs, zs, gs, ns, xp, zp, vc4, mine, 0, 1, lx, lz, lg, au, aw, ga, gb, gc);
+      u = au * kInv2PiD; w = -aw * kInv2PiD;
+      if (mine) k = t0 + j;
+    } else {
+      int slices = kBlock / cnt;
+      if (slices > kEnsSlicesMax) slices = kEnsSlicesMax;
+      const int slice = j / cnt, q = j - slice * cnt;
+      const bool mine = slice < slices;
+      const double xp = mine ? V.x[t0 + q] + shift : 0.0, zp = mine ? V.z[t0 + q] : 0.0;
+      double au, aw;
+      ens_grad_pair_sums<true>(xs, zs, gs, ns, xp, zp, vc4, mine, slice, slices, lx, lz, lg, au, aw, ga, gb, gc);
+      u = au * kInv2PiD; w = -aw * kInv2PiD;
+      if (mine && slice > 0) { pu[slice - 1][q] = u; pw[slice - 1][q] = w; }
+      __syncthreads();
+      if (slice == 0) {
+        for (int r = 1; r < slices; ++r) { u += pu[r - 1][q]; w += pw[r - 1][q]; }
+        k = t0 + q;
+      }
+      __syncthreads();
+      if (mine && slice > 0) { pu[slice - 1][q] = ga; pw[slice - 1][q] = gb; }
+      __syncthreads();
+      if (slice == 0)
+        for (int r = 1; r < slices; ++r) { ga += pu[r - 1][q]; gb += pw[r - 1][q]; }
+      __syncthreads();
+      if (mine && slice > 0) pu[slice - 1][q] = gc;
+      __syncthreads();
+      if (slice == 0)
+        for (int r = 1; r < slices; ++r) gc += pu[r - 1][q];
+    }
+    if (k >= 0) {
+      double* s = V.sums + k;
+      s[0] += u;
+      s[K] += w;
+      s[2 * (size_t)K] = __builtin_fma(u, u, s[2 * (size_t)K]);
+      s[3 * (size_t)K] = __builtin_fma(w, w, s[3 * (size_t)K]);
+      s[4 * (size_t)K] = __builtin_fma(u, w, s[4 * (size_t)K]);
+      // (grad_split_sums' three terms.  They are rounded HERE, for both blocks below: contraction is on and works one basic
+      // block at a time, so without the fences the `+=` of the plain sums -- in this block -- would fuse with these products
+      // while the bin's -- behind the branch -- would add the rounded values, and a bin would lose the bits of the plain sums
+      // of its steps)
+      double ux = -ga * kInvPiD, e = gb * kInv2PiD, om = -(vc4 * gc) * kInvPiD;
+      asm volatile("" : "+v"(ux), "+v"(e), "+v"(om));
+      survey_grad_add(gsums + k, K, ux, e, om);
+      if (bin) {
+        double* b = bin + k;
+        b[0] += u;
+        b[K] += w;
+        b[2 * (size_t)K] = __builtin_fma(u, u, b[2 * (size_t)K]);
+        b[3 * (size_t)K] = __builtin_fma(w, w, b[3 * (size_t)K]);
+        b[4 * (size_t)K] = __builtin_fma(u, w, b[4 * (size_t)K]);
+        survey_grad_add(gbin + k, K, ux, e, om);
+      }
+    }
+  }
+  __syncthreads();
+}
+
 // The time loop of one member.  ensemble_march<PROBES> is <PROBES, false, false>: what it compiled to before there were tracers;
 // ensemble_traced<PROBES> is <PROBES, true, false>: what it compiled to before there was a survey; ensemble_surveyed<PROBES,
-// TRACERS> is <PROBES, TRACERS, true>: what it compiled to before there were bins.
-template <bool PROBES, bool TRACERS, bool SURVEY, bool BINS = false>
+// TRACERS> is <PROBES, TRACERS, true>: what it compiled to before there were bins; ensemble_binned<PROBES, TRACERS> is <PROBES,
+// TRACERS, true, true>: what it compiled to before there were gradient sums.  GRAD (ensemble_graded) takes the bins' table as
+// a run-time value: a null table is a gradient survey without bins.
+template <bool PROBES, bool TRACERS, bool SURVEY, bool BINS = false, bool GRAD = false>
 __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps,
                                                int nsnap, const EnsembleTracers* __restrict__ tracers,
                                                const long long* __restrict__ trec_steps, int ntrec,
                                                const EnsembleSurvey* __restrict__ surveys,
-                                               [[maybe_unused]] const EnsembleSurveyBins* __restrict__ bins = nullptr) {
+                                               [[maybe_unused]] const EnsembleSurveyBins* __restrict__ bins = nullptr,
+                                               [[maybe_unused]] const EnsembleSurveyGrad* __restrict__ grads = nullptr) {
   static_assert(SURVEY || !BINS, "bins belong to a survey");
+  static_assert(BINS || !GRAD, "the gradient sums take the bins' table at run time");
   __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lz[kEnsTile + kEnsGroup];
   __shared__ __attribute__((aligned(16))) double lg[kEnsTile + kEnsGroup];
@@ -566,13 +729,22 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
       // (the same for every lane of the workgroup: an unsampled step skips the phase before its first barrier)
       if (step >= V.first && step < V.stop && (step - V.first) % V.every == 0) {
         double* bin = nullptr;
-        if constexpr (BINS) {
+        if constexpr (GRAD) {
+          // (read once per sampled step; the same for every lane of the workgroup)
+          const EnsembleSurveyBins& Q = bins[blockIdx.x];
+          const EnsembleSurveyGrad& G = grads[blockIdx.x];
+          const int b = Q.bin_of_step ? Q.bin_of_step[step] : -1;
+          double* gbin = nullptr;
+          if (b >= 0) { bin = Q.sums + (size_t)b * 5 * (size_t)V.K; gbin = G.bin_sums + (size_t)b * 5 * (size_t)V.K; }
+          ens_grad_survey_step(V, xc, zc, g, n + npan, V.shift ? V.shift[step] : 0.0, m.vc4, lx, lz, lg, pu, pw, bin, G.sums, gbin);
+        } else if constexpr (BINS) {
           // (read once per sampled step; the same for every lane of the workgroup)
           const EnsembleSurveyBins& Q = bins[blockIdx.x];
           const int b = Q.bin_of_step[step];
           if (b >= 0) bin = Q.sums + (size_t)b * 5 * (size_t)V.K;
         }
-        ens_survey_step<BINS>(V, xc, zc, g, n + npan, V.shift ? V.shift[step] : 0.0, m.vc4, lx, lz, lg, pu, pw, bin);
+        if constexpr (!GRAD)
+          ens_survey_step<BINS>(V, xc, zc, g, n + npan, V.shift ? V.shift[step] : 0.0, m.vc4, lx, lz, lg, pu, pw, bin);
       }
     }
 
@@ -649,6 +821,17 @@ ensemble_binned(const EnsembleMember* __restrict__ members, const long long* __r
                 const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec,
                 const EnsembleSurvey* __restrict__ surveys, const EnsembleSurveyBins* __restrict__ bins) {
   ens_member_run<PROBES, TRACERS, true, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, surveys, bins);
+}
+
+// ensemble_binned<PROBES, TRACERS> with the gradient sums of phase 2s: the launches of ludvm_ensemble_run_surveyed_graded (a null
+// table in a member's bin record: a gradient survey without bins)
+template <bool PROBES, bool TRACERS>
+__global__ void __launch_bounds__(kBlock)
+ensemble_graded(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap,
+                const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec,
+                const EnsembleSurvey* __restrict__ surveys, const EnsembleSurveyBins* __restrict__ bins,
+                const EnsembleSurveyGrad* __restrict__ grads) {
+  ens_member_run<PROBES, TRACERS, true, true, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, surveys, bins, grads);
 }
 
 }  // namespace ludvm

@@ -1012,10 +1012,14 @@ struct EnsembleSurveyArgs {
   const int* bin_of_step = nullptr; size_t bin_rows = 0;
   int nbins = 0;
   double* bin_sums = nullptr; size_t bin_doubles = 0;
+  // the gradient sums of ludvm_ensemble_run_surveyed_graded (grad_doubles = 0 and both arrays null: none)
+  double* grad_sums = nullptr; size_t grad_doubles = 0;
+  double* bin_grad_sums = nullptr; size_t bin_grad_doubles = 0;
 };
 
 // ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at), ludvm_ensemble_run_probed, with tracers
-// ludvm_ensemble_run_traced, with a survey ludvm_ensemble_run_surveyed and, with bins, ludvm_ensemble_run_surveyed_binned
+// ludvm_ensemble_run_traced, with a survey ludvm_ensemble_run_surveyed, with bins ludvm_ensemble_run_surveyed_binned and, with
+// gradient sums, ludvm_ensemble_run_surveyed_graded
 int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
@@ -1102,6 +1106,22 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     if (sv.bin_doubles != members * B * 5 * K)
       return fail(c, LUDVM_E_ARG, "ensemble: survey bin sums must hold members x bins x 5 x points doubles");
   }
+  const bool G = sv.grad_doubles || sv.grad_sums || sv.bin_grad_sums || sv.bin_grad_doubles;
+  if (G) {
+    if (!K) return fail(c, LUDVM_E_ARG, "ensemble: survey gradient sums need survey points");
+    if (!sv.grad_sums || (B && !sv.bin_grad_sums)) return fail(c, LUDVM_E_ARG, "null array");
+    if (!B && (sv.bin_grad_sums || sv.bin_grad_doubles))
+      return fail(c, LUDVM_E_ARG, "ensemble: survey bin gradient sums need survey bins");
+    // members x (bins + 1) x 10 x 8 x K bytes of plain, bin and gradient sums: at most 1 GiB
+    if (members > ((((size_t)1 << 30) / 80) / K) / (B + 1))
+      return fail(c, LUDVM_E_ARG, "ensemble: " + std::to_string(80.0 * (double)members * (double)(B + 1) * (double)K / (1 << 20)) +
+                                      " MiB of survey and gradient sums (10 x 8 x " + std::to_string(members) + " members x (" +
+                                      std::to_string(B) + " bins + 1) x " + std::to_string(K) + " points) are over 1 GiB; split the batch");
+    if (sv.grad_doubles != members * 5 * K)
+      return fail(c, LUDVM_E_ARG, "ensemble: survey gradient sums must hold members x 5 x points doubles");
+    if (sv.bin_grad_doubles != members * B * 5 * K)
+      return fail(c, LUDVM_E_ARG, "ensemble: survey bin gradient sums must hold members x bins x 5 x points doubles");
+  }
   if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
     return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
@@ -1159,8 +1179,11 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
                                    Arena::need(members, sizeof(EnsembleSurvey))
                              : 0;
   // (bins: the table and the members' bin records behind those; the bin sums behind the outputs)
-  const size_t in_bins = B ? Arena::need(sv.bin_rows, sizeof(int)) + Arena::need(members, sizeof(EnsembleSurveyBins)) : 0;
-  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey + in_bins));
+  // (gradient sums: the members' bin records -- a null table without bins -- and their gradient records; the sums behind the
+  // outputs)
+  const size_t in_bins = (B ? Arena::need(sv.bin_rows, sizeof(int)) : 0) + (B || G ? Arena::need(members, sizeof(EnsembleSurveyBins)) : 0);
+  const size_t in_grad = G ? Arena::need(members, sizeof(EnsembleSurveyGrad)) : 0;
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey + in_bins + in_grad));
   CHK(ensure(c, c->ens_work, work_doubles * 8));
   const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
   const size_t out_n = Arena::need(members * nrec, 8);
@@ -1169,7 +1192,8 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   const size_t out_tracer = M ? Arena::need(trec_doubles, 8) : 0;
   const size_t out_survey = K ? Arena::need(members * 5 * K, 8) : 0;
   const size_t out_bins = B ? Arena::need(members * B * 5 * K, 8) : 0;
-  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey + out_bins));
+  const size_t out_grad = G ? Arena::need(members * 5 * K, 8) + (B ? Arena::need(members * B * 5 * K, 8) : 0) : 0;
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey + out_bins + out_grad));
   Arena in(c->ens_in.p), out(c->ens_out.p);
   double* d_tab = in.take<double>(members * tab_doubles);
   double* d_kin = in.take<double>(kin_rows * krow);
@@ -1215,13 +1239,21 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   EnsembleSurveyBins* d_sb = nullptr;
   if (B) {
     d_btab = in.take<int>(sv.bin_rows);
-    d_sb = in.take<EnsembleSurveyBins>(members);
     d_bsums = out.take<double>(members * B * 5 * K);
+  }
+  if (B || G) d_sb = in.take<EnsembleSurveyBins>(members);
+  double *d_gsums = nullptr, *d_bgsums = nullptr;
+  EnsembleSurveyGrad* d_sg = nullptr;
+  if (G) {
+    d_sg = in.take<EnsembleSurveyGrad>(members);
+    d_gsums = out.take<double>(members * 5 * K);
+    if (B) d_bgsums = out.take<double>(members * B * 5 * K);
   }
 
   std::vector<EnsembleMember> hm(members);
   std::vector<EnsembleSurvey> hv(K ? members : 0);
-  std::vector<EnsembleSurveyBins> hb(B ? members : 0);
+  std::vector<EnsembleSurveyBins> hb(B || G ? members : 0);
+  std::vector<EnsembleSurveyGrad> hg(G ? members : 0);
   std::vector<EnsembleTracers> ht(M ? members : 0);
   std::vector<long long> tmin(ttiles, std::numeric_limits<long long>::max());     // earliest release step of each tile
   for (size_t k = 0; k < M; ++k) tmin[k / kBlock] = std::min(tmin[k / kBlock], tr.release[k]);
@@ -1266,6 +1298,13 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     if (B) {
       hb[mi].bin_of_step = d_btab + (size_t)d[1];
       hb[mi].sums = d_bsums + mi * B * 5 * K;
+    } else if (G) {
+      hb[mi].bin_of_step = nullptr;
+      hb[mi].sums = nullptr;
+    }
+    if (G) {
+      hg[mi].sums = d_gsums + mi * 5 * K;
+      hg[mi].bin_sums = B ? d_bgsums + mi * B * 5 * K : nullptr;
     }
     e.rows = d_rows + (size_t)d[4] * row_doubles;
     e.rec = d_wakes + (size_t)d[5];
@@ -1310,12 +1349,27 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   }
   if (B) {
     HIPCHK(c, hipMemcpyAsync(d_btab, sv.bin_of_step, sv.bin_rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sb, hb.data(), members * sizeof(EnsembleSurveyBins), hipMemcpyHostToDevice, c->stream));
     // (the kernel adds to the bin sums)
     HIPCHK(c, hipMemsetAsync(d_bsums, 0, members * B * 5 * K * 8, c->stream));
   }
+  if (B || G) HIPCHK(c, hipMemcpyAsync(d_sb, hb.data(), members * sizeof(EnsembleSurveyBins), hipMemcpyHostToDevice, c->stream));
+  if (G) {
+    HIPCHK(c, hipMemcpyAsync(d_sg, hg.data(), members * sizeof(EnsembleSurveyGrad), hipMemcpyHostToDevice, c->stream));
+    // (the kernel adds to the gradient sums)
+    HIPCHK(c, hipMemsetAsync(d_gsums, 0, members * 5 * K * 8, c->stream));
+    if (B) HIPCHK(c, hipMemsetAsync(d_bgsums, 0, members * B * 5 * K * 8, c->stream));
+  }
   // ONE launch: a workgroup per member, all of its time steps inside
-  if (B) {
+  if (G) {
+    const dim3 grid((unsigned)members), block(kBlock);
+    const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
+    const long long* ar = d_trec; const EnsembleSurvey* av = d_sv; const EnsembleSurveyBins* ab = d_sb;
+    const EnsembleSurveyGrad* ag = d_sg;
+    if (M && nprobe) hipLaunchKernelGGL((ensemble_graded<true, true>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab, ag);
+    else if (M) hipLaunchKernelGGL((ensemble_graded<false, true>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab, ag);
+    else if (nprobe) hipLaunchKernelGGL((ensemble_graded<true, false>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab, ag);
+    else hipLaunchKernelGGL((ensemble_graded<false, false>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, ab, ag);
+  } else if (B) {
     const dim3 grid((unsigned)members), block(kBlock);
     const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
     const long long* ar = d_trec; const EnsembleSurvey* av = d_sv; const EnsembleSurveyBins* ab = d_sb;
@@ -1354,7 +1408,9 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   if (M) HIPCHK(c, hipMemcpyAsync(tr.rows, d_trows, trec_doubles * 8, hipMemcpyDeviceToHost, c->stream));
   if (K) HIPCHK(c, hipMemcpyAsync(sv.sums, d_vsums, members * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
   if (B) HIPCHK(c, hipMemcpyAsync(sv.bin_sums, d_bsums, members * B * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv, hb and tmin live on this frame)
+  if (G) HIPCHK(c, hipMemcpyAsync(sv.grad_sums, d_gsums, members * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
+  if (G && B) HIPCHK(c, hipMemcpyAsync(sv.bin_grad_sums, d_bgsums, members * B * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv, hb, hg and tmin live on this frame)
   return LUDVM_OK;
 }
 
@@ -1449,6 +1505,38 @@ int ludvm_ensemble_run_surveyed_binned(ludvm_ctx* c, size_t members, int npan, i
   sv.sums = survey_sums; sv.doubles = survey_doubles;
   sv.bin_of_step = bin_of_step; sv.bin_rows = bin_rows; sv.nbins = nbins;
   sv.bin_sums = bin_sums; sv.bin_doubles = bin_doubles;
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
+                           shift_rows, probe_u, probe_w, tr, sv);
+}
+
+int ludvm_ensemble_run_surveyed_graded(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                                       const double* tables, const double* kin, size_t kin_rows, const double* init,
+                                       const double* free_xzg, size_t free_count, const long long* desc, const long long* snap_steps,
+                                       size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
+                                       long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
+                                       const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w, const double* seed_x,
+                                       const double* seed_z, const long long* release, size_t ntracer, const double* tshift_x,
+                                       size_t tshift_rows, const long long* trec_steps, size_t ntrec, double* tracer_rows,
+                                       size_t tracer_doubles, const double* survey_x, const double* survey_z, size_t nsurvey,
+                                       const double* sshift_x, size_t sshift_rows, long long first, long long stop, long long every,
+                                       double* survey_sums, size_t survey_doubles, const int* bin_of_step, size_t bin_rows, int nbins,
+                                       double* bin_sums, size_t bin_doubles, double* grad_sums, size_t grad_doubles,
+                                       double* bin_grad_sums, size_t bin_grad_doubles) {
+  EnsembleTracerArgs tr;
+  tr.seed_x = seed_x; tr.seed_z = seed_z; tr.release = release; tr.count = ntracer;
+  tr.shift_x = tshift_x; tr.shift_rows = tshift_rows;
+  tr.rec_steps = trec_steps; tr.nrec = ntrec;
+  tr.rows = tracer_rows; tr.doubles = tracer_doubles;
+  EnsembleSurveyArgs sv;
+  sv.x = survey_x; sv.z = survey_z; sv.count = nsurvey;
+  sv.shift_x = sshift_x; sv.shift_rows = sshift_rows;
+  sv.first = first; sv.stop = stop; sv.every = every;
+  sv.sums = survey_sums; sv.doubles = survey_doubles;
+  sv.bin_of_step = bin_of_step; sv.bin_rows = bin_rows; sv.nbins = nbins;
+  sv.bin_sums = bin_sums; sv.bin_doubles = bin_doubles;
+  sv.grad_sums = grad_sums; sv.grad_doubles = grad_doubles;
+  sv.bin_grad_sums = bin_grad_sums; sv.bin_grad_doubles = bin_grad_doubles;
   return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
                            snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
                            shift_rows, probe_u, probe_w, tr, sv);

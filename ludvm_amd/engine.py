@@ -748,9 +748,26 @@ class Engine:
                                        free_xzg, desc, snap_steps, survey_x, survey_z, survey_steps, survey_shift_x, seed_x, seed_z,
                                        release, shift_x, record_steps, probe_x, probe_z, probe_shift_x)
 
+    def ensemble_run_surveyed_graded(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=(), *, survey_x,
+                                     survey_z, survey_steps, bin_of_step=None, nbins=0, survey_shift_x=None, seed_x=(), seed_z=(),
+                                     release=(), shift_x=None, record_steps=(), probe_x=None, probe_z=None, probe_shift_x=None):
+        """`ensemble_run_surveyed_binned` (bins, tracers and probes optional) with the survey's gradient sums accumulated inside
+        the launch (ludvm_ensemble_run_surveyed_graded): in every sampled step the closed-form gradient of the survey's field at
+        the survey's shifted points adds ux, e, om, om^2 and Q = om^2 / 4 - ux^2 - e^2 to five more raw float64 sums per point,
+        and in a step with a bin to the bin's block.  nbins = 0 (bin_of_step is not looked at): no bins.
+        -> `ensemble_run_surveyed_binned`'s tuple (bin_sums None without bins) with grad_sums [members, 5, K] and bin_grad_sums
+        [members, nbins, 5, K] (None without bins) appended."""
+        nbins = int(nbins)
+        if nbins < 0:
+            raise ValueError("ensemble_run_surveyed_graded: nbins >= 0")
+        table = np.ascontiguousarray(bin_of_step, dtype=np.intc).reshape(-1) if nbins else np.empty(0, dtype=np.intc)
+        return self._ensemble_surveyed("ensemble_run_surveyed_graded", (table, nbins), npan, ncoef, scalars, tables, kin, init,
+                                       free_xzg, desc, snap_steps, survey_x, survey_z, survey_steps, survey_shift_x, seed_x, seed_z,
+                                       release, shift_x, record_steps, probe_x, probe_z, probe_shift_x, grad=True)
+
     def _ensemble_surveyed(self, who, bins, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, survey_x, survey_z,
                            survey_steps, survey_shift_x, seed_x, seed_z, release, shift_x, record_steps, probe_x, probe_z,
-                           probe_shift_x):
+                           probe_shift_x, grad=False):
         if not hasattr(self._lib, "ludvm_" + who):
             raise LudvmHipError(_ffi.E_STATE, f"this build of the library has no ludvm_{who}")
         vx, vz = _f64(survey_x), _f64(survey_z)
@@ -771,10 +788,10 @@ class Engine:
                 raise ValueError(f"{who}: probe_x and probe_z must have the same length")
             probes = (px, pz, None if probe_shift_x is None else _f64(probe_shift_x))
         return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, (sx, sz, rel, sh, rec),
-                              (vx, vz, vsh, first, stop, every), bins)
+                              (vx, vz, vsh, first, stop, every), bins, grad)
 
     def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None, survey=None,
-                  bins=None):
+                  bins=None, grad=False):
         npan, ncoef = int(npan), int(ncoef)
         desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
         members = desc.shape[0]
@@ -807,6 +824,17 @@ class Engine:
                          rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),
                          _pd(trows), trows.size, _pd(vx), _pd(vz), len(vx), _pd(vsh), 0 if vsh is None else len(vsh), first, stop,
                          every, _pd(sums), sums.size)
+                if grad:
+                    table, nbins = bins
+                    K = len(vx)
+                    bsums = np.zeros([members, nbins, 5, K]) if nbins else None
+                    gsums = np.zeros([members, 5, K])
+                    bgsums = np.zeros([members, nbins, 5, K]) if nbins else None
+                    self._check(self._lib.ludvm_ensemble_run_surveyed_graded(
+                        *sargs, table.ctypes.data_as(POINTER(c_int)) if nbins else None, len(table), nbins, _pd(bsums),
+                        0 if bsums is None else bsums.size, _pd(gsums), gsums.size, _pd(bgsums), 0 if bgsums is None else bgsums.size))
+                    out = (rows, wakes, wake_n, trows) if probes is None else (rows, wakes, wake_n, trows, pu, pw)
+                    return out + (sums, bsums, gsums, bgsums)
                 if bins is not None:
                     table, nbins = bins
                     bsums = np.zeros([members, nbins, 5, len(vx)])

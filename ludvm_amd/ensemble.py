@@ -1,7 +1,8 @@
 """`sweep`: many small LUDVM simulations in ONE device launch (Engine.ensemble_run / ludvm_ensemble_run; with velocity probes
 Engine.ensemble_run_probed / ludvm_ensemble_run_probed; with passive tracers Engine.ensemble_run_traced /
 ludvm_ensemble_run_traced; with a wake survey Engine.ensemble_run_surveyed / ludvm_ensemble_run_surveyed; with a phase-locked
-one Engine.ensemble_run_surveyed_binned / ludvm_ensemble_run_surveyed_binned).
+one Engine.ensemble_run_surveyed_binned / ludvm_ensemble_run_surveyed_binned; with the survey's gradient sums
+Engine.ensemble_run_surveyed_graded / ludvm_ensemble_run_surveyed_graded).
 
 A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
 'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
@@ -64,7 +65,7 @@ def _check_case(idx, kw, first):
     """Everything that can be refused from the keywords alone (no device, no engine call)."""
     who = f"sweep: member {idx}: "
     for key in ("engine", "device", "snapshot_steps", "verbose", "probes", "probe_frame", "particles", "particle_release",
-                "particle_frame", "particle_steps", "survey_phases"):
+                "particle_frame", "particle_steps", "survey_phases", "survey_grad"):
         if key in kw:
             raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
     if "survey_precision" in kw:
@@ -256,9 +257,29 @@ def _check_sweep_phases(survey_phases, surveyed, merged):
     return tables, B, phase
 
 
+def _check_sweep_grad(survey_grad, surveyed, binned, merged):
+    """The sweep's `survey_grad` -> bool; refused from the keywords alone."""
+    if isinstance(survey_grad, str) and survey_grad == "f32x2":
+        raise ValueError("sweep: survey_grad='f32x2': the gradient sums of a sweep are float64 -- survey_grad=True (hi+lo fp32 "
+                         "gradient sums: run a member on its own, LUDVM(..., survey=..., survey_gradient='f32x2'))")
+    if not isinstance(survey_grad, (bool, np.bool_)):
+        raise ValueError(f"sweep: survey_grad={survey_grad!r}: survey_grad must be True or False")
+    if not survey_grad:
+        return False
+    if surveyed is None:
+        raise ValueError("sweep: survey_grad needs `survey`")
+    K, B = surveyed[0].shape[1], 0 if binned is None else binned[1]
+    size = len(merged) * (B + 1) * 10 * 8 * K
+    if size > _ffi.ENSEMBLE_SURVEY_BYTES:
+        raise ValueError(f"sweep: survey_grad: {len(merged)} members x ({B} bins + 1) x {K} points are {size} bytes "
+                         f"({size / 2**30:.2f} GiB) of survey and gradient sums, over the {_ffi.ENSEMBLE_SURVEY_BYTES >> 30} GiB one "
+                         "launch returns: split the case list")
+    return True
+
+
 def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", particles=None, particle_release=None,
-          particle_frame="lab", particle_steps=None, survey=None, survey_frame="lab", survey_steps=None, survey_phases=None, verbose=False,
-          cls=LUDVM,
+          particle_frame="lab", particle_steps=None, survey=None, survey_frame="lab", survey_steps=None, survey_phases=None, survey_grad=False,
+          verbose=False, cls=LUDVM,
           **common):
     """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
     return the list of LUDVM objects, in order.  Each carries what a solo
@@ -306,6 +327,19 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     with `probes` and `particles`; everything else a member returns, the plain survey sums included, is bit-identical to the sweep
     without survey_phases, and bin b's sums are bit for bit the plain sums of a sweep that samples exactly bin b's steps.
 
+    survey_grad: False, or True for the gradient sums of the survey, the sweep-level form of LUDVM(..., survey_gradient=True)
+    (which stays a solo keyword and is refused here; the name matches flowfield(grad=)).  In every sampled step of a member the
+    closed-form gradient of the survey's field -- the same sources, its wake and bound vortices of that step -- at the survey's
+    shifted points adds ux = -A / pi, e = B / (2 pi), om = -v_core^4 C / pi, om^2 and Q = om^2 / 4 - ux^2 - e^2 to five more raw
+    float64 sums per point inside the one launch, and with survey_phases the same five terms to the step's bin block.  Every member
+    carries the attributes of a solo run with survey_gradient=True, formed by the solo code: `survey_gradient` (True),
+    `survey_grad_sums` [5, ...], `survey_mean_ux` / `_strain` / `_omega` / `_uz` / `_wx` / `_q`, `survey_omega2`, `survey_omega_var`,
+    `survey_production`, and with bins `survey_bin_grad_sums` [B, 5, ...], `survey_bin_mean_ux` / `_strain` / `_omega` / `_q`,
+    `survey_bin_omega2`, `survey_coherent_omega2`, `survey_random_omega2`.  Composes with `probes`, `particles`, `survey_frame`,
+    `survey_steps` and `survey_phases`; everything else a member returns, the velocity sums and their bins included, is
+    bit-identical to the sweep without survey_grad, and bin b's gradient block is bit for bit the gradient sums of a sweep that
+    samples exactly bin b's steps.  A sweep without it makes the engine calls it made before.
+
     Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
@@ -324,9 +358,11 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     a bool, B outside 1 .. 64, a sequence that does not hold one table per member, a table (member named) that is not an integer
     array [nt] or has entries below -1, a member none of whose sampled steps has a bin, `survey_bins` / `survey_period` /
     `survey_phase0` anywhere, an engine without ensemble_run_surveyed_binned, and plain and bin sums (40 bytes x members x (B + 1)
-    x K) over 1 GiB: split the case list.
+    x K) over 1 GiB: split the case list; `survey_grad` inside a member's dict, without `survey`, a value that is not a bool
+    ('f32x2': a sweep's sums are float64), an engine without ensemble_run_surveyed_graded, and plain, bin and gradient sums (80
+    bytes x members x (B + 1) x K) over 1 GiB: split the case list.
 
-    Out of scope: per-member probe, seed or survey point sets and windows, gradient or harmonic sums of a survey in a sweep, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe, seed or survey point sets and windows, harmonic sums of a survey in a sweep, hi+lo fp32 gradient sums in a sweep, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     if "survey_precision" in common:
         raise ValueError(f"sweep: survey_precision={common['survey_precision']!r}: the survey of a sweep is evaluated in float64 "
@@ -357,6 +393,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     traced = _check_sweep_particles(particles, particle_release, particle_frame, particle_steps, snapshot_steps, merged)
     surveyed = _check_sweep_survey(survey, survey_frame, survey_steps, merged)
     binned = _check_sweep_phases(survey_phases, surveyed, merged)
+    graded = _check_sweep_grad(survey_grad, surveyed, binned, merged)
     if engine is None:
         from .engine import Engine
         engine = Engine(device)
@@ -370,6 +407,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         raise ValueError("sweep: survey: this engine has no ensemble_run_surveyed")
     if binned is not None and not hasattr(engine, "ensemble_run_surveyed_binned"):
         raise ValueError("sweep: survey_phases: this engine has no ensemble_run_surveyed_binned")
+    if graded and not hasattr(engine, "ensemble_run_surveyed_graded"):
+        raise ValueError("sweep: survey_grad: this engine has no ensemble_run_surveyed_graded")
     snaps = sorted({int(s) for s in snapshot_steps})
     dev_snaps = [s for s in snaps if s >= 1]
     if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
@@ -434,7 +473,12 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
                      survey_shift_x=np.concatenate(shift) if survey_frame == "tunnel" else None)
         if probe_xz is not None:
             targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
-        if binned is not None:
+        gsums = bgsums = None
+        if graded:
+            if binned is not None:
+                targs.update(bin_of_step=np.concatenate(binned[0]), nbins=binned[1])
+            *out, ssums, bsums, gsums, bgsums = engine.ensemble_run_surveyed_graded(*packed, **targs)
+        elif binned is not None:
             # (one entry per kinematics row, like the offsets: member m's step i at [kin_off + i])
             *out, ssums, bsums = engine.ensemble_run_surveyed_binned(*packed, **targs, bin_of_step=np.concatenate(binned[0]),
                                                                      nbins=binned[1])
@@ -476,6 +520,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
             if binned is not None:              # (the samples of a bin: counted on the host from the member's table)
                 table = sim.survey_bin_of_step
                 sim._survey_bin_results(bsums[idx], np.bincount(table[table >= 0], minlength=sim.survey_nbins))
+            if graded:
+                sim.survey_gradient = True
+                sim._survey_gradient_results(gsums[idx], None if binned is None else bgsums[idx])
         cap = nf + 2 * (nt - 1)
         R = rows[r0:r0 + nt - 1]
         hist = _RecordedWakes()

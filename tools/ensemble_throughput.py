@@ -30,7 +30,14 @@ step sampled), and the probe phase on the K = 256 rake beside them.
 What the bins of a survey in a sweep cost: the surveyed device call of 256 copies of config 1 at K = 256 and K =
 4096 (every step sampled) on the parent build and on this one, alternated -- the same kernels -- and, on this build, the same
 call with every step in one of B phase bins of the stroke (ludvm_ensemble_run_surveyed_binned): the added time per sampled step,
-and beside it the call with ONE bin -- the same updates in the kernel, B times less to clear and to copy back."""
+and beside it the call with ONE bin -- the same updates in the kernel, B times less to clear and to copy back.
+
+    python tools/ensemble_throughput.py --survey-leg --grad [--bins 8] [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_survey_grad_cost.txt
+What the gradient sums of a survey in a sweep cost: the unsurveyed and the surveyed device call of 256 copies of
+config 1 at K = 256 and K = 4096 (every step sampled) on the parent build and on this one, alternated -- the same kernels --
+and, on this build, the same call with the gradient sums (ludvm_ensemble_run_surveyed_graded): per call, per sampled step, and
+the survey phase alone (the call less the unsurveyed call) against the plain survey phase.  With --bins B also the binned call
+and the graded call with every step in one of B phase bins."""
 import argparse
 import os
 import sys
@@ -50,6 +57,7 @@ ap.add_argument("--probes-leg", action="store_true", help="the cost of probes in
 ap.add_argument("--particles-leg", action="store_true", help="the cost of passive tracers in a sweep instead of the size ladder")
 ap.add_argument("--survey-leg", action="store_true", help="the cost of a wake survey in a sweep instead of the size ladder")
 ap.add_argument("--bins", type=int, default=0, help="survey leg: the cost of B phase bins over the plain survey instead (0: the plain leg)")
+ap.add_argument("--grad", action="store_true", help="survey leg: the cost of the gradient sums over the plain (and, with --bins, the binned) survey instead")
 ap.add_argument("--parent-lib", default="", help="probes / particles / survey leg: a build of the parent commit, timed beside this one")
 a = ap.parse_args()
 
@@ -456,9 +464,95 @@ def survey_bins_leg(nbins):
             print(f"plain surveyed device call at K = {K} against the parent build: NOT MEASURED (no --parent-lib given)")
 
 
+def survey_grad_leg(nbins):
+    """Device call only, like the survey leg: B = 256 copies of config 1 packed once; unsurveyed, surveyed (binned) and graded."""
+    B = 256
+    kept = {}
+    plain_call = inner
+
+    def keep(*args, **kw):
+        kept[len(args[7])] = args
+        return plain_call(*args, **kw)
+    eng.ensemble_run = keep
+    sims = sweep([dict(CONFIG1)] * B, engine=eng)
+    del eng.ensemble_run
+    engines = {"this build": eng}
+    if a.parent_lib:
+        engines["parent build"] = Engine(0, lib_path=os.path.abspath(a.parent_lib))
+    packed, s1 = kept[B], sims[0]
+    shift = np.concatenate([s.xpiv for s in sims])
+    steps_per_period = int(round(1.0 / s1.f / s1.dt))
+    table = np.tile((np.arange(s1.nt) % steps_per_period) * max(nbins, 1) // steps_per_period, B)
+
+    def variant(which, K, bins, grad):
+        e = engines[which]
+        if K == 0:
+            return lambda: e.ensemble_run(*packed)
+        vx, vz = np.full(K, 2.0), np.linspace(-2.0, 2.0, K)
+        kw = dict(survey_x=vx, survey_z=vz, survey_steps=(1, 1 << 62, 1), survey_shift_x=shift)
+        if bins:
+            kw.update(bin_of_step=table, nbins=bins)
+        if grad:
+            return lambda: e.ensemble_run_surveyed_graded(*packed, **kw)
+        if bins:
+            return lambda: e.ensemble_run_surveyed_binned(*packed, **kw)
+        return lambda: e.ensemble_run_surveyed(*packed, **kw)
+    builds = (["parent build"] if a.parent_lib else []) + ["this build"]
+    order = [(w, 0, 0, False) for w in builds]
+    for K in (256, 4096):
+        for bins in ([0, nbins] if nbins else [0]):
+            order += [(w, K, bins, False) for w in builds] + [("this build", K, bins, True)]
+    calls = {v: variant(*v) for v in order}
+    reps_in = {}
+    for v, f in calls.items():                        # warm-up of every shape (buffers grow here)
+        f()
+        t0 = time.perf_counter()
+        f()
+        reps_in[v] = max(1, int(a.window / (time.perf_counter() - t0)))
+    T = {v: [] for v in order}
+    for _ in range(a.reps):                           # the variants alternated
+        for v, f in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps_in[v]):
+                f()
+            T[v].append((time.perf_counter() - t0) / reps_in[v] * 1e3)
+    print("# survey gradient leg: device call (host clock around the synchronous entry point: uploads, ONE kernel, downloads) of 256\n"
+          "# copies of config 1 packed once, a survey of K points with every step sampled: without a survey (K 0), plain, and with the\n"
+          "# gradient sums (grad); ms per call, min / median / max over the windows and the build's own spread (max - min) / min")
+    none = np.median(T[("this build", 0, 0, False)])
+    for v in order:
+        which, K, bins, grad = v
+        t = np.array(T[v])
+        line = (f"{which:<13} B {B:4d}  K {K:5d}  bins {bins:2d}  {'grad ' if grad else 'plain'}  windows of {reps_in[v]:3d}  device call "
+                f"{t.min():9.3f} / {np.median(t):9.3f} / {t.max():9.3f}  spread {(t.max() - t.min()) / t.min() * 100:5.2f} %")
+        if grad:
+            base = np.array(T[(which, K, bins, False)])
+            added = np.median(t) - np.median(base)
+            line += (f"\n{'':13} over the {'binned' if bins else 'plain'} survey call of this build: {np.median(t) / np.median(base):.4f} x per call, "
+                     f"added {added:9.3f} ms = {added / (s1.nt - 1) * 1e3:8.3f} us per sampled step (of every member, side by side); the survey "
+                     f"phase alone (call less the unsurveyed call, {none:.3f} ms): {(np.median(t) - none) / (np.median(base) - none):.4f} x "
+                     f"(expected from the solo route's pair phase: 1.59-1.63); sums returned "
+                     f"{B * (bins + 1) * 10 * K * 8 / 2**20:.1f} MiB against {B * (bins + 1) * 5 * K * 8 / 2**20:.1f} MiB")
+        print(line, flush=True)
+    for v in order:
+        which, K, bins, grad = v
+        if which != "this build" or grad:
+            continue
+        name = "unsurveyed" if K == 0 else f"{'binned' if bins else 'plain'} surveyed (K = {K})"
+        if a.parent_lib:
+            p, n = np.array(T[("parent build", K, bins, False)]), np.array(T[v])
+            print(f"{name} device call, this build against the parent build: median {np.median(n) / np.median(p):.4f} x; the parent's own "
+                  f"windows span {p.min():.3f} .. {p.max():.3f} ms, this build's {n.min():.3f} .. {n.max():.3f} ms: "
+                  f"{'inside' if p.min() <= np.median(n) <= p.max() else 'OUTSIDE'} the parent's run-to-run spread")
+        else:
+            print(f"{name} device call against the parent build: NOT MEASURED (no --parent-lib given)")
+
+
 if a.survey_leg:
     eng.ensemble_run = inner
-    if a.bins:
+    if a.grad:
+        survey_grad_leg(a.bins)
+    elif a.bins:
         survey_bins_leg(a.bins)
     else:
         survey_leg()
