@@ -400,6 +400,43 @@ int ludvm_march_set_probes(ludvm_ctx* ctx, const double* x, const double* z, siz
                            size_t shift_rows);
 int ludvm_march_read_probes(ludvm_ctx* ctx, double* u, double* w, size_t rows);
 
+/* ---- wake integrals: class moments and kinetic energy of the vortex system (an addition to ABI 7: detect it by symbol) ----
+ *
+ * The SYSTEM of time step i >= 1 is what the probes see (above): the wake before the Euler update of step i, the vortices
+ * shed in step i at their placement, the bound vortices of step i at airfoil_gamma_points[i], in the lab frame.  Float64.
+ *
+ * Moments: classes FREE (0), TEV (1), LEV (2), BOUND (3), signs slot 0: Gamma >= 0, slot 1: Gamma < 0; for every class and
+ *   sign six sums over its vortices, in this order: the count (a double), sum G, sum G x, sum G z, sum G (x^2 + z^2),
+ *   sum G^2 -- 48 doubles per step, sums[row][class][sign][moment].  Every workgroup owns a fixed chunk of source indices,
+ *   combines its sums by a fixed tree, and the chunk partials are added in chunk order: a run repeats bit for bit however it
+ *   is cut into calls.
+ * Energy: W_i = 1/2 sum_a sum_b G_a G_b / (4 pi) ln((r_ab^2 + s_ab) / 2), s = sqrt(r^4 + v_core^4), over ALL sources of
+ *   step i, the bound vortices and a = b included -- 1/2 sum_a G_a psi(x_a) with the stream function's pair term
+ *   (ludvm_scalar_f64, LUDVM_FIELD_PSI).  The self part is ln(v_core^2 / 2) / (8 pi) times the row's sum of moment 6.
+ *   Evaluated at the sampled steps first <= i < stop, (i - first) % every == 0, under a launch plan that is a function of
+ *   the step's anchor-derived bound of the source count alone.
+ *
+ * ludvm_march_set_integrals: valid after ludvm_march_setup (LUDVM_E_STATE otherwise; LUDVM_E_STATE as well on a sharded or
+ *   multi-device context).  on = 0 turns the observer off (nothing else is looked at).  tags[ntags]: the class, 0 .. 2, of
+ *   every vortex of the resident wake in its stored order -- ntags must equal the wake the context holds (initial free
+ *   vortices, or the wake of a run that is continued); the library tags the vortices every later step sheds and keeps the
+ *   tags across the calls of one run.  energy_every = 0: no energy samples; otherwise energy_first >= 1,
+ *   energy_stop > energy_first, energy_every >= 1.  LUDVM_E_ARG for a tag outside 0 .. 2, a wrong ntags or a malformed window;
+ *   everything is validated before anything is changed: a refused call leaves the previous state -- and the rows of the
+ *   last run -- as they were.  A call that passes validation and then fails in the runtime leaves the observer off.
+ *   ludvm_march_setup forgets the observer; changing the resident wake other than through ludvm_march_run makes the next
+ *   ludvm_march_run fail with LUDVM_E_STATE until the observer is set again.
+ * ludvm_march_read_integrals: the rows of the LAST ludvm_march_run call, sums[rows][48] and energy[rows] (NaN for a step
+ *   outside the window); `rows` must equal that call's `count` (LUDVM_E_ARG otherwise); LUDVM_E_STATE when the observer is
+ *   off, or when no ludvm_march_run call has succeeded since it was set.
+ * Guarantee: with the observer on, every other result of ludvm_march_run -- `rows`, `state`, `hist`, the resident wake, the
+ *   probe rows, the tracer paths, the survey sums -- is bit-identical to a call without it (its kernels read the wake and
+ *   write only buffers of their own). */
+#define LUDVM_INTEGRAL_SUMS 48
+int ludvm_march_set_integrals(ludvm_ctx* ctx, int on, const unsigned char* tags, size_t ntags, long long energy_first,
+                              long long energy_stop, long long energy_every);
+int ludvm_march_read_integrals(ludvm_ctx* ctx, double* sums, double* energy, size_t rows);
+
 /* ---- passive tracers: particles advected inside the march (an addition to ABI 7: detect it by symbol) ----------
  *
  * A tracer is a probe that moves with what it measures.  Tracer m has a seed (xs, zs) and a release step r_m >= 1; with

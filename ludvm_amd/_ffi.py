@@ -101,6 +101,8 @@ SIGNATURES = {
     "ludvm_march_run": [c_void_p, c_longlong, c_longlong, c_int, _pd, _pd, _pd, c_size_t, POINTER(c_longlong)],
     "ludvm_march_set_probes": [c_void_p, _pd, _pd, c_size_t, _pd, c_size_t],
     "ludvm_march_read_probes": [c_void_p, _pd, _pd, c_size_t],
+    "ludvm_march_set_integrals": [c_void_p, c_int, POINTER(ctypes.c_ubyte), c_size_t, c_longlong, c_longlong, c_longlong],
+    "ludvm_march_read_integrals": [c_void_p, _pd, _pd, c_size_t],
     "ludvm_march_set_tracers": [c_void_p, _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, _pd, POINTER(c_longlong),
                                 c_size_t],
     "ludvm_march_read_tracers": [c_void_p, _pd, _pd, c_size_t, POINTER(c_longlong), POINTER(c_size_t)],
@@ -185,7 +187,7 @@ ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm
                   "ludvm_march_read_survey_gradient", "ludvm_scalar_f32x2", "ludvm_flowfield_scalar_rows_f32x2",
                   "ludvm_gradient_f32x2", "ludvm_flowfield_gradient_rows_f32x2", "ludvm_march_set_tracer_gradient_f32x2",
                   "ludvm_ensemble_run_surveyed_binned", "ludvm_march_set_survey_gradient_f32x2",
-                  "ludvm_ensemble_run_surveyed_graded")
+                  "ludvm_ensemble_run_surveyed_graded", "ludvm_march_set_integrals", "ludvm_march_read_integrals")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

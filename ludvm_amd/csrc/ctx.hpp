@@ -151,6 +151,17 @@ struct ludvm_ctx {
   // with survey_gradient: the five columns come from one walk in hi+lo fp32 under kObsSurveyF32's plan
   // (ludvm_march_set_survey_gradient_f32x2); survey_precision stays 0
   bool survey_gradient_f32x2 = false;
+  // wake integrals of the march (ludvm_march_set_integrals): one class byte per wake vortex (sized for the run's cap when
+  // the observer is set; the kernels add the tags of the vortices a step sheds), the chunk partials of one step
+  // [chunks][48], the rows of the last ludvm_march_run call [rows][48]; the energy's slab [split][pad], its tile sums and
+  // the call's samples [rows] -- buffers of the observer's own, like the probes'
+  Buf integral_tags, integral_part, integral_out, energy_part, energy_tiles, energy_out;
+  bool integrals_on = false;
+  size_t integral_tagged = 0;                  // wake vortices that have a tag (= wake_n between the calls of a run)
+  size_t integral_cap = 0;                     // wake vortices the tags and the energy's slab are sized for
+  size_t integral_rows = 0;                    // steps of the last ludvm_march_run call that left rows (0: none to read)
+  long long integral_first_step = 0;           // ... and its first step
+  long long energy_first = 1, energy_stop = 0, energy_every = 0;   // sampled steps (every = 0: none)
 
   // ensemble of small simulations (ludvm_ensemble_run): inputs, the members' wake slabs, outputs -- buffers of its own, so
   // that a sweep leaves the resident wake and the march's state alone

@@ -31,6 +31,8 @@ int ludvm_march_setup(ludvm_ctx* c, int npan, int ncoef, const double* scalars, 
   c->survey_precision = 0;
   c->survey_nbins = 0;      // ... and its bins (ludvm_march_set_survey_bins)
   c->survey_gradient = c->survey_gradient_f32x2 = false;
+  c->integrals_on = false;  // ... and its wake integrals (ludvm_march_set_integrals)
+  c->integral_rows = 0;
   if (!scalars || !tables || !kin) return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
     return fail(c, LUDVM_E_ARG, "march: 1 <= Npanels <= 256 and 4 <= Ncoeffs <= 64");
@@ -272,6 +274,48 @@ int march_survey_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long 
   else
     hipLaunchKernelGGL(march_survey_finish, dim3(blocks_for((long long)K)), dim3(kBlock), 0, st, (const double*)slab, p.pad, p.nsplit,
                        (long long)K, static_cast<double*>(c->survey_sums.p));
+  HIPCHK(c, hipGetLastError());
+  return LUDVM_OK;
+}
+
+// is time step s one of the energy's sampled steps?
+bool energy_samples_step(const ludvm_ctx* c, long long s) {
+  return c->integrals_on && c->energy_every > 0 && s >= c->energy_first && s < c->energy_stop &&
+         (s - c->energy_first) % c->energy_every == 0;
+}
+
+// The wake integrals of time step s, row `rel` of the call: enqueued where the probes are, behind march_solve of step s on
+// the stream that ran it, so before the roll-up's finisher moves anything.  The moments run at EVERY step (they also tag the
+// vortices the step shed); the energy at its sampled steps, under the plan of the step's bound alone.  The tags, the partials,
+// the slab and the rows are the observer's own buffers, touched only by these kernels in stream order.  Reads the wake,
+// writes nothing of it: rows, state, hist, the resident wake and every other observer's results keep their bits.
+int march_integral_launch(ludvm_ctx* c, hipStream_t st, long long n_ub, long long s, long long rel) {
+  const MarchSetup& m = c->msetup;
+  const long long ns_ub = n_ub + (long long)m.npan;
+  if (n_ub > (long long)c->integral_cap) return fail(c, LUDVM_E_STATE, "march: the wake outgrew what ludvm_march_set_integrals sized");
+  const MarchState* S = static_cast<const MarchState*>(c->march_state.p);
+  double* part = static_cast<double*>(c->integral_part.p);
+  const unsigned chunks = (unsigned)((ns_ub + kIntegralChunk - 1) / kIntegralChunk);
+  hipLaunchKernelGGL(march_integral_partial, dim3(chunks), dim3(kBlock), 0, st, (const double*)c->x64, (const double*)c->z64,
+                     (const double*)c->g64, S, m.npan, static_cast<unsigned char*>(c->integral_tags.p), part);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(march_integral_finish, dim3(1), dim3(64), 0, st, (const double*)part, S, m.npan,
+                     static_cast<double*>(c->integral_out.p) + (size_t)rel * kIntegralSums);
+  HIPCHK(c, hipGetLastError());
+  if (!energy_samples_step(c, s)) return LUDVM_OK;
+  const ObserverPlan p = energy_plan(ns_ub);
+  if ((size_t)p.nsplit * (size_t)p.pad * 8 > c->energy_part.cap || (size_t)p.tiles * 8 > c->energy_tiles.cap)
+    return fail(c, LUDVM_E_STATE, "march: the energy's slab is smaller than this step's plan");
+  double* slab = static_cast<double*>(c->energy_part.p);
+  double* tiles = static_cast<double*>(c->energy_tiles.p);
+  hipLaunchKernelGGL(march_energy_partial, dim3((unsigned)p.tiles, (unsigned)p.nsplit), dim3(kBlock), 0, st, (const double*)c->x64,
+                     (const double*)c->z64, (const double*)c->g64, S, m.npan, p.chunk, p.pad, m.vc4, slab);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(march_energy_tiles, dim3((unsigned)p.tiles), dim3(kBlock), 0, st, (const double*)slab, p.pad, p.nsplit,
+                     (const double*)c->g64, S, m.npan, tiles);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(march_energy_finish, dim3(1), dim3(64), 0, st, (const double*)tiles, S, m.npan,
+                     static_cast<double*>(c->energy_out.p) + (size_t)rel);
   HIPCHK(c, hipGetLastError());
   return LUDVM_OK;
 }
@@ -684,11 +728,70 @@ int ludvm_march_read_probes(ludvm_ctx* c, double* u, double* w, size_t rows) {
   return LUDVM_OK;
 }
 
+int ludvm_march_set_integrals(ludvm_ctx* c, int on, const unsigned char* tags, size_t ntags, long long energy_first,
+                              long long energy_stop, long long energy_every) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
+  if (!on) {
+    c->integrals_on = false;
+    c->integral_rows = 0;
+    return LUDVM_OK;
+  }
+  if (c->shard_world > 1 || c->comm_world > 1)
+    return fail(c, LUDVM_E_STATE, "march: the wake integrals run on one GPU: not on a sharded or multi-device context");
+  // everything is validated before anything is changed
+  if (ntags != c->wake_n) return fail(c, LUDVM_E_ARG, "march: one tag per vortex of the resident wake (" + std::to_string(c->wake_n) + ")");
+  if (ntags && !tags) return fail(c, LUDVM_E_ARG, "null array");
+  for (size_t k = 0; k < ntags; ++k)
+    if (tags[k] > kClassLev) return fail(c, LUDVM_E_ARG, "march: a tag is 0 (FREE), 1 (TEV) or 2 (LEV)");
+  if (energy_every < 0 || (energy_every > 0 && (energy_first < 1 || energy_stop <= energy_first)))
+    return fail(c, LUDVM_E_ARG, "march: the energy window needs first >= 1, stop > first and every >= 1 (every = 0: no samples)");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->integrals_on = false;
+  c->integral_rows = 0;
+  // the run's cap: at most two vortices per remaining kinematics row on top of the wake as it stands
+  const size_t cap = c->wake_n + 2 * c->march_kin_rows;
+  const size_t ns_cap = cap + (size_t)c->msetup.npan;
+  CHK(ensure(c, c->integral_tags, cap + 64));
+  CHK(ensure(c, c->integral_part, (ns_cap + kIntegralChunk - 1) / kIntegralChunk * kIntegralSums * 8));
+  if (energy_every > 0) {
+    CHK(ensure(c, c->energy_part, energy_slab_bytes((long long)ns_cap)));
+    CHK(ensure(c, c->energy_tiles, (size_t)observer_tiles(kEnergyRule, (long long)ns_cap) * 8));
+  }
+  if (ntags) {
+    HIPCHK(c, hipMemcpyAsync(c->integral_tags.p, tags, ntags, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->integral_tagged = ntags;
+  c->integral_cap = cap;
+  c->energy_first = energy_first; c->energy_stop = energy_stop; c->energy_every = energy_every;
+  c->integrals_on = true;
+  return LUDVM_OK;
+}
+
+int ludvm_march_read_integrals(ludvm_ctx* c, double* sums, double* energy, size_t rows) {
+  if (!c) return LUDVM_E_ARG;
+  if (!c->march_ready || !c->integrals_on) return fail(c, LUDVM_E_STATE, "march: the wake integrals are not set");
+  if (c->integral_rows == 0) return fail(c, LUDVM_E_STATE, "march: no ludvm_march_run call has left integral rows");
+  if (!sums || !energy) return fail(c, LUDVM_E_ARG, "null array");
+  if (rows != c->integral_rows) return fail(c, LUDVM_E_ARG, "march: rows must equal the count of the last ludvm_march_run call");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(sums, c->integral_out.p, rows * kIntegralSums * 8, hipMemcpyDeviceToHost, c->stream));
+  bool sampled = false;
+  for (size_t r = 0; r < rows; ++r) sampled = sampled || energy_samples_step(c, c->integral_first_step + (long long)r);
+  if (sampled) HIPCHK(c, hipMemcpyAsync(energy, c->energy_out.p, rows * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t r = 0; r < rows; ++r)
+    if (!energy_samples_step(c, c->integral_first_step + (long long)r)) energy[r] = std::numeric_limits<double>::quiet_NaN();
+  return LUDVM_OK;
+}
+
 int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int precision, double* state, double* rows,
                     double* hist, size_t hist_nmax, const long long* anchors) {
   if (!c) return LUDVM_E_ARG;
   if (!c->march_ready) return fail(c, LUDVM_E_STATE, "ludvm_march_setup has not been called");
   c->probe_rows = 0;
+  c->integral_rows = 0;
   c->tracer_ran = false;
   c->tracer_grad_ran = false;
   c->tracer_rows.clear();
@@ -719,6 +822,16 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   if (hist) CHK(ensure(c, c->march_hist, (size_t)count * 2 * hist_nmax * 8));
   const bool probes = c->probe_count != 0;
   if (probes) CHK(ensure(c, c->probe_out, (size_t)count * 2 * c->probe_count * 8));      // (the slab: ludvm_march_set_probes)
+  const bool integrals = c->integrals_on;
+  if (integrals) {
+    // (the tags, the partials and the energy's slab: ludvm_march_set_integrals, for the run's cap)
+    if (c->integral_tagged != (size_t)n0)
+      return fail(c, LUDVM_E_STATE, "march: the resident wake changed since ludvm_march_set_integrals tagged it");
+    if ((size_t)(n0 + 2 * count) > c->integral_cap)
+      return fail(c, LUDVM_E_STATE, "march: the wake can outgrow what ludvm_march_set_integrals sized");
+    CHK(ensure(c, c->integral_out, (size_t)count * kIntegralSums * 8));
+    if (c->energy_every > 0) CHK(ensure(c, c->energy_out, (size_t)count * 8));
+  }
   const bool tracers = c->tracer_count != 0;
   std::vector<long long> trec;      // the call's recorded tracer steps, ascending: row k of the record is step trec[k]
   if (tracers) {
@@ -872,6 +985,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
         ++surveyed;
         count_bin(s);
       }
+      if (integrals) CHK(march_integral_launch(c, c->stream, n_ub, s, rel));
       MarchSym ms;
       ms.scale = &S->sc[(s + 1) & 1]; ms.bad = &S->sym_bad; ms.n_lo = n_lo + 1; ms.march = overlap_ok;
       CHK(advect_launch(c, (size_t)n_ub, &S->n, m.dt, nfoil, c->march_vcore, precision, nullptr, nullptr, td, ms));
@@ -912,6 +1026,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
         ++surveyed;
         count_bin(s);
       }
+      if (rc == LUDVM_OK && integrals) rc = march_integral_launch(c, c->stream_b, n_ub, s, rel);
       c->stream = main_stream;
       CHK(rc);
       HIPCHK(c, hipEventRecord(c->ev_join, c->stream_b));
@@ -970,6 +1085,7 @@ int ludvm_march_run(ludvm_ctx* c, long long first_step, long long count, int pre
   for (int k = 0; k < m.ncoef; ++k) state[16 + k] = hs.prevA[k];
   if (c->timing) CHK(drain_timing(c));
   if (probes) c->probe_rows = (size_t)count;
+  if (integrals) { c->integral_rows = (size_t)count; c->integral_first_step = first_step; c->integral_tagged = (size_t)hs.n; }
   if (tracers) { c->tracer_rows = trec; c->tracer_ran = true; c->tracer_grad_ran = c->tracer_gradient; }
   c->survey_samples += surveyed;
   for (size_t b = 0; b < binned.size(); ++b) c->survey_bin_samples[b] += binned[b];

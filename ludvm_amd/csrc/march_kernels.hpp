@@ -29,6 +29,7 @@
 #include "pair_kernels.hpp"
 #include "pair_sym_kernels.hpp"
 #include "march_types.hpp"
+#include "scalar_term.hpp"
 
 namespace ludvm {
 
@@ -1486,6 +1487,187 @@ march_f32x2_grad_survey_partial(const double* __restrict__ px, const double* __r
       row[4 * k_pad + m] = gc[k];
     }
   }
+}
+
+// ---- wake integrals: class moments and kinetic energy of the vortex system (ludvm_march_set_integrals) ------------------------------
+// The SYSTEM of time step i is what the probes see: the sources [0, S->n + nfoil) right behind march_solve of step i -- the wake
+// before the Euler update of step i, the vortices shed in step i at their placement, the bound vortices of step i -- in the lab
+// frame.  Everything is float64.
+//
+// Moments.  Classes FREE, TEV, LEV, BOUND (0 .. 3), signs slot 0: G >= 0, slot 1: G < 0; for every (class, sign) six sums over
+// its vortices: the count, G, G x, G z, G (x^2 + z^2), G^2 -- kIntegralSums = 48 doubles per step.  The wake is stored in shedding
+// order, so the class of a wake index is kept in one byte per vortex (`tags`): the host gives the tags of the wake that exists
+// when the observer is set; the S->tail vortices appended by the step just solved are the TEV and -- S->shed -- the LEV, and the
+// kernel stores their tags for the later steps (hence it runs at EVERY step of a run that has the observer on); the nfoil
+// entries behind S->n are BOUND.
+// march_integral_partial  one workgroup per chunk of kIntegralChunk source indices (a compile-time constant: which lane adds
+//                         which vortex, and in what order, depends on the index alone): lane t takes begin + t + 256 k,
+//                         k = 0 .. 7, in that order; the workgroup's 48 sums by block_sum_n's fixed tree; -> part[chunk][48].
+//                         The source count is read on the device: a workgroup past the end leaves at once
+// march_integral_finish   one lane per sum: the chunk partials in chunk order -> the step's row of the call's buffer
+// A run of config 2's size (67 000 vortices: 1.6 MB of x, z, G) is 33 workgroups, not one.
+constexpr int kIntegralClasses = 4;
+constexpr int kIntegralMoments = 6;
+constexpr int kIntegralSums = kIntegralClasses * 2 * kIntegralMoments;
+constexpr int kIntegralPerLane = 8;
+constexpr int kIntegralChunk = kBlock * kIntegralPerLane;
+enum IntegralClass { kClassFree = 0, kClassTev = 1, kClassLev = 2, kClassBound = 3 };
+
+__global__ void __launch_bounds__(kBlock)
+march_integral_partial(const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
+                       const MarchState* S, int nfoil, unsigned char* tags, double* part) {
+  __shared__ double scratch[4 * kIntegralMoments];
+  __builtin_amdgcn_s_setprio(3);
+  const long long n = S->n, ns = n + nfoil, n_old = n - S->tail;
+  const long long begin = (long long)blockIdx.x * kIntegralChunk;
+  if (begin >= ns) return;                           // (uniform: before any barrier)
+  double x[kIntegralPerLane], z[kIntegralPerLane], g[kIntegralPerLane];
+  int key[kIntegralPerLane];                         // 2 class + sign; -1: no vortex
+#pragma unroll
+  for (int k = 0; k < kIntegralPerLane; ++k) {
+    const long long i = begin + threadIdx.x + (long long)k * kBlock;
+    const bool on = i < ns;
+    x[k] = on ? xs[i] : 0.0;
+    z[k] = on ? zs[i] : 0.0;
+    g[k] = on ? gs[i] : 0.0;
+    int cls = kClassBound;
+    if (i < n_old) {
+      cls = tags[i];
+    } else if (i < n) {
+      cls = i == n_old ? kClassTev : kClassLev;      // the step's own: the TEV first, then -- if shed -- the LEV
+      tags[i] = (unsigned char)cls;
+    }
+    key[k] = on ? 2 * cls + (g[k] < 0.0 ? 1 : 0) : -1;
+  }
+  double* out = part + (long long)blockIdx.x * kIntegralSums;
+#pragma unroll
+  for (int q = 0; q < 2 * kIntegralClasses; ++q) {
+    double v[kIntegralMoments] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < kIntegralPerLane; ++k) {
+      const bool m = key[k] == q;
+      const double gk = m ? g[k] : 0.0;
+      v[0] += m ? 1.0 : 0.0;
+      v[1] += gk;
+      v[2] += gk * x[k];
+      v[3] += gk * z[k];
+      v[4] += gk * __builtin_fma(z[k], z[k], x[k] * x[k]);
+      v[5] += gk * gk;
+    }
+    block_sum_n<kIntegralMoments>(v, scratch);
+    if (threadIdx.x < kIntegralMoments) {
+      double r = v[0];
+#pragma unroll
+      for (int k = 1; k < kIntegralMoments; ++k) r = (int)threadIdx.x == k ? v[k] : r;
+      out[q * kIntegralMoments + threadIdx.x] = r;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64)
+march_integral_finish(const double* part, const MarchState* S, int nfoil, double* row) {
+  __builtin_amdgcn_s_setprio(3);
+  const long long ns = S->n + nfoil;
+  const long long chunks = (ns + kIntegralChunk - 1) / kIntegralChunk;
+  const int t = threadIdx.x;
+  if (t >= kIntegralSums) return;
+  double acc = 0.0;
+  for (long long c = 0; c < chunks; ++c) acc += part[c * kIntegralSums + t];
+  row[t] = acc;
+}
+
+// Energy.  W_i = 1/2 sum_a sum_b G_a G_b / (4 pi) ln((r_ab^2 + s_ab) / 2), s = sqrt(r^4 + vc^4), over ALL sources of step i,
+// the bound vortices and a = b included: 1/2 sum_a G_a psi(x_a) with psi exactly LUDVM.stream_function's pair term
+// (scalar_term<kScalarPsi>, scalar_term.hpp).  The self part, ln(vc^2 / 2) / (8 pi) sum G^2, follows from moment 6 on the host.
+// march_energy_partial  the points are the step's own sources: point tiles of kEnergyTile (256 lanes x 2 points: point
+//                       t0 + 256 k + lane in register set k) x source splits; kFieldTile-source tiles in LDS, walked in
+//                       source order and bounded by the tile's count (a padded slot would give 0 ln(inf): pair_scalar_f64's
+//                       rule); both counts are read on the device; psi partials to a slab [split][pad] of the observer's own
+// march_energy_tiles    one workgroup per point tile: every lane adds its points' splits in split order, multiplies by G_a / 2,
+//                       adds its two points; the workgroup's block_sum tree -> tile_sums[tile]
+// march_energy_finish   one lane: the tiles in tile order -> the step's entry of the call's buffer
+// Points and sources both grow with the run: tiles, chunk and nsplit are functions of the step's anchor-derived bound ns_ub
+// alone (observer_plan(kEnergyRule, ns_ub, ns_ub), plan_rule.hpp), so a run's bits do not depend on how it is cut into calls.
+constexpr int kEnergyPerLane = 2;
+constexpr int kEnergyTile = kBlock * kEnergyPerLane;
+
+__global__ void __launch_bounds__(kBlock)
+march_energy_partial(const double* __restrict__ xs, const double* __restrict__ zs, const double* __restrict__ gs,
+                     const MarchState* S, int nfoil, long long chunk, long long pad, double vc4, double* slab) {
+  __shared__ __attribute__((aligned(16))) double lx[kFieldTile];
+  __shared__ __attribute__((aligned(16))) double lz[kFieldTile];
+  __shared__ __attribute__((aligned(16))) double lg[kFieldTile];
+  static_assert(kFieldTile == kBlock, "one source slot per lane");
+  __builtin_amdgcn_s_setprio(3);
+  const long long ns = S->n + nfoil;
+  if ((long long)blockIdx.x * kEnergyTile >= ns) return;       // (uniform: before any barrier)
+  const SplitRange src = split_range(S, nfoil, chunk);
+  const int tid = threadIdx.x;
+  double xp[kEnergyPerLane], zp[kEnergyPerLane], acc[kEnergyPerLane];
+#pragma unroll
+  for (int k = 0; k < kEnergyPerLane; ++k) {
+    const long long m = observer_point<kEnergyPerLane, kBlock>(k);
+    const bool on = m < ns;
+    xp[k] = on ? xs[m] : 0.0;                        // (a lane without a point walks along at the origin: every a > 0)
+    zp[k] = on ? zs[m] : 0.0;
+    acc[k] = 0.0;
+  }
+  for (long long base = src.begin; base < src.end; base += kFieldTile) {
+    const int cnt = src.end - base < kFieldTile ? (int)(src.end - base) : kFieldTile;      // sources of this tile (uniform)
+    __syncthreads();
+    if (tid < cnt) {
+      lx[tid] = xs[base + tid];
+      lz[tid] = zs[base + tid];
+      lg[tid] = gs[base + tid];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < cnt; ++j) {
+      const double sx = lx[j], sz = lz[j], sg = lg[j];
+#pragma unroll
+      for (int k = 0; k < kEnergyPerLane; ++k)
+        acc[k] = __builtin_fma(sg, scalar_term<kScalarPsi>(xp[k] - sx, zp[k] - sz, vc4), acc[k]);
+    }
+  }
+  double* row = slab + (long long)blockIdx.y * pad;
+#pragma unroll
+  for (int k = 0; k < kEnergyPerLane; ++k) {
+    const long long m = observer_point<kEnergyPerLane, kBlock>(k);
+    if (m < ns) row[m] = acc[k] * kInv4PiD;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+march_energy_tiles(const double* slab, long long pad, int nsplit, const double* __restrict__ gs, const MarchState* S, int nfoil,
+                   double* tile_sums) {
+  __shared__ double scratch[kBlock / 64];
+  __builtin_amdgcn_s_setprio(3);
+  const long long ns = S->n + nfoil;
+  if ((long long)blockIdx.x * kEnergyTile >= ns) return;       // (uniform: before any barrier)
+  double v = 0.0;
+#pragma unroll
+  for (int k = 0; k < kEnergyPerLane; ++k) {
+    const long long m = observer_point<kEnergyPerLane, kBlock>(k);
+    double term = 0.0;
+    if (m < ns) {
+      double psi = 0.0;
+      for (int sidx = 0; sidx < nsplit; ++sidx) psi += slab[(long long)sidx * pad + m];
+      term = 0.5 * gs[m] * psi;
+    }
+    v += term;
+  }
+  v = block_sum(v, scratch);
+  if (threadIdx.x == 0) tile_sums[blockIdx.x] = v;
+}
+
+__global__ void __launch_bounds__(64)
+march_energy_finish(const double* tile_sums, const MarchState* S, int nfoil, double* out) {
+  if (threadIdx.x != 0) return;
+  const long long ns = S->n + nfoil;
+  const long long tiles = (ns + kEnergyTile - 1) / kEnergyTile;
+  double acc = 0.0;
+  for (long long t = 0; t < tiles; ++t) acc += tile_sums[t];
+  *out = acc;
 }
 
 }  // namespace ludvm

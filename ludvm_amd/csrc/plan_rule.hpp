@@ -244,6 +244,20 @@ inline size_t observer_slab_bytes(const ObserverRule& r, long long count) {
   return (size_t)observer_want(r, count) * 2 * (size_t)(observer_tiles(r, count) * r.point_tile) * 8;
 }
 
+// ---- launch rule of the wake energy (march_kernels.hpp: march_energy_partial; ludvm_march_set_integrals) ---------------------
+// The points are the step's own sources, so points and sources both grow with the run: the plan of a step is
+// observer_plan(kEnergyRule, ns_ub, ns_ub), a function of the step's anchor-derived bound alone.  512 points per workgroup (256
+// lanes x 2), 256-source tiles, about four workgroups per CU, at most 64 splits (the finisher adds them one after the other).
+// A constant of its own: kObserverRules is the table of the observers whose points the user supplies.
+constexpr ObserverRule kEnergyRule = {512, 256, 1024, 64};
+inline ObserverPlan energy_plan(long long ns_ub) { return observer_plan(kEnergyRule, plan_max(ns_ub, 1), ns_ub); }
+// the slab [split][pad] of any step of a run whose sources never exceed ns_cap: nsplit <= observer_want, so
+// nsplit x tiles <= max(groups, tiles)
+inline size_t energy_slab_bytes(long long ns_cap) {
+  const long long tiles = observer_tiles(kEnergyRule, plan_max(ns_cap, 1));
+  return (size_t)plan_max(kEnergyRule.groups, tiles) * (size_t)kEnergyRule.point_tile * 8;
+}
+
 // ---- launch rule of the hi+lo fp32 field sums (field_kernels.hpp: field_hilo_f32, analytic vorticity and velocity gradient) -----
 // Targets in workgroups of kFieldHiloTargets (256 lanes x kFieldHiloPerLane points), sources in tiles of kFieldHiloTile; the
 // sources in `nsplit` splits of `chunk` sources, a multiple of the tile, so that target workgroups x splits comes to about

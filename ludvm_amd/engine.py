@@ -419,6 +419,30 @@ class Engine:
         self._check(self._lib.ludvm_march_read_probes(self._ctx, _pd(u), _pd(w), int(count)))
         return u, w
 
+    INTEGRAL_SUMS = 48
+
+    def march_set_integrals(self, on, tags=(), energy_steps=None):
+        """Wake integrals of every marched step (ludvm_march_set_integrals); valid after `march_setup`, which forgets them.
+        tags: the class -- 0 FREE, 1 TEV, 2 LEV -- of every vortex of the resident wake, in its stored order (the library tags
+        what later steps shed).  energy_steps: None (no energy samples) or (first, stop, every).  on = False turns the
+        observer off."""
+        if not hasattr(self._lib, "ludvm_march_set_integrals"):
+            raise LudvmHipError(_ffi.E_STATE, "this build of the library has no ludvm_march_set_integrals")
+        raw = np.asarray(tags).reshape(-1)
+        if len(raw) and (not np.issubdtype(raw.dtype, np.integer) or raw.min() < 0 or raw.max() > 255):
+            raise ValueError("march_set_integrals: tags must be integers 0 .. 2")
+        t = np.ascontiguousarray(raw, dtype=np.uint8)
+        first, stop, every = (0, 0, 0) if energy_steps is None else (int(v) for v in energy_steps)
+        self._check(self._lib.ludvm_march_set_integrals(self._ctx, 1 if on else 0, t.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+                                                        len(t), first, stop, every))
+
+    def march_integrals(self, count):
+        """(sums float64 [count, 4, 2, 6], energy float64 [count], NaN outside the window): the integral rows of the last
+        `march_run` call, which ran `count` steps (ludvm_march_read_integrals)."""
+        sums, energy = np.empty([int(count), 4, 2, 6]), np.empty(int(count))
+        self._check(self._lib.ludvm_march_read_integrals(self._ctx, _pd(sums), _pd(energy), int(count)))
+        return sums, energy
+
     def march_set_tracers(self, seed_x, seed_z, release=None, shift_x=None, cur=None, record_steps=()):
         """Passive tracers advected by every marched step (ludvm_march_set_tracers); valid after `march_setup`, which forgets
         them.  release: None (all released at step 1), or one step >= 1 per tracer -- before it a tracer is held at its

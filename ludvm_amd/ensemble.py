@@ -27,6 +27,9 @@ __all__ = ["sweep"]
 _BINS_SOLO = ("the bins of a sweep are common to it: sweep(cases, survey=..., survey_phases=...) -- survey_bins / survey_period / "
               "survey_phase0 belong to a solo run, LUDVM(..., survey=..., survey_bins=...)")
 
+_INTEGRALS_SOLO = ("the wake integrals are a solo keyword: a sweep carries none (run the member on its own, "
+                   "LUDVM(..., wake_integrals=True))")
+
 _REFUSED = {
     # keyword -> (value that is fine, why not otherwise)
     "checkpoint_every": (0, "a sweep has no checkpoint / resume"),
@@ -80,6 +83,9 @@ def _check_case(idx, kw, first):
     if "survey_gradient" in kw:
         raise ValueError(who + f"survey_gradient={kw['survey_gradient']!r}: the survey of a sweep carries no gradient sums (run the "
                          "member on its own, LUDVM(..., survey=..., survey_gradient=True))")
+    for key in ("wake_integrals", "wake_energy_steps"):
+        if key in kw:
+            raise ValueError(who + f"{key}={kw[key]!r}: {_INTEGRALS_SOLO}")
     for key, (fine, why) in _REFUSED.items():
         if key in kw and not (kw[key] is fine or (fine is not None and kw[key] == fine)):
             raise ValueError(who + f"{key}={kw[key]!r}: {why}")
@@ -379,6 +385,9 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     for key in ("survey_bins", "survey_period", "survey_phase0"):
         if common.get(key) is not None:
             raise ValueError(f"sweep: {key}={common[key]!r}: {_BINS_SOLO}")
+    for key in ("wake_integrals", "wake_energy_steps"):
+        if key in common:
+            raise ValueError(f"sweep: {key}={common[key]!r}: {_INTEGRALS_SOLO}")
     cases = list(cases)
     if not cases:
         return []

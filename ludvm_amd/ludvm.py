@@ -224,6 +224,23 @@ class LUDVM:
                  bit-identical however the run is cut, and a bin is still the plain sums of its steps.
                  Not a survey precision: refused with survey_precision other than 'f64' (it brings its own arithmetic), with
                  march=False, and with a run that cannot take the march (RuntimeError, no float64 in its place)
+      wake_integrals  False (default).  True: every time step also records the classical integrals of its vortex SYSTEM -- what
+                 the probes see: the wake before the step's Euler update, the vortices shed in the step at their placement, the
+                 bound vortices of the step, in the lab frame -- inside the device-resident march, float64.  `integral_sums`
+                 [nt, 4, 2, 6]: for every class of `integral_classes` = ('FREE', 'TEV', 'LEV', 'BOUND') and sign (slot 0: Gamma >= 0,
+                 slot 1: Gamma < 0) the count, sum G, sum G x, sum G z, sum G (x^2 + z^2), sum G^2 (row 0: the initial free
+                 vortices).  From them, on the host: `wake_circulation(cls, sign)`, `wake_centroid(cls, sign)`, `wake_impulse`
+                 [nt, 2] = rho (-sum G z, sum G x), `wake_angular_impulse`, `impulse_force` = -dI/dt, `impulse_Cl`, `impulse_Cd` (a
+                 check of `Cl`, `Cd` by another route through the physics).  The rows are bit-identical however the run is cut,
+                 checkpoints included, and every other result of the run keeps its bits.  The per-step
+                 path (march=False) forms the same rows on the host.  Refused: not a bool, in a sweep (a solo keyword), with
+                 `devices` > 1 or `distributed`
+      wake_energy_steps  None (default), or (first, stop, every) in `survey_steps`' form: at those steps the Hamiltonian of the
+                 system, W = 1/2 sum_a sum_b G_a G_b / (4 pi) ln((r_ab^2 + s_ab) / 2) = 1/2 sum_a G_a psi(x_a) over all its vortices
+                 (a = b included; the pair term of `stream_function`), goes to `wake_energy` [nt] (NaN where not sampled);
+                 `wake_energy_interaction` is W minus the self part ln(v_core^2 / 2) / (8 pi) sum G^2.  Gamma is clockwise-positive
+                 (its vorticity is -Gamma), so the kinetic energy per unit span is -rho W: W falls as the foil works on the
+                 fluid.  An O(N^2) float64 pair sum per sample.  Needs wake_integrals=True
       devices    several GPUs of this node in ONE process, no launcher: an int G (devices 0 .. G-1) or a list of ordinals.  One host
                  thread, one engine and one replica per device, the library's own RCCL communicator over them (ncclCommInitAll);
                  the object returned is a front whose attributes are replica 0's and whose methods run on all replicas
@@ -247,6 +264,9 @@ class LUDVM:
                 if kwargs.get('probes') is not None:
                     cls._check_probes(kwargs['probes'], kwargs.get('probe_frame', 'lab'))
                     raise ValueError("probes run on one GPU: not with more than one device in `devices`")
+                if kwargs.get('wake_integrals', False) is not False or kwargs.get('wake_energy_steps') is not None:
+                    cls._check_wake_integrals(kwargs.get('wake_integrals', False), kwargs.get('wake_energy_steps'))
+                    raise ValueError("wake_integrals runs on one GPU: not with more than one device in `devices`")
                 if kwargs.get('tracer_gradient', False) is not False:
                     cls._check_tracer_gradient(kwargs['tracer_gradient'], kwargs.get('tracers') is not None,
                                                kwargs.get('march', True), kwargs.get('tracer_precision', 'f64'))
@@ -337,6 +357,22 @@ class LUDVM:
         if stop <= first:
             raise ValueError(f"survey_steps: the window [{first}, {stop}) holds no time step")
         return np.ascontiguousarray(xz), shape, (first, stop, every)
+
+    @staticmethod
+    def _check_wake_integrals(wake_integrals, wake_energy_steps, nt=None):
+        """-> the energy window (first, stop, every) with stop clipped to nt, or None; ValueError from the keywords alone (nothing
+        else has been created yet)."""
+        if not isinstance(wake_integrals, (bool, np.bool_)):
+            raise ValueError(f"wake_integrals must be a bool (got {wake_integrals!r})")
+        if wake_energy_steps is None:
+            return None
+        if not wake_integrals:
+            raise ValueError("wake_energy_steps needs wake_integrals=True")
+        # (survey_steps' form and validation: one point stands in for the survey)
+        try:
+            return LUDVM._check_survey(np.zeros([2, 1]), 'lab', wake_energy_steps, nt=nt)[2]
+        except ValueError as e:
+            raise ValueError(str(e).replace('survey_steps', 'wake_energy_steps')) from e
 
     @staticmethod
     def _check_survey_precision(survey_precision, surveyed, march=True):
@@ -521,7 +557,12 @@ class LUDVM:
                  checkpoint_every=0, checkpoint_path=None, march=True, distributed=None, devices=None,
                  probes=None, probe_frame='lab', tracers=None, tracer_release=None, tracer_frame='lab', tracer_steps=None,
                  survey=None, survey_frame='lab', survey_steps=None, survey_precision='f64', tracer_precision='f64',
-                 survey_bins=None, survey_period=None, survey_phase0=None, tracer_gradient=False, survey_gradient=False):
+                 survey_bins=None, survey_period=None, survey_phase0=None, tracer_gradient=False, survey_gradient=False,
+                 wake_integrals=False, wake_energy_steps=None):
+        # refused before any engine, thread or communicator exists
+        energy_win = self._check_wake_integrals(wake_integrals, wake_energy_steps, nt=len(np.arange(t0, tf + dt, dt)))
+        if wake_integrals and distributed is not None and distributed is not False:
+            raise ValueError("wake_integrals runs on one GPU: not with `distributed`")
         if probes is not None:
             # refused before any engine, thread or communicator exists
             probe_xz = self._check_probes(probes, probe_frame)
@@ -607,6 +648,10 @@ class LUDVM:
             self.survey_gradient = 'f32x2' if isinstance(survey_gradient, str) else bool(survey_gradient)
             if self.survey_gradient:                # (a survey without it likewise)
                 self._ctor.update(survey_gradient=self.survey_gradient)
+        self.wake_integrals = bool(wake_integrals)
+        if self.wake_integrals:                     # (a run without them keeps the checkpoints it had)
+            self._ctor.update(wake_integrals=True, wake_energy_steps=None if energy_win is None else list(energy_win))
+            self.wake_energy_steps = energy_win
         # parameters (LUDVM.py:237-263)
         self.t0, self.tf, self.dt = t0, tf, dt
         self.chord, self.rho, self.Uinf = chord, rho, Uinf
@@ -943,7 +988,7 @@ class LUDVM:
         __slots__ = (
             # constants of the run
             'nf', 'x_gamma', 'detadx', 'gpts', 'foil', 'one_plus_cos_over_sin', 'half_c_sin_dth', 'wx', 'sum_free', 'first_step',
-            'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes',
+            'fslot', 'fsl', 'sb', 'prec_code', 'can_march', 'dense_march', 'march_chunk', 'probes', 'integrals',
             'tracers', 'trec', 'tcur', 'tF', 'survey', 'ssums', 'scount', 'sbins', 'sbsums', 'sbcounts', 'sgsums', 'sbgsums',
             # carried from step to step
             'itev', 'ilev', 'lesp_crit', 'sum_tev', 'sum_lev', 'last_tev', 'last_lev', 'LEV_shed', 'tev_slot', 'lev_slot', 'have_next')
@@ -1040,6 +1085,12 @@ class LUDVM:
             self.probe_u, self.probe_w = np.zeros([nt, S.probes.shape[1]]), np.zeros([nt, S.probes.shape[1]])
             p0 = self.probe_positions(0)
             self.probe_u[0], self.probe_w[0] = eng.induce(g_free, free0[0], free0[1], p0[0], p0[1], self.v_core, precision='f64')
+        S.integrals = self.wake_integrals
+        if S.integrals:
+            # row 0: the initial free vortices, as `probe_u` has it; the energy has no sample there (its window begins at 1)
+            self.integral_sums = np.zeros([nt, 4, 2, 6])
+            self.wake_energy = np.full(nt, np.nan)
+            self.integral_sums[0] = self._integral_row(np.zeros(nf, dtype=np.int64), g_free, free0[0], free0[1])
         S.tracers = getattr(self, 'tracer_xz', None)
         S.trec = S.tcur = None
         if S.tracers is not None:
@@ -1183,6 +1234,116 @@ class LUDVM:
             F = self.tracer_F_path[step]
         return self.ftle_from_F(F, self.dt * (step - self.tracer_release + 1.0))
 
+    # ---- wake integrals (wake_integrals=True) ---------------------------------------------------------
+    integral_classes = ('FREE', 'TEV', 'LEV', 'BOUND')
+
+    @staticmethod
+    def _integral_row(cls, g, x, z):
+        """float64 [4, 2, 6]: the six sums -- count, G, G x, G z, G (x^2 + z^2), G^2 -- of every class (0 .. 3) and sign (slot 0:
+        G >= 0, slot 1: G < 0) over the vortices (cls, g, x, z), as the per-step path forms them."""
+        cls, g, x, z = np.asarray(cls), np.asarray(g, dtype=float), np.asarray(x, dtype=float), np.asarray(z, dtype=float)
+        row = np.zeros([4, 2, 6])
+        neg = g < 0.0
+        for c in range(4):
+            for s in range(2):
+                m = (cls == c) & (neg == bool(s))
+                gm, xm, zm = g[m], x[m], z[m]
+                row[c, s] = [m.sum(), gm.sum(), (gm * xm).sum(), (gm * zm).sum(), (gm * (xm * xm + zm * zm)).sum(), (gm * gm).sum()]
+        return row
+
+    def _wake_tags(self, S):
+        """uint8 [wake size]: the class (0 FREE, 1 TEV, 2 LEV) of every vortex of the resident wake in its stored order, from the
+        free-vortex count and the slot maps of the vortices shed so far."""
+        tags = np.zeros(S.nf + S.itev + S.ilev, dtype=np.uint8)
+        tags[S.tev_slot[:S.itev]] = 1
+        tags[S.lev_slot[:S.ilev]] = 2
+        return tags
+
+    def _energy_sampled(self, step):
+        """Is time step `step` one of the energy's sampled steps?"""
+        if self.wake_energy_steps is None:
+            return False
+        first, stop, every = self.wake_energy_steps
+        return first <= step < stop and (step - first) % every == 0
+
+    def _integrals(self):
+        if not getattr(self, 'wake_integrals', False) or not hasattr(self, 'integral_sums'):
+            raise ValueError("the wake integrals need a run with wake_integrals=True")
+        return self.integral_sums
+
+    def _class_index(self, cls):
+        if isinstance(cls, str):
+            if cls.upper() not in self.integral_classes:
+                raise ValueError(f"class must be one of {self.integral_classes} (got {cls!r})")
+            return self.integral_classes.index(cls.upper())
+        if int(cls) != cls or not 0 <= int(cls) < 4:
+            raise ValueError(f"class must be one of {self.integral_classes} or 0 .. 3 (got {cls!r})")
+        return int(cls)
+
+    @staticmethod
+    def _sign_index(sign):
+        if sign in ('+', 1, 'pos'):
+            return 0
+        if sign in ('-', -1, 'neg'):
+            return 1
+        raise ValueError(f"sign must be '+' (Gamma >= 0) or '-' (Gamma < 0) (got {sign!r})")
+
+    def wake_circulation(self, cls=None, sign=None):
+        """float64 [nt]: the circulation the system of every step carries -- of class `cls` ('FREE', 'TEV', 'LEV', 'BOUND' or
+        0 .. 3; None: all) and sign ('+': the vortices with Gamma >= 0, '-': those with Gamma < 0; None: both)."""
+        sums = self._integrals()[:, :, :, 1]
+        if cls is not None:
+            sums = sums[:, [self._class_index(cls)]]
+        if sign is not None:
+            sums = sums[:, :, [self._sign_index(sign)]]
+        return sums.sum(axis=(1, 2))
+
+    def wake_centroid(self, cls, sign):
+        """float64 [nt, 2]: (sum G x / sum G, sum G z / sum G) of the vortices of class `cls` and sign `sign`; NaN where there is
+        none."""
+        row = self._integrals()[:, self._class_index(cls), self._sign_index(sign)]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            out = np.stack([row[:, 2] / row[:, 1], row[:, 3] / row[:, 1]], axis=1)
+        out[row[:, 0] == 0] = np.nan
+        return out
+
+    @property
+    def wake_impulse(self):
+        """float64 [nt, 2]: the linear impulse rho (-sum G z, +sum G x) of the whole system (Gamma is clockwise-positive:
+        u = +G dz / (2 pi s))."""
+        tot = self._integrals().sum(axis=(1, 2))
+        return self.rho * np.stack([-tot[:, 3], tot[:, 2]], axis=1)
+
+    @property
+    def wake_angular_impulse(self):
+        """float64 [nt]: the angular impulse about the lab origin, rho / 2 sum G (x^2 + z^2) (clockwise-positive Gamma)."""
+        return 0.5 * self.rho * self._integrals().sum(axis=(1, 2))[:, 4]
+
+    @property
+    def impulse_force(self):
+        """float64 [nt, 2]: the force on the foil the impulse implies, -(I_i - I_(i-1)) / dt; NaN in row 0 (free vortices only:
+        no foil) and in row 1, the first row of a system with the foil in it."""
+        I = self.wake_impulse
+        F = np.full_like(I, np.nan)
+        F[2:] = -(I[2:] - I[1:-1]) / self.dt
+        return F
+
+    @property
+    def impulse_Cl(self):
+        """float64 [nt]: impulse_force's lab z component over rho Uinf^2 chord / 2, the axes and normalisation of `Cl`."""
+        return self.impulse_force[:, 1] / (0.5 * self.rho * self.Uinf**2 * self.chord)
+
+    @property
+    def impulse_Cd(self):
+        """float64 [nt]: impulse_force's lab x component (the foil moves towards -x) over rho Uinf^2 chord / 2, as `Cd`."""
+        return self.impulse_force[:, 0] / (0.5 * self.rho * self.Uinf**2 * self.chord)
+
+    @property
+    def wake_energy_interaction(self):
+        """float64 [nt]: `wake_energy` minus its self part ln(v_core^2 / 2) / (8 pi) sum G^2 (the a = b terms)."""
+        self._integrals()
+        return self.wake_energy - np.log(0.5 * self.v_core**2) / (8.0 * np.pi) * self.integral_sums.sum(axis=(1, 2))[:, 5]
+
     def probe_positions(self, step):
         """Lab coordinates [2, P] of the probes at time step `step` ('tunnel' frame: x + xpiv[step])."""
         xz = self.probe_xz.copy()
@@ -1204,6 +1365,8 @@ class LUDVM:
             getattr(self, name)[...] = R[name]
         if S.probes is not None:
             self.probe_u[:S.first_step], self.probe_w[:S.first_step] = R['probe_u'], R['probe_w']
+        if S.integrals:
+            self.integral_sums[:S.first_step], self.wake_energy[:S.first_step] = R['integral_sums'], R['wake_energy']
         if S.tracers is not None:
             S.tcur = R['tracer_cur'].copy()
             for srow, row in zip(R['tracer_rows_steps'], R['tracer_rows']):
@@ -1241,6 +1404,9 @@ class LUDVM:
             raise RuntimeError("survey: this engine marches but has no march_set_survey (pass march=False for the per-step path)")
         if S.sbins is not None and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_survey_bins'):
             raise RuntimeError("survey_bins: this engine marches but has no march_set_survey_bins (pass march=False for the per-step "
+                               "path)")
+        if S.integrals and self.march and hasattr(eng, 'march_run') and not hasattr(eng, 'march_set_integrals'):
+            raise RuntimeError("wake_integrals: this engine marches but has no march_set_integrals (pass march=False for the per-step "
                                "path)")
         grad_tracers = S.tracers is not None and self.tracer_gradient
         # (tracer_gradient='f32x2': u, w and the gradient's sums from one hi+lo fp32 walk, so ONE setter for precision and gradient)
@@ -1303,6 +1469,10 @@ class LUDVM:
                     else:
                         eng.march_set_survey_gradient(True, gsums=S.sgsums if carried else None,
                                                       bin_gsums=S.sbgsums if carried else None)
+            if S.integrals:
+                eng.march_set_integrals(True, self._wake_tags(S), energy_steps=self.wake_energy_steps)
+        if S.integrals and self.wake_energy_steps is not None and not S.can_march and not hasattr(eng, 'scalar_field'):
+            raise RuntimeError("wake_energy_steps: the per-step path needs an engine with scalar_field")
         if grad_f32_survey and not S.can_march:
             # (neither float64 nor the per-step path in its place)
             raise RuntimeError("survey_gradient='f32x2' is evaluated inside the device-resident march, which this run cannot take "
@@ -1429,6 +1599,8 @@ class LUDVM:
             R = self.engine.march_run(i, cnt, S.prec_code, st, anchors=anchors)
         if S.probes is not None:
             self.probe_u[i:j], self.probe_w[i:j] = self.engine.march_probes(cnt)
+        if S.integrals:
+            self.integral_sums[i:j], self.wake_energy[i:j] = self.engine.march_integrals(cnt)
         if S.tracers is not None:
             for srow, row in zip(*self.engine.march_tracers()):
                 self.tracer_path.store(int(srow), row)
@@ -1703,6 +1875,17 @@ class LUDVM:
                 if S.sbgsums is not None and S.sbins[i] >= 0:
                     for acc, term in zip(S.sbgsums[S.sbins[i]], terms):
                         acc += term
+        if S.integrals:
+            # the step's sources in the march's order -- old wake, shed vortices, bound vortices -- and their classes
+            ns = 2 if shed else 1
+            wx_, wz_, wg_ = eng.wake_read(0, n_wake, gamma=True) if n_wake else (np.empty(0),) * 3
+            g_all = np.concatenate([wg_, new_g[:ns], dGamma])
+            x_all, z_all = np.concatenate([wx_, new_x[:ns], xg]), np.concatenate([wz_, new_z[:ns], zg])
+            cls_all = np.concatenate([self._wake_tags(S), [1, 2][:ns], np.full(len(xg), 3)])
+            self.integral_sums[i] = self._integral_row(cls_all, g_all, x_all, z_all)
+            if self._energy_sampled(i):
+                psi = eng.scalar_field('psi', g_all, x_all, z_all, x_all, z_all, vc)
+                self.wake_energy[i] = 0.5 * float(np.sum(g_all * psi))
         n_after = n_wake + len(new_x)
         one_trip = (not record) and sb is not None and i < nt - 1 and hasattr(eng, 'wake_step_into')
         if not one_trip:
@@ -1798,6 +1981,8 @@ class LUDVM:
             d[name] = getattr(self, name)
         if S.probes is not None:        # (the definition travels in `ctor`)
             d['probe_u'], d['probe_w'] = self.probe_u[:next_step], self.probe_w[:next_step]
+        if S.integrals:                 # (likewise; the tags are re-derived from the slot maps)
+            d['integral_sums'], d['wake_energy'] = self.integral_sums[:next_step], self.wake_energy[:next_step]
         if S.tracers is not None:       # (likewise; the current positions and the rows recorded so far)
             d['tracer_cur'] = self.engine.march_tracer_state() if S.can_march else S.tcur
             steps_t = self.tracer_path.steps()
@@ -1846,6 +2031,8 @@ class LUDVM:
                     raise ValueError("probes run on one GPU: this checkpoint cannot be resumed on more than one device")
                 if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('tracers') is not None:
                     raise ValueError("tracers run on one GPU: this checkpoint cannot be resumed on more than one device")
+                if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('wake_integrals'):
+                    raise ValueError("wake_integrals runs on one GPU: this checkpoint cannot be resumed on more than one device")
                 if json.loads(str(np.load(path, allow_pickle=False)['ctor'])).get('survey') is not None:
                     raise ValueError("a survey runs on one GPU: this checkpoint cannot be resumed on more than one device")
                 return MultiDeviceLUDVM((), {}, devs, builder=lambda r, eng, grp: cls.resume(
