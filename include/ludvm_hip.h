@@ -920,6 +920,52 @@ int ludvm_ensemble_run_surveyed_graded(ludvm_ctx* ctx, size_t members, int npan,
                                        size_t bin_rows, int nbins, double* bin_sums, size_t bin_doubles, double* grad_sums,
                                        size_t grad_doubles, double* bin_grad_sums, size_t bin_grad_doubles);
 
+/* ---- wake integrals in an ensemble: class moments and energy of every member's vortex system ---------------------------
+ *
+ * ludvm_ensemble_run_integrals is ludvm_ensemble_run_surveyed_graded (every observer optional: nprobe, ntracer, nsurvey, nbins
+ * = 0 and the gradient arrays NULL are allowed) with the wake integrals of ludvm_march_set_integrals accumulated inside the one
+ * launch.  The definition is the same, per member and in float64: the system of step i >= 1 of a member is the sources its
+ * probes see -- its wake before the Euler update of step i, the vortices shed in step i at their placement, the npan bound
+ * vortices of step i -- and for every class (0 FREE, 1 TEV, 2 LEV, 3 BOUND) and sign (slot 0: G >= 0, slot 1: G < 0) six sums
+ * are formed: the count (as a double), sum G, sum G x, sum G z, sum G (x^2 + z^2), sum G^2.  At the sampled steps of the energy
+ * (energy_first <= i < min(energy_stop, nt), (i - energy_first) % energy_every == 0) W = 1/2 sum_a G_a psi(x_a) over all those
+ * sources, a = b included, psi being ludvm_scalar_f64's LUDVM_FIELD_PSI pair term with the member's own vcore: an
+ * O((n + npan)^2) float64 pair sum with a logarithm per pair inside the member's workgroup (a member at the 8192-vortex limit:
+ * about 7e7 pairs per sample).
+ *   integral_sums (host)        [kin_rows][4][2][6] doubles (integral_doubles = exactly kin_rows * 48): a member's time level i
+ *                               is row kin_off + i, like its probe rows; the launch writes rows 1 .. nt - 1, row 0 of a member
+ *                               and rows no member owns are 0
+ *   energy (host)               [kin_rows] doubles (energy_doubles = exactly kin_rows): W at the sampled steps, NaN elsewhere
+ *                               (the entry fills the array with NaN before the launch)
+ * integral_doubles = 0 with both arrays NULL (and energy_every = 0) is ludvm_ensemble_run_surveyed_graded itself: the same launch
+ * and the same bits.  energy_every = 0 with energy NULL and energy_doubles = 0: no samples (energy_first / energy_stop are not
+ * looked at).  Every other argument, output, limit and guarantee is ludvm_ensemble_run_surveyed_graded's, and those outputs keep
+ * the bits of the same call without integrals: the two phases read the member's slab and write nothing but the two arrays.  The
+ * order of every add depends on the member's own wake size and npan only (lane j adds the indices j, j + 256, ... in that
+ * order, then a fixed tree; the energy walks the sources in index order and adds a lane's points in tile order): a member's rows
+ * do not depend on the batch and repeat bit for bit, and a sampled step's W does not depend on the window.  A member differs
+ * from ludvm_march_run(LUDVM_PREC_F64) with ludvm_march_set_integrals by summation order only.  Nothing is kept on the context.
+ * Checked on the host before anything touches the device (LUDVM_E_ARG): an array NULL with its count non-zero (or given with a
+ * count of 0), integral_doubles != kin_rows * 48, energy_doubles != kin_rows, energy (array, count or energy_every != 0) without
+ * the integral sums, energy_first < 1, energy_every < 1 with an energy array (energy_every < 0 always), energy_stop <=
+ * energy_first, and kin_rows * 49 * 8 bytes of rows over 1 GiB (split the batch).  A sharded context answers LUDVM_E_STATE.
+ * The entry point is an addition to ABI 7: detect it by its symbol. */
+int ludvm_ensemble_run_integrals(ludvm_ctx* ctx, size_t members, int npan, int ncoef, const double* scalars,
+                                 size_t scalar_count, const double* tables, const double* kin, size_t kin_rows,
+                                 const double* init, const double* free_xzg, size_t free_count, const long long* desc,
+                                 const long long* snap_steps, size_t nsnap, double* rows, size_t rows_count, double* wakes,
+                                 size_t wake_doubles, long long* wake_n, const double* probe_x, const double* probe_z,
+                                 size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w,
+                                 const double* seed_x, const double* seed_z, const long long* release, size_t ntracer,
+                                 const double* tshift_x, size_t tshift_rows, const long long* trec_steps, size_t ntrec,
+                                 double* tracer_rows, size_t tracer_doubles, const double* survey_x, const double* survey_z,
+                                 size_t nsurvey, const double* sshift_x, size_t sshift_rows, long long first, long long stop,
+                                 long long every, double* survey_sums, size_t survey_doubles, const int* bin_of_step,
+                                 size_t bin_rows, int nbins, double* bin_sums, size_t bin_doubles, double* grad_sums,
+                                 size_t grad_doubles, double* bin_grad_sums, size_t bin_grad_doubles, double* integral_sums,
+                                 size_t integral_doubles, double* energy, size_t energy_doubles, long long energy_first,
+                                 long long energy_stop, long long energy_every);
+
 /* ---- flow field: backs LUDVM.flowfield (LUDVM.py:1186-1298) -------------------------------- */
 
 /* Grid targets generated on the device, x-major ravel like np.meshgrid(indexing='ij')

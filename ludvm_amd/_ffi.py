@@ -148,6 +148,13 @@ SIGNATURES = {
                                            _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, POINTER(c_longlong), c_size_t, _pd, c_size_t,
                                            _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_size_t,
                                            POINTER(c_int), c_size_t, c_int, _pd, c_size_t, _pd, c_size_t, _pd, c_size_t],
+    "ludvm_ensemble_run_integrals": [c_void_p, c_size_t, c_int, c_int, _pd, c_size_t, _pd, _pd, c_size_t, _pd, _pd, c_size_t,
+                                     POINTER(c_longlong), POINTER(c_longlong), c_size_t, _pd, c_size_t, _pd, c_size_t,
+                                     POINTER(c_longlong), _pd, _pd, c_size_t, _pd, c_size_t, _pd, _pd,
+                                     _pd, _pd, POINTER(c_longlong), c_size_t, _pd, c_size_t, POINTER(c_longlong), c_size_t, _pd, c_size_t,
+                                     _pd, _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong, _pd, c_size_t,
+                                     POINTER(c_int), c_size_t, c_int, _pd, c_size_t, _pd, c_size_t, _pd, c_size_t,
+                                     _pd, c_size_t, _pd, c_size_t, c_longlong, c_longlong, c_longlong],
     "ludvm_flowfield_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
                             c_double, _pf, _pf],
     "ludvm_flowfield_vorticity_f32": [c_void_p, c_double, c_double, c_double, c_size_t, c_size_t, _pd, _pd, _pd, c_size_t,
@@ -187,7 +194,8 @@ ADDED_IN_ABI_7 = ("ludvm_ensemble_run_probed", "ludvm_march_set_tracers", "ludvm
                   "ludvm_march_read_survey_gradient", "ludvm_scalar_f32x2", "ludvm_flowfield_scalar_rows_f32x2",
                   "ludvm_gradient_f32x2", "ludvm_flowfield_gradient_rows_f32x2", "ludvm_march_set_tracer_gradient_f32x2",
                   "ludvm_ensemble_run_surveyed_binned", "ludvm_march_set_survey_gradient_f32x2",
-                  "ludvm_ensemble_run_surveyed_graded", "ludvm_march_set_integrals", "ludvm_march_read_integrals")
+                  "ludvm_ensemble_run_surveyed_graded", "ludvm_march_set_integrals", "ludvm_march_read_integrals",
+                  "ludvm_ensemble_run_integrals")
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t, c_void_p)
 

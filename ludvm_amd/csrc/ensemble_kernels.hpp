@@ -45,6 +45,16 @@
 //                      member's gradient sums [5][K] and, on a step with a bin, to block b of its [B][5][K].  (u, w) keep their
 //                      bits: the velocity sums and bins are those of the sweep without gradient sums.  The bins' table is a
 //                      run-time value here (null: no bins).  Nothing else changes: no other kernel contains it.
+// With wake integrals (ensemble_integrals<PROBES, TRACERS, SURVEY>; the definitions of march_integral_partial /
+// march_energy_partial, march_kernels.hpp), between 2 and 2p:
+//   2i. moments        every step: the sources [0, n + npan) of 2p -> for each class (FREE, TEV, LEV, BOUND) and sign the count,
+//                      sum G, sum G x, sum G z, sum G (x^2 + z^2), sum G^2; row `step` of the member's integral rows [nt][48].
+//                      The class of a wake vortex is a byte of the member's tag buffer [cap]: FREE for the free vortices
+//                      (step 0), TEV / LEV written by the lane that appends the shed vortices; an index >= n is BOUND.
+//   2e. energy         on the sampled steps W = 1/2 sum_a G_a psi(x_a) over the same sources, a = b included (scalar_term<
+//                      kScalarPsi>): O((n + npan)^2) float64 pairs with a logarithm each, inside the one workgroup.
+//                      Both phases read the slab and write nothing but the member's integral buffers: no other kernel contains
+//                      them.
 //
 
 // Determinism: every sum is formed in an order that depends on the member's own wake size, npan and ncoef only (lane p
@@ -475,18 +485,89 @@ __device__ __forceinline__ void ens_grad_survey_step(const EnsembleSurvey& V, co
   __syncthreads();
 }
 
+// The wake integrals of a member (ensemble_integrals only), one record per member in a device array of its own indexed by
+// blockIdx.x: the records above stay what the other kernels read.
+struct EnsembleIntegrals {
+  unsigned char* tags;          // [cap]: the class (IntegralClass) of every wake vortex of this member
+  double* sums;                 // nt rows of kIntegralSums doubles (row 0 is the host's)
+  double* energy;               // nt doubles (NaN before the launch), or null without samples
+  long long first, stop, every; // sampled steps of the energy: first <= step < stop, (step - first) % every == 0
+};
+
+// Phase 2i: the 48 moment sums of sources [0, ns) -- wake [0, n), bound vortices behind it -- into `row`.  For each of the eight
+// (class, sign) keys lane j walks i = j, j + kBlock, ... in that order and adds the six terms by select (march_integral_partial's
+// statements), then block_sum_n's fixed tree: the order of every add depends on n and ns alone.  All threads of the workgroup
+// call this.
+__device__ __forceinline__ void ens_moment_row(const double* __restrict__ xs, const double* __restrict__ zs,
+                                               const double* __restrict__ gs, const unsigned char* __restrict__ tags, long long n,
+                                               long long ns, double* __restrict__ row, double* scratch) {
+  const int j = threadIdx.x;
+  for (int q = 0; q < 2 * kIntegralClasses; ++q) {
+    double v[kIntegralMoments] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long i = j; i < ns; i += kBlock) {
+      const double x = xs[i], z = zs[i], g = gs[i];
+      const int cls = i < n ? (int)tags[i] : (int)kClassBound;
+      const bool m = 2 * cls + (g < 0.0 ? 1 : 0) == q;
+      const double gk = m ? g : 0.0;
+      v[0] += m ? 1.0 : 0.0;
+      v[1] += gk;
+      v[2] += gk * x;
+      v[3] += gk * z;
+      v[4] += gk * __builtin_fma(z, z, x * x);
+      v[5] += gk * gk;
+    }
+    block_sum_n<kIntegralMoments>(v, scratch);
+    if (j < kIntegralMoments) {
+      double r = v[0];
+#pragma unroll
+      for (int k = 1; k < kIntegralMoments; ++k) r = j == k ? v[k] : r;
+      row[q * kIntegralMoments + j] = r;
+    }
+  }
+}
+
+// Phase 2e: W = 1/2 sum_a G_a psi(x_a) over sources [0, ns), the points being the sources themselves in tiles of kBlock points.
+// Every source tile is staged through lx / lz / lg and walked in index order, bounded by the tile's count: a padded slot is
+// never evaluated (0 ln(inf), pair_scalar_f64's rule).  A lane multiplies each of its points' sums by G_a and accumulates in
+// tile order; block_sum's tree; times 1/2 1/(4 pi).  A lane without a point walks along at the origin and its sum is dropped by
+// select.  All threads of the workgroup call this; every thread gets W.
+__device__ __forceinline__ double ens_energy(const double* __restrict__ xs, const double* __restrict__ zs,
+                                             const double* __restrict__ gs, long long ns, double vc4, double* lx, double* lz,
+                                             double* lg, double* scratch) {
+  const int j = threadIdx.x;
+  double acc = 0.0;
+  for (long long t0 = 0; t0 < ns; t0 += kBlock) {
+    const long long a = t0 + j;
+    const bool mine = a < ns;
+    const double xp = mine ? xs[a] : 0.0, zp = mine ? zs[a] : 0.0, ga = mine ? gs[a] : 0.0;
+    double psi = 0.0;
+    for (long long base = 0; base < ns; base += kEnsTile) {
+      const int cnt = (int)(ns - base < kEnsTile ? ns - base : kEnsTile);
+      __syncthreads();
+      if (j < cnt) { lx[j] = xs[base + j]; lz[j] = zs[base + j]; lg[j] = gs[base + j]; }
+      __syncthreads();
+#pragma unroll 2
+      for (int s = 0; s < cnt; ++s) psi = __builtin_fma(lg[s], scalar_term<kScalarPsi>(xp - lx[s], zp - lz[s], vc4), psi);
+    }
+    acc += mine ? ga * psi : 0.0;
+  }
+  return block_sum(acc, scratch) * (0.5 * kInv4PiD);
+}
+
 // The time loop of one member.  ensemble_march<PROBES> is <PROBES, false, false>: what it compiled to before there were tracers;
 // ensemble_traced<PROBES> is <PROBES, true, false>: what it compiled to before there was a survey; ensemble_surveyed<PROBES,
 // TRACERS> is <PROBES, TRACERS, true>: what it compiled to before there were bins; ensemble_binned<PROBES, TRACERS> is <PROBES,
 // TRACERS, true, true>: what it compiled to before there were gradient sums.  GRAD (ensemble_graded) takes the bins' table as
-// a run-time value: a null table is a gradient survey without bins.
-template <bool PROBES, bool TRACERS, bool SURVEY, bool BINS = false, bool GRAD = false>
+// a run-time value: a null table is a gradient survey without bins.  INTEG (ensemble_integrals) adds phases 2i and 2e to any of
+// them.
+template <bool PROBES, bool TRACERS, bool SURVEY, bool BINS = false, bool GRAD = false, bool INTEG = false>
 __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps,
                                                int nsnap, const EnsembleTracers* __restrict__ tracers,
                                                const long long* __restrict__ trec_steps, int ntrec,
                                                const EnsembleSurvey* __restrict__ surveys,
                                                [[maybe_unused]] const EnsembleSurveyBins* __restrict__ bins = nullptr,
-                                               [[maybe_unused]] const EnsembleSurveyGrad* __restrict__ grads = nullptr) {
+                                               [[maybe_unused]] const EnsembleSurveyGrad* __restrict__ grads = nullptr,
+                                               [[maybe_unused]] const EnsembleIntegrals* __restrict__ integrals = nullptr) {
   static_assert(SURVEY || !BINS, "bins belong to a survey");
   static_assert(BINS || !GRAD, "the gradient sums take the bins' table at run time");
   __shared__ __attribute__((aligned(16))) double lx[kEnsTile + kEnsGroup];
@@ -516,6 +597,8 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
 
   // step 0: the free vortices are the wake; state of the march as ludvm_march_run takes it from its caller
   for (long long i = j; i < E.nfree; i += kBlock) { xc[i] = E.free_x[i]; zc[i] = E.free_z[i]; g[i] = E.free_g[i]; }
+  if constexpr (INTEG)
+    for (long long i = j; i < E.nfree; i += kBlock) integrals[blockIdx.x].tags[i] = (unsigned char)kClassFree;
   if (j < ncoef) prevA[j] = E.init[kEnsInitHead + j];
   if (j < 4) place[j] = E.init[j];
   if (j <= nsnap) E.rec_n[j] = -1;
@@ -682,6 +765,11 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
       // the shed vortices join the wake (:1095-1098)
       xc[n0] = tev_x; zc[n0] = tev_z; g[n0] = g_tev;
       if (shed) { xc[n0 + 1] = lev_x; zc[n0 + 1] = lev_z; g[n0 + 1] = g_lev; }
+      if constexpr (INTEG) {
+        unsigned char* tags = integrals[blockIdx.x].tags;
+        tags[n0] = (unsigned char)kClassTev;
+        if (shed) tags[n0 + 1] = (unsigned char)kClassLev;
+      }
     }
     if (j < ncoef) {
       prevA[j] = A[j];
@@ -699,6 +787,17 @@ __device__ __forceinline__ void ens_member_run(const EnsembleMember* __restrict_
     sum_tev += g_tev;
     sum_lev += g_lev;
     __syncthreads();
+
+    // ---- 2i. moments of every step, 2e. energy of a sampled one: the sources of 2p, into the member's integral buffers ----------
+    if constexpr (INTEG) {
+      const EnsembleIntegrals& I = integrals[blockIdx.x];
+      ens_moment_row(xc, zc, g, I.tags, n, n + npan, I.sums + (size_t)step * kIntegralSums, scratch);
+      // (the same for every lane of the workgroup: an unsampled step skips the phase before its first barrier)
+      if (I.energy && step >= I.first && step < I.stop && (step - I.first) % I.every == 0) {
+        const double W = ens_energy(xc, zc, g, n + npan, m.vc4, lx, lz, lg, scratch);
+        if (j == 0) I.energy[step] = W;
+      }
+    }
 
     // ---- 2p. probes: the sources of the roll-up below, at the probe points (:1095-1106) -----------------------------------
     if constexpr (PROBES)
@@ -832,6 +931,19 @@ ensemble_graded(const EnsembleMember* __restrict__ members, const long long* __r
                 const EnsembleSurvey* __restrict__ surveys, const EnsembleSurveyBins* __restrict__ bins,
                 const EnsembleSurveyGrad* __restrict__ grads) {
   ens_member_run<PROBES, TRACERS, true, true, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec, surveys, bins, grads);
+}
+
+// Any of the kernels above with phases 2i and 2e: the launches of ludvm_ensemble_run_integrals.  SURVEY: 0 none (ensemble_march /
+// ensemble_traced), 1 plain (ensemble_surveyed), 2 binned (ensemble_binned), 3 graded (ensemble_graded).
+template <bool PROBES, bool TRACERS, int SURVEY>
+__global__ void __launch_bounds__(kBlock)
+ensemble_integrals(const EnsembleMember* __restrict__ members, const long long* __restrict__ snap_steps, int nsnap,
+                   const EnsembleTracers* __restrict__ tracers, const long long* __restrict__ trec_steps, int ntrec,
+                   const EnsembleSurvey* __restrict__ surveys, const EnsembleSurveyBins* __restrict__ bins,
+                   const EnsembleSurveyGrad* __restrict__ grads, const EnsembleIntegrals* __restrict__ integrals) {
+  static_assert(SURVEY >= 0 && SURVEY <= 3, "0 none, 1 plain, 2 binned, 3 graded");
+  ens_member_run<PROBES, TRACERS, SURVEY >= 1, SURVEY >= 2, SURVEY == 3, true>(members, snap_steps, nsnap, tracers, trec_steps, ntrec,
+                                                                               surveys, bins, grads, integrals);
 }
 
 }  // namespace ludvm

@@ -1133,16 +1133,24 @@ struct EnsembleSurveyArgs {
   double* bin_grad_sums = nullptr; size_t bin_grad_doubles = 0;
 };
 
+// The integral arguments of ludvm_ensemble_run_integrals (all zero / null: none)
+struct EnsembleIntegralArgs {
+  double* sums = nullptr; size_t doubles = 0;
+  double* energy = nullptr; size_t energy_doubles = 0;
+  long long first = 0, stop = 0, every = 0;
+};
+
 // ludvm_ensemble_run (nprobe = 0: the probe arguments are not looked at), ludvm_ensemble_run_probed, with tracers
 // ludvm_ensemble_run_traced, with a survey ludvm_ensemble_run_surveyed, with bins ludvm_ensemble_run_surveyed_binned and, with
-// gradient sums, ludvm_ensemble_run_surveyed_graded
+// gradient sums, ludvm_ensemble_run_surveyed_graded; any of them with wake integrals, ludvm_ensemble_run_integrals
 int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
                       const double* tables, const double* kin, size_t kin_rows, const double* init, const double* free_xzg,
                       size_t free_count, const long long* desc, const long long* snap_steps, size_t nsnap, double* rows,
                       size_t rows_count, double* wakes, size_t wake_doubles, long long* wake_n, const double* probe_x,
                       const double* probe_z, size_t nprobe, const double* shift_x, size_t shift_rows, double* probe_u,
                       double* probe_w, const EnsembleTracerArgs& tr = EnsembleTracerArgs(),
-                      const EnsembleSurveyArgs& sv = EnsembleSurveyArgs()) {
+                      const EnsembleSurveyArgs& sv = EnsembleSurveyArgs(),
+                      const EnsembleIntegralArgs& ig = EnsembleIntegralArgs()) {
   if (!c) return LUDVM_E_ARG;
   if (c->shard_world > 1 || (c->comm && c->comm_world > 1))
     return fail(c, LUDVM_E_STATE, "ensemble: the context is sharded; members are independent -- split the list per device");
@@ -1238,6 +1246,25 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     if (sv.bin_grad_doubles != members * B * 5 * K)
       return fail(c, LUDVM_E_ARG, "ensemble: survey bin gradient sums must hold members x bins x 5 x points doubles");
   }
+  const bool I = ig.sums || ig.doubles;
+  const bool E = ig.energy || ig.energy_doubles || ig.every != 0;
+  if (E && !I) return fail(c, LUDVM_E_ARG, "ensemble: the wake energy needs the integral sums");
+  if (I) {
+    if (!ig.sums) return fail(c, LUDVM_E_ARG, "null array");
+    // kin_rows x (48 + 1) x 8 bytes of integral rows and energy: at most 1 GiB
+    if (kin_rows > ((size_t)1 << 30) / (8 * (kIntegralSums + 1)))
+      return fail(c, LUDVM_E_ARG, "ensemble: " + std::to_string(8.0 * (kIntegralSums + 1) * (double)kin_rows / (1 << 20)) +
+                                      " MiB of integral rows (8 x 49 x " + std::to_string(kin_rows) +
+                                      " kinematics rows) are over 1 GiB; split the batch");
+    if (ig.doubles != kin_rows * kIntegralSums)
+      return fail(c, LUDVM_E_ARG, "ensemble: integral sums must hold kinematics rows x 48 doubles");
+  }
+  if (E) {
+    if (!ig.energy) return fail(c, LUDVM_E_ARG, "null array");
+    if (ig.energy_doubles != kin_rows) return fail(c, LUDVM_E_ARG, "ensemble: the wake energy must hold one double per kinematics row");
+    if (ig.first < 1 || ig.every < 1) return fail(c, LUDVM_E_ARG, "ensemble: energy steps: first >= 1 and every >= 1");
+    if (ig.stop <= ig.first) return fail(c, LUDVM_E_ARG, "ensemble: energy steps: the window holds no time step");
+  }
   if (!scalars || !tables || !kin || !init || !desc || !rows || !wakes || !wake_n || (free_count && !free_xzg) || (nsnap && !snap_steps))
     return fail(c, LUDVM_E_ARG, "null array");
   if (npan < 1 || npan > kMarchMaxPan || ncoef < 4 || ncoef > kMarchMaxCoef)
@@ -1273,7 +1300,7 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     const double* sc = scalars + 12 * mi;
     if (sc[8] != 0.0 && !(sc[9] > 0.0 && sc[10] >= 1.0 && sc[11] > 0.0))
       return fail(c, LUDVM_E_ARG, who + "'Ramesh' needs maxerror > 0, maxiter >= 1, epsilon > 0");
-    work_doubles += 5 * (cap + P) + 2 * M;
+    work_doubles += 5 * (cap + P) + 2 * M + (I ? (cap + 7) / 8 : 0);      // (integrals: a tag byte per wake vortex)
   }
 
   HIPCHK(c, hipSetDevice(c->device));
@@ -1299,7 +1326,10 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   // outputs)
   const size_t in_bins = (B ? Arena::need(sv.bin_rows, sizeof(int)) : 0) + (B || G ? Arena::need(members, sizeof(EnsembleSurveyBins)) : 0);
   const size_t in_grad = G ? Arena::need(members, sizeof(EnsembleSurveyGrad)) : 0;
-  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey + in_bins + in_grad));
+  // (integrals: the members' integral records; rows and energy behind the outputs, the tags in the work memory)
+  const size_t in_integ = I ? Arena::need(members, sizeof(EnsembleIntegrals)) : 0;
+  CHK(ensure(c, c->ens_in, in_tab + in_kin + in_init + in_free + in_snap + in_mem + in_probe + in_tracer + in_survey + in_bins + in_grad +
+                               in_integ));
   CHK(ensure(c, c->ens_work, work_doubles * 8));
   const size_t out_rows = Arena::need(rows_count * row_doubles, 8), out_wakes = Arena::need(wake_doubles, 8);
   const size_t out_n = Arena::need(members * nrec, 8);
@@ -1309,7 +1339,8 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   const size_t out_survey = K ? Arena::need(members * 5 * K, 8) : 0;
   const size_t out_bins = B ? Arena::need(members * B * 5 * K, 8) : 0;
   const size_t out_grad = G ? Arena::need(members * 5 * K, 8) + (B ? Arena::need(members * B * 5 * K, 8) : 0) : 0;
-  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey + out_bins + out_grad));
+  const size_t out_integ = I ? Arena::need(kin_rows * kIntegralSums, 8) + (E ? Arena::need(kin_rows, 8) : 0) : 0;
+  CHK(ensure(c, c->ens_out, out_rows + out_wakes + out_n + out_probe + out_tracer + out_survey + out_bins + out_grad + out_integ));
   Arena in(c->ens_in.p), out(c->ens_out.p);
   double* d_tab = in.take<double>(members * tab_doubles);
   double* d_kin = in.take<double>(kin_rows * krow);
@@ -1365,8 +1396,16 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     d_gsums = out.take<double>(members * 5 * K);
     if (B) d_bgsums = out.take<double>(members * B * 5 * K);
   }
+  double *d_isums = nullptr, *d_energy = nullptr;
+  EnsembleIntegrals* d_ig = nullptr;
+  if (I) {
+    d_ig = in.take<EnsembleIntegrals>(members);
+    d_isums = out.take<double>(kin_rows * kIntegralSums);
+    if (E) d_energy = out.take<double>(kin_rows);
+  }
 
   std::vector<EnsembleMember> hm(members);
+  std::vector<EnsembleIntegrals> hi(I ? members : 0);
   std::vector<EnsembleSurvey> hv(K ? members : 0);
   std::vector<EnsembleSurveyBins> hb(B || G ? members : 0);
   std::vector<EnsembleSurveyGrad> hg(G ? members : 0);
@@ -1422,6 +1461,14 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
       hg[mi].sums = d_gsums + mi * 5 * K;
       hg[mi].bin_sums = B ? d_bgsums + mi * B * 5 * K : nullptr;
     }
+    if (I) {
+      EnsembleIntegrals& q = hi[mi];
+      q.tags = reinterpret_cast<unsigned char*>(work);
+      work += (cap + 7) / 8;
+      q.sums = d_isums + (size_t)d[1] * kIntegralSums;
+      q.energy = E ? d_energy + (size_t)d[1] : nullptr;
+      q.first = ig.first; q.stop = ig.stop; q.every = ig.every;
+    }
     e.rows = d_rows + (size_t)d[4] * row_doubles;
     e.rec = d_wakes + (size_t)d[5];
     e.rec_n = d_n + mi * nrec;
@@ -1475,8 +1522,43 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
     HIPCHK(c, hipMemsetAsync(d_gsums, 0, members * 5 * K * 8, c->stream));
     if (B) HIPCHK(c, hipMemsetAsync(d_bgsums, 0, members * B * 5 * K * 8, c->stream));
   }
+  if (I) {
+    HIPCHK(c, hipMemcpyAsync(d_ig, hi.data(), members * sizeof(EnsembleIntegrals), hipMemcpyHostToDevice, c->stream));
+    // (row 0 of a member and rows of `kin` that no member owns stay 0; the energy is NaN wherever no sample lands)
+    HIPCHK(c, hipMemsetAsync(d_isums, 0, kin_rows * kIntegralSums * 8, c->stream));
+    if (E) {
+      std::fill(ig.energy, ig.energy + kin_rows, std::numeric_limits<double>::quiet_NaN());
+      HIPCHK(c, hipMemcpyAsync(d_energy, ig.energy, kin_rows * 8, hipMemcpyHostToDevice, c->stream));
+    }
+  }
   // ONE launch: a workgroup per member, all of its time steps inside
-  if (G) {
+  if (I) {
+    const dim3 grid((unsigned)members), block(kBlock);
+    const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
+    const long long* ar = d_trec; const EnsembleSurvey* av = d_sv; const EnsembleSurveyBins* ab = d_sb;
+    const EnsembleSurveyGrad* ag = d_sg; const EnsembleIntegrals* ai = d_ig;
+#define LUDVM_ENS_INTEGRALS(SURVEY)                                                                                                      \
+  do {                                                                                                                                   \
+    if (M && nprobe)                                                                                                                     \
+      hipLaunchKernelGGL((ensemble_integrals<true, true, SURVEY>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec, av, \
+                         ab, ag, ai);                                                                                                    \
+    else if (M)                                                                                                                          \
+      hipLaunchKernelGGL((ensemble_integrals<false, true, SURVEY>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec,    \
+                         av, ab, ag, ai);                                                                                                \
+    else if (nprobe)                                                                                                                     \
+      hipLaunchKernelGGL((ensemble_integrals<true, false, SURVEY>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec,    \
+                         av, ab, ag, ai);                                                                                                \
+    else                                                                                                                                 \
+      hipLaunchKernelGGL((ensemble_integrals<false, false, SURVEY>), grid, block, 0, c->stream, am, as, (int)nsnap, at, ar, (int)ntrec,   \
+                         av, ab, ag, ai);                                                                                                \
+  } while (0)
+    // SURVEY: 3 graded, 2 binned, 1 plain, 0 none -- the kernel the call without integrals launches, with phases 2i and 2e
+    if (G) LUDVM_ENS_INTEGRALS(3);
+    else if (B) LUDVM_ENS_INTEGRALS(2);
+    else if (K) LUDVM_ENS_INTEGRALS(1);
+    else LUDVM_ENS_INTEGRALS(0);
+#undef LUDVM_ENS_INTEGRALS
+  } else if (G) {
     const dim3 grid((unsigned)members), block(kBlock);
     const EnsembleMember* am = d_mem; const long long* as = d_snap; const EnsembleTracers* at = d_tr;
     const long long* ar = d_trec; const EnsembleSurvey* av = d_sv; const EnsembleSurveyBins* ab = d_sb;
@@ -1526,7 +1608,9 @@ int ensemble_run_body(ludvm_ctx* c, size_t members, int npan, int ncoef, const d
   if (B) HIPCHK(c, hipMemcpyAsync(sv.bin_sums, d_bsums, members * B * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
   if (G) HIPCHK(c, hipMemcpyAsync(sv.grad_sums, d_gsums, members * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
   if (G && B) HIPCHK(c, hipMemcpyAsync(sv.bin_grad_sums, d_bgsums, members * B * 5 * K * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv, hb, hg and tmin live on this frame)
+  if (I) HIPCHK(c, hipMemcpyAsync(ig.sums, d_isums, kin_rows * kIntegralSums * 8, hipMemcpyDeviceToHost, c->stream));
+  if (E) HIPCHK(c, hipMemcpyAsync(ig.energy, d_energy, kin_rows * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // (hm, ht, hv, hb, hg, hi and tmin live on this frame)
   return LUDVM_OK;
 }
 
@@ -1656,6 +1740,44 @@ int ludvm_ensemble_run_surveyed_graded(ludvm_ctx* c, size_t members, int npan, i
   return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
                            snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
                            shift_rows, probe_u, probe_w, tr, sv);
+}
+
+int ludvm_ensemble_run_integrals(ludvm_ctx* c, size_t members, int npan, int ncoef, const double* scalars, size_t scalar_count,
+                                 const double* tables, const double* kin, size_t kin_rows, const double* init,
+                                 const double* free_xzg, size_t free_count, const long long* desc, const long long* snap_steps,
+                                 size_t nsnap, double* rows, size_t rows_count, double* wakes, size_t wake_doubles,
+                                 long long* wake_n, const double* probe_x, const double* probe_z, size_t nprobe,
+                                 const double* shift_x, size_t shift_rows, double* probe_u, double* probe_w, const double* seed_x,
+                                 const double* seed_z, const long long* release, size_t ntracer, const double* tshift_x,
+                                 size_t tshift_rows, const long long* trec_steps, size_t ntrec, double* tracer_rows,
+                                 size_t tracer_doubles, const double* survey_x, const double* survey_z, size_t nsurvey,
+                                 const double* sshift_x, size_t sshift_rows, long long first, long long stop, long long every,
+                                 double* survey_sums, size_t survey_doubles, const int* bin_of_step, size_t bin_rows, int nbins,
+                                 double* bin_sums, size_t bin_doubles, double* grad_sums, size_t grad_doubles,
+                                 double* bin_grad_sums, size_t bin_grad_doubles, double* integral_sums, size_t integral_doubles,
+                                 double* energy, size_t energy_doubles, long long energy_first, long long energy_stop,
+                                 long long energy_every) {
+  EnsembleTracerArgs tr;
+  tr.seed_x = seed_x; tr.seed_z = seed_z; tr.release = release; tr.count = ntracer;
+  tr.shift_x = tshift_x; tr.shift_rows = tshift_rows;
+  tr.rec_steps = trec_steps; tr.nrec = ntrec;
+  tr.rows = tracer_rows; tr.doubles = tracer_doubles;
+  EnsembleSurveyArgs sv;
+  sv.x = survey_x; sv.z = survey_z; sv.count = nsurvey;
+  sv.shift_x = sshift_x; sv.shift_rows = sshift_rows;
+  sv.first = first; sv.stop = stop; sv.every = every;
+  sv.sums = survey_sums; sv.doubles = survey_doubles;
+  sv.bin_of_step = bin_of_step; sv.bin_rows = bin_rows; sv.nbins = nbins;
+  sv.bin_sums = bin_sums; sv.bin_doubles = bin_doubles;
+  sv.grad_sums = grad_sums; sv.grad_doubles = grad_doubles;
+  sv.bin_grad_sums = bin_grad_sums; sv.bin_grad_doubles = bin_grad_doubles;
+  EnsembleIntegralArgs ig;
+  ig.sums = integral_sums; ig.doubles = integral_doubles;
+  ig.energy = energy; ig.energy_doubles = energy_doubles;
+  ig.first = energy_first; ig.stop = energy_stop; ig.every = energy_every;
+  return ensemble_run_body(c, members, npan, ncoef, scalars, scalar_count, tables, kin, kin_rows, init, free_xzg, free_count, desc,
+                           snap_steps, nsnap, rows, rows_count, wakes, wake_doubles, wake_n, probe_x, probe_z, nprobe, shift_x,
+                           shift_rows, probe_u, probe_w, tr, sv, ig);
 }
 
 }  // extern "C"

@@ -789,9 +789,31 @@ class Engine:
                                        free_xzg, desc, snap_steps, survey_x, survey_z, survey_steps, survey_shift_x, seed_x, seed_z,
                                        release, shift_x, record_steps, probe_x, probe_z, probe_shift_x, grad=True)
 
+    def ensemble_run_integrals(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps=(), *, energy_steps=None,
+                               survey_x=(), survey_z=(), survey_steps=(1, 0, 1), bin_of_step=None, nbins=0, grad=False,
+                               survey_shift_x=None, seed_x=(), seed_z=(), release=(), shift_x=None, record_steps=(), probe_x=None,
+                               probe_z=None, probe_shift_x=None):
+        """`ensemble_run_surveyed_graded` (survey, bins, gradient sums -- grad=True --, tracers and probes all optional) with the
+        wake integrals of every member accumulated inside the launch (ludvm_ensemble_run_integrals): in every step of a member the
+        count, sum G, sum G x, sum G z, sum G (x^2 + z^2), sum G^2 of its sources by class (FREE, TEV, LEV, BOUND) and sign, and --
+        energy_steps = (first, stop, every), None: no samples -- at the sampled steps W = 1/2 sum G_a psi(x_a) over them.
+        -> `ensemble_run_surveyed_graded`'s tuple (survey_sums None without a survey, grad_sums None without grad) with
+        integral_sums [rows of kin, 4, 2, 6] and energy [rows of kin] (None without energy_steps; NaN where not sampled) appended: a
+        member's time level i is row kin_off + i (row 0 is the caller's: zeros)."""
+        nbins = int(nbins)
+        if nbins < 0:
+            raise ValueError("ensemble_run_integrals: nbins >= 0")
+        table = np.ascontiguousarray(bin_of_step, dtype=np.intc).reshape(-1) if nbins else np.empty(0, dtype=np.intc)
+        win = None if energy_steps is None else tuple(int(v) for v in energy_steps)
+        if win is not None and len(win) != 3:
+            raise ValueError("ensemble_run_integrals: energy_steps = (first, stop, every)")
+        return self._ensemble_surveyed("ensemble_run_integrals", (table, nbins), npan, ncoef, scalars, tables, kin, init, free_xzg, desc,
+                                       snap_steps, survey_x, survey_z, survey_steps, survey_shift_x, seed_x, seed_z, release, shift_x,
+                                       record_steps, probe_x, probe_z, probe_shift_x, grad=bool(grad), integrals=(win,))
+
     def _ensemble_surveyed(self, who, bins, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, survey_x, survey_z,
                            survey_steps, survey_shift_x, seed_x, seed_z, release, shift_x, record_steps, probe_x, probe_z,
-                           probe_shift_x, grad=False):
+                           probe_shift_x, grad=False, integrals=None):
         if not hasattr(self._lib, "ludvm_" + who):
             raise LudvmHipError(_ffi.E_STATE, f"this build of the library has no ludvm_{who}")
         vx, vz = _f64(survey_x), _f64(survey_z)
@@ -812,10 +834,10 @@ class Engine:
                 raise ValueError(f"{who}: probe_x and probe_z must have the same length")
             probes = (px, pz, None if probe_shift_x is None else _f64(probe_shift_x))
         return self._ensemble(npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, (sx, sz, rel, sh, rec),
-                              (vx, vz, vsh, first, stop, every), bins, grad)
+                              (vx, vz, vsh, first, stop, every), bins, grad, integrals)
 
     def _ensemble(self, npan, ncoef, scalars, tables, kin, init, free_xzg, desc, snap_steps, probes, tracers=None, survey=None,
-                  bins=None, grad=False):
+                  bins=None, grad=False, integrals=None):
         npan, ncoef = int(npan), int(ncoef)
         desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, _ffi.ENSEMBLE_DESC)
         members = desc.shape[0]
@@ -848,6 +870,20 @@ class Engine:
                          rel.ctypes.data_as(pll), len(sx), _pd(tsh), 0 if tsh is None else len(tsh), rec.ctypes.data_as(pll), len(rec),
                          _pd(trows), trows.size, _pd(vx), _pd(vz), len(vx), _pd(vsh), 0 if vsh is None else len(vsh), first, stop,
                          every, _pd(sums), sums.size)
+                if integrals is not None:
+                    (win,), (table, nbins), K = integrals, bins, len(vx)
+                    bsums = np.zeros([members, nbins, 5, K]) if nbins else None
+                    gsums = np.zeros([members, 5, K]) if grad else None
+                    bgsums = np.zeros([members, nbins, 5, K]) if grad and nbins else None
+                    isums = np.zeros([kin.shape[0], 4, 2, 6])
+                    energy = None if win is None else np.empty(kin.shape[0])
+                    self._check(self._lib.ludvm_ensemble_run_integrals(
+                        *sargs, table.ctypes.data_as(POINTER(c_int)) if nbins else None, len(table), nbins, _pd(bsums),
+                        0 if bsums is None else bsums.size, _pd(gsums), 0 if gsums is None else gsums.size, _pd(bgsums),
+                        0 if bgsums is None else bgsums.size, _pd(isums), isums.size, _pd(energy), 0 if energy is None else energy.size,
+                        *(win or (0, 0, 0))))
+                    out = (rows, wakes, wake_n, trows) if probes is None else (rows, wakes, wake_n, trows, pu, pw)
+                    return out + (sums if K else None, bsums, gsums, bgsums, isums, energy)
                 if grad:
                     table, nbins = bins
                     K = len(vx)

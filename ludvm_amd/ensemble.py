@@ -2,7 +2,8 @@
 Engine.ensemble_run_probed / ludvm_ensemble_run_probed; with passive tracers Engine.ensemble_run_traced /
 ludvm_ensemble_run_traced; with a wake survey Engine.ensemble_run_surveyed / ludvm_ensemble_run_surveyed; with a phase-locked
 one Engine.ensemble_run_surveyed_binned / ludvm_ensemble_run_surveyed_binned; with the survey's gradient sums
-Engine.ensemble_run_surveyed_graded / ludvm_ensemble_run_surveyed_graded).
+Engine.ensemble_run_surveyed_graded / ludvm_ensemble_run_surveyed_graded; with wake integrals Engine.ensemble_run_integrals /
+ludvm_ensemble_run_integrals).
 
 A reduced-order model is run many times -- calibrate LESPcrit, sweep k, alpha_max, phi, dt, move a gust vortex, switch
 'Faure' / 'Ramesh'.  Each such run on its own is a chain of tiny dependent launches that leaves the GPU idle; the members of
@@ -27,8 +28,8 @@ __all__ = ["sweep"]
 _BINS_SOLO = ("the bins of a sweep are common to it: sweep(cases, survey=..., survey_phases=...) -- survey_bins / survey_period / "
               "survey_phase0 belong to a solo run, LUDVM(..., survey=..., survey_bins=...)")
 
-_INTEGRALS_SOLO = ("the wake integrals are a solo keyword: a sweep carries none (run the member on its own, "
-                   "LUDVM(..., wake_integrals=True))")
+_INTEGRALS_SOLO = ("the wake integrals are a solo keyword: the integrals of a sweep are common to it -- sweep(cases, integrals=True, "
+                   "energy_steps=...) (or run the member on its own, LUDVM(..., wake_integrals=True))")
 
 _REFUSED = {
     # keyword -> (value that is fine, why not otherwise)
@@ -68,7 +69,7 @@ def _check_case(idx, kw, first):
     """Everything that can be refused from the keywords alone (no device, no engine call)."""
     who = f"sweep: member {idx}: "
     for key in ("engine", "device", "snapshot_steps", "verbose", "probes", "probe_frame", "particles", "particle_release",
-                "particle_frame", "particle_steps", "survey_phases", "survey_grad"):
+                "particle_frame", "particle_steps", "survey_phases", "survey_grad", "integrals", "energy_steps"):
         if key in kw:
             raise ValueError(who + f"`{key}` belongs to the sweep, not to a member")
     if "survey_precision" in kw:
@@ -283,9 +284,28 @@ def _check_sweep_grad(survey_grad, surveyed, binned, merged):
     return True
 
 
+def _check_sweep_integrals(integrals, energy_steps, merged):
+    """The sweep's `integrals` / `energy_steps` -> None without integrals, else (the energy window (first, stop, every) as given, or
+    None without samples,); refused from the keywords alone."""
+    if not isinstance(integrals, (bool, np.bool_)):
+        raise ValueError(f"sweep: integrals={integrals!r}: integrals must be True or False")
+    try:
+        win = LUDVM._check_wake_integrals(bool(integrals), energy_steps)
+    except ValueError as e:
+        raise ValueError("sweep: " + str(e).replace("wake_energy_steps", "energy_steps").replace("wake_integrals", "integrals")) from e
+    if not integrals:
+        return None
+    for idx, kw in enumerate(merged):
+        nt = _time_levels(kw)
+        if win is not None and min(win[1], nt) <= win[0]:
+            raise ValueError(f"sweep: member {idx}: energy_steps: the window [{win[0]}, {min(win[1], nt)}) holds no time step of "
+                             f"its {nt - 1}")
+    return (win,)
+
+
 def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe_frame="lab", particles=None, particle_release=None,
           particle_frame="lab", particle_steps=None, survey=None, survey_frame="lab", survey_steps=None, survey_phases=None, survey_grad=False,
-          verbose=False, cls=LUDVM,
+          integrals=False, energy_steps=None, verbose=False, cls=LUDVM,
           **common):
     """Run `cases` -- a list of dicts of LUDVM constructor keywords, each merged over `common` -- as ONE device launch and
     return the list of LUDVM objects, in order.  Each carries what a solo
@@ -346,6 +366,21 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     bit-identical to the sweep without survey_grad, and bin b's gradient block is bit for bit the gradient sums of a sweep that
     samples exactly bin b's steps.  A sweep without it makes the engine calls it made before.
 
+    integrals: False, or True for the wake integrals of every member, the sweep-level form of LUDVM(..., wake_integrals=True,
+    wake_energy_steps=) (which stay solo keywords and are refused here), with energy_steps = (first, stop, every) in survey_steps'
+    form, None: no energy samples.  In every step of a member the six moments -- count, sum G, sum G x, sum G z, sum G (x^2 + z^2),
+    sum G^2 -- of its vortex system (the sources its probes see: wake before the Euler update, the step's shed vortices, the bound
+    vortices) by class ('FREE', 'TEV', 'LEV', 'BOUND') and sign are accumulated inside the member's workgroup, in float64, and at the
+    sampled steps (first <= i < min(stop, its nt), (i - first) % every == 0) W = 1/2 sum G_a psi(x_a) over the same sources with the
+    member's own v_core: an O((n + Npoints - 1)^2) float64 pair sum with a logarithm per pair inside ONE workgroup (a member at the
+    8192-vortex limit: about 7e7 pairs per sample), so sample sparingly.  Every member carries the attributes of a solo run with
+    wake_integrals=True, formed by the solo code: `wake_integrals` (True), `wake_energy_steps` (stop clipped to its nt),
+    `integral_sums` [nt, 4, 2, 6] (row 0: its free vortices), `wake_energy` [nt] (NaN where not sampled), and `wake_circulation`,
+    `wake_centroid`, `wake_impulse`, `wake_angular_impulse`, `impulse_force`, `impulse_Cl`, `impulse_Cd`, `wake_energy_interaction`.
+    Composes with `probes`, `particles`, `survey`, `survey_phases` and `survey_grad` in one launch; everything else a member returns
+    is bit-identical to the sweep without integrals, a member's rows do not depend on the batch, and a sampled step's W does not
+    depend on the window.  A sweep without it makes the engine calls it made before.
+
     Npoints (3 .. 257) and Ncoeffs (4 .. 64) are common to a sweep; everything else may differ per member (dt, tf, method, LESPcrit, the section,
     kinematics, free vortices).  Refused with ValueError before any device work, naming the member: differing Npoints / Ncoeffs, or ones outside those ranges,
     a member over the limits (2048 steps, 8192 wake vortices: run it on its own), precision other than 'auto' / 'f64',
@@ -366,9 +401,12 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     `survey_phase0` anywhere, an engine without ensemble_run_surveyed_binned, and plain and bin sums (40 bytes x members x (B + 1)
     x K) over 1 GiB: split the case list; `survey_grad` inside a member's dict, without `survey`, a value that is not a bool
     ('f32x2': a sweep's sums are float64), an engine without ensemble_run_surveyed_graded, and plain, bin and gradient sums (80
-    bytes x members x (B + 1) x K) over 1 GiB: split the case list.
+    bytes x members x (B + 1) x K) over 1 GiB: split the case list; `integrals` / `energy_steps` inside a member's dict,
+    `wake_integrals` / `wake_energy_steps` anywhere (solo keywords: use `integrals=`), an `integrals` that is not a bool,
+    energy_steps without integrals=True, not three integers with first >= 1 and every >= 1, or holding no step of some member
+    (named), and an engine without ensemble_run_integrals.
 
-    Out of scope: per-member probe, seed or survey point sets and windows, harmonic sums of a survey in a sweep, hi+lo fp32 gradient sums in a sweep, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
+    Out of scope: per-member probe, seed or survey point sets and windows, per-member energy windows, an fp32 or hi+lo fp32 wake energy, an energy walk that visits each pair once, wake integrals of a sweep on several GPUs, harmonic sums of a survey in a sweep, hi+lo fp32 gradient sums in a sweep, tracers or a survey of a sweep on several GPUs, fp32 tracer or survey sums in a sweep (a solo run has tracer_precision='f32x2' and survey_precision='f32'), fp32 members, dense history, checkpoint / resume of a sweep, sweeps over several GPUs (members are independent:
     split the list per device), members above the limits; a solo run executes exactly as before."""
     if "survey_precision" in common:
         raise ValueError(f"sweep: survey_precision={common['survey_precision']!r}: the survey of a sweep is evaluated in float64 "
@@ -403,6 +441,7 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     surveyed = _check_sweep_survey(survey, survey_frame, survey_steps, merged)
     binned = _check_sweep_phases(survey_phases, surveyed, merged)
     graded = _check_sweep_grad(survey_grad, surveyed, binned, merged)
+    integrated = _check_sweep_integrals(integrals, energy_steps, merged)
     if engine is None:
         from .engine import Engine
         engine = Engine(device)
@@ -418,6 +457,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         raise ValueError("sweep: survey_phases: this engine has no ensemble_run_surveyed_binned")
     if graded and not hasattr(engine, "ensemble_run_surveyed_graded"):
         raise ValueError("sweep: survey_grad: this engine has no ensemble_run_surveyed_graded")
+    if integrated is not None and not hasattr(engine, "ensemble_run_integrals"):
+        raise ValueError("sweep: integrals: this engine has no ensemble_run_integrals")
     snaps = sorted({int(s) for s in snapshot_steps})
     dev_snaps = [s for s in snaps if s >= 1]
     if len(dev_snaps) > _ffi.ENSEMBLE_MAX_SNAPSHOTS:
@@ -431,6 +472,8 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
     nrec = len(dev_snaps) + 1
     for idx, kw in enumerate(merged):
         kw = dict(kw, precision="f64", history="sparse")
+        if integrated is not None:      # (the solo constructor and _loop_begin: the attributes, row 0, the window clipped to nt)
+            kw.update(wake_integrals=True, wake_energy_steps=integrated[0])
         sim = cls(**kw, engine=engine, snapshot_steps=snaps, verbose=False, run=False)
         if sims and (sim.Npoints, sim.Ncoeffs) != (sims[0].Npoints, sims[0].Ncoeffs):       # (a .dat section sets its own)
             raise ValueError(f"sweep: member {idx}: Npoints / Ncoeffs differ from member 0's: they are common to a sweep")
@@ -476,7 +519,22 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
         trec = [s for s in (dev_snaps if traced[2] is None else traced[2]) if 1 <= s <= max(sim.nt for sim in sims) - 1]
         targs = dict(seed_x=traced[0][0], seed_z=traced[0][1], release=traced[1], record_steps=trec,
                      shift_x=np.concatenate(shift) if particle_frame == "tunnel" else None)
-    if surveyed is not None:
+    if integrated is not None:
+        # (every observer is optional in this call; the energy window as given: the device clips it to each member's nt)
+        targs["energy_steps"] = integrated[0]
+        if surveyed is not None:
+            targs.update(survey_x=surveyed[0][0], survey_z=surveyed[0][1], survey_steps=surveyed[2],
+                         survey_shift_x=np.concatenate(shift) if survey_frame == "tunnel" else None, grad=graded)
+            if binned is not None:
+                targs.update(bin_of_step=np.concatenate(binned[0]), nbins=binned[1])
+        if probe_xz is not None:
+            targs.update(probe_x=probe_xz[0], probe_z=probe_xz[1], probe_shift_x=np.concatenate(shift) if probe_frame == "tunnel" else None)
+        *out, ssums, bsums, gsums, bgsums, isums, wsums = engine.ensemble_run_integrals(*packed, **targs)
+        if probe_xz is not None:
+            rows, wakes, wake_n, trows, pu, pw = out
+        else:
+            rows, wakes, wake_n, trows = out
+    elif surveyed is not None:
         # (the window as given: the device clips it to each member's nt)
         targs.update(survey_x=surveyed[0][0], survey_z=surveyed[0][1], survey_steps=surveyed[2],
                      survey_shift_x=np.concatenate(shift) if survey_frame == "tunnel" else None)
@@ -532,6 +590,10 @@ def sweep(cases, *, engine=None, device=0, snapshot_steps=(), probes=None, probe
             if graded:
                 sim.survey_gradient = True
                 sim._survey_gradient_results(gsums[idx], None if binned is None else bgsums[idx])
+        if integrated is not None:          # (row 0 and the NaN of the energy are _loop_begin's, as in a solo run)
+            sim.integral_sums[1:] = isums[k0 + 1:k0 + nt]
+            if wsums is not None:
+                sim.wake_energy[1:] = wsums[k0 + 1:k0 + nt]
         cap = nf + 2 * (nt - 1)
         R = rows[r0:r0 + nt - 1]
         hist = _RecordedWakes()

@@ -37,7 +37,14 @@ What the gradient sums of a survey in a sweep cost: the unsurveyed
 config 1 at K = 256 and K = 4096 (every step sampled) on the parent build and on this one, alternated -- the same kernels --
 and, on this build, the same call with the gradient sums (ludvm_ensemble_run_surveyed_graded): per call, per sampled step, and
 the survey phase alone (the call less the unsurveyed call) against the plain survey phase.  With --bins B also the binned call
-and the graded call with every step in one of B phase bins."""
+and the graded call with every step in one of B phase bins.
+
+    python tools/ensemble_throughput.py --integrals-leg [--parent-lib _ab/libludvm_hip_parent.so] > profiles/ensemble_integrals_cost.txt
+What the wake integrals of a sweep cost: the device call of 256 copies of config 1, packed once, (a) without
+integrals on the parent build and on this one, alternated -- the same kernel --, (b) with the moments of every step
+(ludvm_ensemble_run_integrals): the added time per member-step, and (c) with the energy sampled every 10th step beside them: the
+added time per sample, and pairs per second of the one-workgroup psi walk against the solo march_energy_partial figure of DESIGN
+4.22 (3.8e11 pairs/s)."""
 import argparse
 import os
 import sys
@@ -58,6 +65,7 @@ ap.add_argument("--particles-leg", action="store_true", help="the cost of passiv
 ap.add_argument("--survey-leg", action="store_true", help="the cost of a wake survey in a sweep instead of the size ladder")
 ap.add_argument("--bins", type=int, default=0, help="survey leg: the cost of B phase bins over the plain survey instead (0: the plain leg)")
 ap.add_argument("--grad", action="store_true", help="survey leg: the cost of the gradient sums over the plain (and, with --bins, the binned) survey instead")
+ap.add_argument("--integrals-leg", action="store_true", help="the cost of the wake integrals in a sweep instead of the size ladder")
 ap.add_argument("--parent-lib", default="", help="probes / particles / survey leg: a build of the parent commit, timed beside this one")
 a = ap.parse_args()
 
@@ -548,6 +556,84 @@ def survey_grad_leg(nbins):
             print(f"{name} device call against the parent build: NOT MEASURED (no --parent-lib given)")
 
 
+def integrals_leg():
+    """Device call only: B = 256 copies of config 1 packed once; plain (both builds), with the moments, with moments and energy."""
+    B = 256
+    kept = {}
+    plain_call = inner
+
+    def keep(*args, **kw):
+        kept[len(args[7])] = args
+        return plain_call(*args, **kw)
+    eng.ensemble_run = keep
+    sims = sweep([dict(CONFIG1)] * B, engine=eng)
+    del eng.ensemble_run
+    engines = {"this build": eng}
+    if a.parent_lib:
+        engines["parent build"] = Engine(0, lib_path=os.path.abspath(a.parent_lib))
+    packed, s1 = kept[B], sims[0]
+    win = (1, s1.nt, 10)
+    sampled = np.arange(win[0], s1.nt, win[2])
+    ns = s1.n_freevort + np.arange(s1.nt) + np.cumsum(s1.LEV_shed != -1) + (s1.Npoints - 1)       # sources behind step i's solve
+    pairs = int((ns[sampled].astype(np.int64) ** 2).sum())
+
+    def variant(which, kind):
+        e = engines[which]
+        if kind == "plain":
+            return lambda: e.ensemble_run(*packed)
+        return lambda: e.ensemble_run_integrals(*packed, energy_steps=win if kind == "energy" else None)
+    builds = (["parent build"] if a.parent_lib else []) + ["this build"]
+    order = [(w, "plain") for w in builds] + [("this build", "moments"), ("this build", "energy")]
+    calls = {v: variant(*v) for v in order}
+    reps_in = {}
+    for v, f in calls.items():                        # warm-up of every shape (buffers grow here)
+        f()
+        t0 = time.perf_counter()
+        f()
+        reps_in[v] = max(1, int(a.window / (time.perf_counter() - t0)))
+    T = {v: [] for v in order}
+    for _ in range(a.reps):                           # the variants alternated
+        for v, f in calls.items():
+            t0 = time.perf_counter()
+            for _ in range(reps_in[v]):
+                f()
+            T[v].append((time.perf_counter() - t0) / reps_in[v] * 1e3)
+    print("# integrals leg: device call (host clock around the synchronous entry point: uploads, ONE kernel, downloads) of 256 copies\n"
+          "# of config 1 packed once: plain, with the moments of every step, and with the energy every 10th step as well; ms per call,\n"
+          "# min / median / max over the windows and the build's own spread (max - min) / min")
+    base = np.median(T[("this build", "plain")])
+    mom = np.median(T[("this build", "moments")])
+    for v in order:
+        which, kind = v
+        t = np.array(T[v])
+        line = (f"{which:<13} B {B:4d}  {kind:<8} windows of {reps_in[v]:3d}  device call {t.min():9.3f} / {np.median(t):9.3f} / {t.max():9.3f}  "
+                f"spread {(t.max() - t.min()) / t.min() * 100:5.2f} %")
+        if kind == "moments":
+            added = np.median(t) - base
+            line += (f"\n{'':13} over the plain call of this build: {np.median(t) / base:.4f} x per call, added {added:9.3f} ms = "
+                     f"{added / (s1.nt - 1) * 1e3:8.3f} us per step (of every member, side by side) = "
+                     f"{added / (B * (s1.nt - 1)) * 1e6:8.3f} ns per member-step; rows returned {B * s1.nt * 48 * 8 / 2**20:.1f} MiB")
+        if kind == "energy":
+            added = np.median(t) - mom
+            line += (f"\n{'':13} over the call with the moments: {np.median(t) / mom:.4f} x per call, added {added:9.3f} ms for {len(sampled)} "
+                     f"samples of every member (sources {ns[sampled].min()} .. {ns[sampled].max()}) = {added / len(sampled) * 1e3:8.3f} us per "
+                     f"sample (of every member, side by side); {pairs} pairs per member, {B * pairs / (added * 1e-3):.3e} pairs/s over "
+                     f"{B} workgroups on {info['cu_count']} CUs, against 3.8e11 of the solo march_energy_partial (DESIGN 4.22): "
+                     f"{B * pairs / (added * 1e-3) / 3.8e11:.3f} x")
+        print(line, flush=True)
+    if a.parent_lib:
+        p, n = np.array(T[("parent build", "plain")]), np.array(T[("this build", "plain")])
+        print(f"plain device call, this build against the parent build: median {np.median(n) / np.median(p):.4f} x; the parent's own windows "
+              f"span {p.min():.3f} .. {p.max():.3f} ms, this build's {n.min():.3f} .. {n.max():.3f} ms: "
+              f"{'inside' if p.min() <= np.median(n) <= p.max() else 'OUTSIDE'} the parent's run-to-run spread")
+    else:
+        print("plain device call against the parent build: NOT MEASURED (no --parent-lib given)")
+
+
+if a.integrals_leg:
+    eng.ensemble_run = inner
+    integrals_leg()
+    sys.exit(0)
 if a.survey_leg:
     eng.ensemble_run = inner
     if a.grad:
